@@ -11,10 +11,18 @@ generated on the GPU before the timed region (generation is reported separately,
 Multi-GPU: one process per GPU (torchrun), independent env shards (no data-path collective),
 weak scaling; value = all ranks' env steps / max-over-ranks wall time.
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) does what the headline figure needs and no
+more: it generates the mazes, runs W untimed and K timed steps of the headline leg, writes the
+last timed step's outputs if --dump-outputs DIR is given (dump_outputs) and prints the JSON line.
+--full adds, after that, everything else this file measures: the eager launch loop beside the
+graph replays, the bits-mode leg, steady-state generation, cpu_baseline, the DDQN win-rate leg
+with q_head, the curriculum legs and the config legs (their JSON fields are null / absent in a
+plain run).
+
 Extra JSON fields: roofline of k_step (one HIP event pair on the launch stream around the whole
 timed region — one k_step launch per step, so elapsed / steps is its average launch duration
 including the back-to-back launch gap; a pair around every launch would drain the queue each
-time and add ~3 us), cpu_baseline (the CPU oracle in reference-cost mode, A* per
+time and add ~3 us), with --full cpu_baseline (the CPU oracle in reference-cost mode, A* per
 find_path, timed on host cores — rank 0, N=1 only).
 """
 import argparse
@@ -69,6 +77,15 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=100)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline leg also run everything else this file measures: the "
+                         "eager launch loop, the bits-mode leg, steady-state generation, "
+                         "cpu_baseline, the DDQN win-rate leg and q_head, the curriculum legs and "
+                         "the config legs (each still governed by its own option). Without it only "
+                         "the headline env-step leg runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of the headline leg returned (step_act's "
+                         "outputs) as DIR/<name>.npy, see dump_outputs()")
     ap.add_argument("--envs", type=int, default=65536, help="instances per GPU")
     ap.add_argument("--dim", type=int, default=81)
     ap.add_argument("--algo", default="r-prim")
@@ -939,6 +956,46 @@ def cpu_baseline(env, seconds):
             "bfs_field_mode": {"value": nf / tf, "steps": nf, "seconds": round(tf, 2)}}
 
 
+DUMP_WINDOW_ROWS = 4096  # instances whose f32 window is dumped (675 floats each: 11 MB at most)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(env, path, rank=0):
+    """--dump-outputs: what a caller of the timed path holds after its last timed step, i.e.
+    step_act's outputs (the observation, reward, truncated, terminated) and the actions it took,
+    as <path>/<name>.npy (rank r > 0: <name>.rank<r>.npy). The mazes, the seeds and the Philox
+    counters are fixed by the arguments, so two builds run with the same arguments write arrays
+    that can be compared element for element.
+      obs6, reward, terminated, truncated, actions   every instance, float32
+      window_bits                                    every instance, float64 (exact int32 words)
+      window                                         float32, the instances listed in window_rows
+      window_rows                                    float64: all instances up to 4,096, above
+                                                     that a fixed seeded sample of 4,096 (sorted)
+    Called straight after the timed region (the stream is idle); at most 64 MB in all."""
+    import numpy as np
+    import torch
+    B = env.num_envs
+    out = {"obs6": env.obs6.float(), "reward": env.reward.float(),
+           "terminated": env.terminated.float(), "truncated": env.truncated.float(),
+           "actions": env.actions.float()}
+    if env.window_bits is not None:
+        out["window_bits"] = env.window_bits.double()
+    if env.window is not None:
+        rows = np.arange(B) if B <= DUMP_WINDOW_ROWS else \
+            np.sort(np.random.RandomState(0xD0F5).permutation(B)[:DUMP_WINDOW_ROWS])
+        idx = torch.from_numpy(rows).to(env.window.device)
+        out["window"] = env.window.index_select(0, idx)
+        out["window_rows"] = torch.from_numpy(rows.astype(np.float64))
+    arrays = {k: v.cpu().numpy() for k, v in out.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(path, exist_ok=True)
+    suffix = f".rank{rank}" if rank else ""
+    for k, v in arrays.items():
+        np.save(os.path.join(path, f"{k}{suffix}.npy"), v)
+    return total
+
+
 def main():
     a = parse()
     if needs_launch(a, os.environ):
@@ -965,6 +1022,9 @@ def main():
     import mazerl
     B = a.envs
     legs = [x for x in a.legs.split(",") if x]
+    head_mode = "window" if "window" in legs else legs[0]
+    if not a.full:
+        legs = [head_mode]  # a plain run: the headline leg and nothing beside it
 
     def leg(mode):
         """One env-step leg: generate B mazes (global instance ids rank*B.. : Philox seed
@@ -1025,8 +1085,12 @@ def main():
                 g.replay()
         el, avg_kernel_ms = timed(lambda: [g.replay() for g in graphs] if graphs else
                                   [vstep(a.warmup + k) for k in range(a.steps)])
+        if a.dump_outputs and mode == head_mode:
+            n_b = dump_outputs(env, a.dump_outputs, rank)
+            if rank == 0:
+                log(f"outputs of the last timed step: {n_b} bytes under {a.dump_outputs}")
         eager = None
-        if graphs:  # the same K steps as K eager launches from the Python loop, for comparison
+        if graphs and a.full:  # the same K steps as K eager launches from the Python loop
             el_e, avg_e = timed(lambda: [vstep(a.warmup + k) for k in range(a.steps)])
             eager = {"value": B * a.steps * world / el_e, "ms_per_step": el_e / a.steps * 1e3,
                      "avg_kernel_ms": avg_e}
@@ -1052,14 +1116,15 @@ def main():
         if rank == 0:
             log(f"env-step leg: {mode}")
         env, res[mode] = leg(mode)
-    head = res["window"] if "window" in res else res[legs[0]]
+    head = res[head_mode]
     value, gen_s = head["value"], head["gen_s"]
     stream = torch.cuda.current_stream(dev)
 
-    # steady-state regeneration of all B mazes per algorithm (after the timed region; the module
-    # is loaded): one mz_generate launch each, HIP events on the launch stream
+    # --full: steady-state regeneration of all B mazes per algorithm (after the timed region; the
+    # module is loaded): one mz_generate launch each, HIP events on the launch stream
     steady = {}
-    for algo in ("dfs", "prim&kill", "r-prim"):  # r-prim last: cpu_baseline reads maze 0
+    # r-prim last: cpu_baseline reads maze 0
+    for algo in ("dfs", "prim&kill", "r-prim") if a.full else ():
         g0, g1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         g0.record(stream)
         env.generate(algorithm=algo, seed=0x6E4E0000 + rank * B)
@@ -1079,6 +1144,7 @@ def main():
                        else ("torchrun / external launcher" if world > 1 else "single process")),
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": bool(a.full),
             "ms_per_step": head["ms_per_step"],
             "higher_is_better": True,
             "scaling": "weak",
@@ -1099,30 +1165,30 @@ def main():
                           if "bits" in res and "window" in res else None),
             "generation": {"mazes": B, "seconds": round(gen_s, 3), "mazes_per_s": B / gen_s,
                            "note": "first build incl. module load; excluded from value",
-                           "steady_mazes_per_s": steady,
+                           "steady_mazes_per_s": steady or None,
                            "steady_note": f"per GPU: all {B} {a.dim}x{a.dim} mazes regenerated in one "
                                           "launch per algorithm (generation + BFS tables + goal)"},
             "win_rate": None,
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             log("cpu_baseline")
             out["cpu_baseline"] = cpu_baseline(env, a.cpu_seconds)
     env.close()
-    if a.train_steps > 0:
+    if a.full and a.train_steps > 0:
         if rank == 0:
             log("DDQN win-rate leg (configs[2])")
         wr = win_rate(a, dev, rank, world)  # every rank trains its shard (grad all-reduce)
         if rank == 0:
             out["win_rate"] = wr
             out["q_head"] = q_head(dev, B)
-    if a.curriculum_steps > 0:
+    if a.full and a.curriculum_steps > 0:
         for j, rule in enumerate(x for x in a.curriculum_rules.split(",") if x):
             if rank == 0:
                 log(f"DDQN curriculum leg, {rule} rule (the reference's new-maze protocol)")
             cl = curriculum_leg(a, dev, rank, world, rule)
             if rank == 0:
                 out["curriculum_leg" if j == 0 else "curriculum_leg_" + rule.replace("-", "_")] = cl
-    if a.config_legs:
+    if a.full and a.config_legs:
         cl = config_legs(a, dev, rank, world)
         if rank == 0:
             out["configs"] = cl

@@ -12,7 +12,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 export PYTHONPATH="$GRAFT_REPO_ROOT/maze-solving-agent-gymnasium_amd:$PYTHONPATH"
 O=gpurun_out/prof
 mkdir -p $O
-ARGS="--steps 300 --warmup 30 --train-steps 0 --curriculum-steps 0 --config-legs= --no-cpu-baseline"
+ARGS="--full --steps 300 --warmup 30 --train-steps 0 --curriculum-steps 0 --config-legs= --no-cpu-baseline"
 # the kernel trace with the bench's captured-graph replays; the counter passes with eager launches
 # (the same k_step launch, one dispatch at a time under counter collection)
 for leg in window bits; do

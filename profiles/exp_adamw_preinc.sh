@@ -16,6 +16,6 @@ timeout -k 10 600 python3 -u -m pytest tests/test_flat_optim.py tests/test_learn
 tail -1 $O/tests.log
 for v in default aw_ticket qw8 rd1 default aw_ticket qw8 rd1; do
   lib=$D; [ $v = default ] || lib=$PWD/profiles/_bin/$v.so
-  MZ_LIB_OVERRIDE=$lib timeout -k 10 300 python3 -u bench.py --steps 10 --warmup 2 --no-cpu-baseline --eval-mazes 200 --legs bits > $O/bench_$v.json
+  MZ_LIB_OVERRIDE=$lib timeout -k 10 300 python3 -u bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --eval-mazes 200 --legs bits > $O/bench_$v.json
   python3 -c "import json; d=json.load(open('$O/bench_$v.json')); w=d['win_rate']; print(json.dumps({'lib': '$v', 'train_env_steps_per_s': w['train_env_steps_per_s'], 'greedy': w['greedy']}))" >> $O/train.jsonl
 done

@@ -16,7 +16,7 @@ for v in default 1 2 4 7; do
 done
 for v in default bank1024 bank512 bank2048 default bank1024 bank512; do
   lib=$D; [ $v = default ] || lib=$B/gen_$v.so
-  MZ_LIB_OVERRIDE=$lib timeout -k 10 300 python3 -u bench.py --steps 10 --warmup 2 --no-cpu-baseline --eval-mazes 200 --legs bits > $O/bench_$v.json
+  MZ_LIB_OVERRIDE=$lib timeout -k 10 300 python3 -u bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --eval-mazes 200 --legs bits > $O/bench_$v.json
   python3 -c "import json; d=json.load(open('$O/bench_$v.json')); w=d['win_rate']; print(json.dumps({'lib': '$v', 'train_env_steps_per_s': w['train_env_steps_per_s'], 'greedy': w['greedy']}))" >> $O/train.jsonl
 done
 # (3) the same caps in config 5 (PPO, 4,096 toroidal 17..79: square-grid builds, 35 KB each)

@@ -21,8 +21,8 @@ done
 for v in ${TRAIN_VARIANTS:-default tree_rd1 bfs default bfs}; do
   lib=$PWD/maze-solving-agent-gymnasium_amd/mazerl/_lib/libmazerl.so
   [ $v = default ] || lib=$B/gen_$v.so
-  MZ_LIB_OVERRIDE=$lib timeout -k 10 300 python3 -u bench.py --steps 10 --warmup 2 --no-cpu-baseline --eval-mazes 200 > $O/bench_$v.json
+  MZ_LIB_OVERRIDE=$lib timeout -k 10 300 python3 -u bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --eval-mazes 200 > $O/bench_$v.json
   python3 -c "import json; d=json.load(open('$O/bench_$v.json')); w=d['win_rate']; print(json.dumps({'lib': '$v', 'train_env_steps_per_s': w['train_env_steps_per_s'], 'greedy': w['greedy'], 'gen': d['generation']['steady_mazes_per_s']}))" >> $O/train.jsonl
 done
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/kt -o run -- python3 bench.py --steps 10 --warmup 2 --train-steps ${TRACE_STEPS:-300} --no-cpu-baseline --eval-mazes 64 > $O/kt.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/kt -o run -- python3 bench.py --full --steps 10 --warmup 2 --train-steps ${TRACE_STEPS:-300} --no-cpu-baseline --eval-mazes 64 > $O/kt.log 2>&1
 for f in $(find $O/kt -name '*kernel_trace.csv'); do python3 profiles/train_streams.py $f > $O/train_streams.json; done

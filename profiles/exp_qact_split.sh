@@ -9,6 +9,6 @@ done
 for rep in 1 2; do
   for lib in default profiles/_bin/lib_qact_fused.so; do
     if [ "$lib" = default ]; then unset MZ_LIB_OVERRIDE; else export MZ_LIB_OVERRIDE=$lib; fi
-    timeout -k 10 300 python -u bench.py --legs bits --steps 50 --warmup 5 --no-cpu-baseline --config-legs '' --eval-mazes 200 > $out/bench_${rep}_$(basename $lib).json 2>> $out/bench.err || exit 1
+    timeout -k 10 300 python -u bench.py --full --legs bits --steps 50 --warmup 5 --no-cpu-baseline --config-legs '' --eval-mazes 200 > $out/bench_${rep}_$(basename $lib).json 2>> $out/bench.err || exit 1
   done
 done

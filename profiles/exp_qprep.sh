@@ -14,7 +14,7 @@ timeout -k 10 900 python3 -u -m pytest tests -m gpu -x -q --timeout 300 --timeou
 tail -1 $O/gpu_tests.log
 for v in default qact2_64 qprep_old default qact2_64 qprep_old; do
   lib=$D; [ $v = default ] || lib=$PWD/profiles/_bin/$v.so
-  MZ_LIB_OVERRIDE=$lib timeout -k 10 300 python3 -u bench.py --steps 10 --warmup 2 --no-cpu-baseline --eval-mazes 200 --legs bits > $O/bench_$v.json
+  MZ_LIB_OVERRIDE=$lib timeout -k 10 300 python3 -u bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --eval-mazes 200 --legs bits > $O/bench_$v.json
   python3 -c "import json; d=json.load(open('$O/bench_$v.json')); w=d['win_rate']; q=d['q_head']['x3']; print(json.dumps({'lib': '$v', 'train_env_steps_per_s': w['train_env_steps_per_s'], 'greedy': w['greedy'], 'qhead_all_ms': q['all_rows']['ms'], 'qhead_greedy_ms': q['greedy_rows']['ms'], 'greedy_rows': q['greedy_rows']['rows']}))" >> $O/train.jsonl
 done
 bash profiles/collect.sh

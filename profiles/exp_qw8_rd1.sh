@@ -10,6 +10,6 @@ mkdir -p $O
 D=$PWD/maze-solving-agent-gymnasium_amd/mazerl/_lib/libmazerl.so
 for v in default qw8 rd1 default qw8 rd1 default qw8; do
   lib=$D; [ $v = default ] || lib=$PWD/profiles/_bin/$v.so
-  MZ_LIB_OVERRIDE=$lib timeout -k 10 300 python3 -u bench.py --steps 10 --warmup 2 --no-cpu-baseline --eval-mazes 200 --legs bits > $O/bench_$v.json
+  MZ_LIB_OVERRIDE=$lib timeout -k 10 300 python3 -u bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --eval-mazes 200 --legs bits > $O/bench_$v.json
   python3 -c "import json; d=json.load(open('$O/bench_$v.json')); w=d['win_rate']; q=d['q_head']['x3']; print(json.dumps({'lib': '$v', 'train_env_steps_per_s': w['train_env_steps_per_s'], 'greedy': w['greedy'], 'qhead_all_ms': q['all_rows']['ms']}))" >> $O/train.jsonl
 done

@@ -14,9 +14,9 @@ timeout -k 10 600 python3 -u -m pytest tests/test_gpu_env.py tests/test_bank.py 
 tail -1 $O/tests.log
 for v in default rd_head default rd_head; do
   lib=$D; [ $v = default ] || lib=$PWD/profiles/_bin/$v.so
-  MZ_LIB_OVERRIDE=$lib timeout -k 10 300 python3 -u bench.py --steps 10 --warmup 2 --no-cpu-baseline --eval-mazes 200 --legs bits > $O/bench_$v.json
+  MZ_LIB_OVERRIDE=$lib timeout -k 10 300 python3 -u bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --eval-mazes 200 --legs bits > $O/bench_$v.json
   python3 -c "import json; d=json.load(open('$O/bench_$v.json')); w=d['win_rate']; print(json.dumps({'lib': '$v', 'train_env_steps_per_s': w['train_env_steps_per_s'], 'greedy': w['greedy']}))" >> $O/train.jsonl
 done
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/kt -o run -- python3 bench.py --steps 10 --warmup 2 --train-steps 1200 --no-cpu-baseline --eval-mazes 64 --legs bits > $O/kt.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/kt -o run -- python3 bench.py --full --steps 10 --warmup 2 --train-steps 1200 --no-cpu-baseline --eval-mazes 64 --legs bits > $O/kt.log 2>&1
 for f in $(find $O/kt -name '*kernel_trace.csv'); do python3 profiles/train_streams.py $f > $O/train_streams.json; rm -f $f; done
 bash profiles/collect.sh
