@@ -668,6 +668,61 @@ int mz_qact(const uint32_t* bits_dev, const float* obs6_dev, const int32_t* rows
             const float* w3_dev, const float* b3_dev, int32_t relu, float drop_p, uint64_t seed,
             uint64_t counter, float* h1_dev, int64_t* greedy_dev, float* q_out_dev, void* stream);
 
+/* ---- Config 1 vectorised: a population of tabular Q-learners in HBM (mz_qtab.hip) ------------
+ * Replaces, per instance, QAgent (agents/q_agent.py:8-79: a dict of 4-entry float64 rows keyed
+ * by str(obs)) and the step / episode end of OffPolicyTrainer.train (lib/trainers/
+ * off_policy_trainer.py:28-80). n instances, one lane each, on the PLAIN observation obs6_dev
+ * [n][6] = (r, c, gr, gc, br, bc) as exact small integers in f32 (an enrich = 0 handle's obs6;
+ * 8-B aligned). Instance i learns on table table_of_dev[i] (NULL: table i, ntables == n) of
+ * q_dev [ntables][rows][4] float64 (16-B aligned, zero = the reference's fresh rows). Every
+ * hyper-parameter and counter is a per-table device array [ntables]. Entries of table_of_dev
+ * outside [0, ntables) make the instance idle (action -1, no update).
+ *
+ * Index layout: row = (((r * P + c) * P + gr) * P + gc) * 5 + k with P = max_dim, rows = 5 P^4
+ * (mz_qtab_states), k the best-dir class: 0 (0, 0); 1 down: br == -1 or br > 1; 2 up: br == 1 or
+ * br < -1; 3 right: bc == -1 or bc > 1; 4 left: bc == 1 or bc < -1 (|x| > 1 is the torus'
+ * wrapped neighbour, +-(N - 1)). Two observations of one env share a row iff their str(obs) keys
+ * are equal. Coordinates are clamped to [0, P), so no access leaves a table. */
+
+/* rows per table for pitch max_dim (5 <= max_dim <= MZ_MAX_DIM). */
+int mz_qtab_states(int32_t max_dim, int64_t* rows);
+
+/* QAgent.get_action (q_agent.py:44-54) for every instance: eps = final + (init - final) *
+ * exp(-1.0 * steps_done[t] / decay) in float64; draws mz_philox(seed, MZ_QTAB_STREAM ^ (i << 32),
+ * counter): u = (w0 >> 8) * 2^-24; u < eps -> action w1 >> 30 (action_space.sample(), uniform
+ * over 4; not mz_act's masked distribution), else the row's first maximum (np.argmax). Writes
+ * actions_dev (int32 [n], mz_step's input) and sidx_dev (int64 [n], the row acted from), then
+ * steps_done_dev[t] += the instances acting on t (never reset, like QAgent's). Instances with
+ * active_dev[i] == 0 (uint8 [n], NULL: all act) idle: action -1, row -1, not counted (an
+ * evaluation's instances whose episode is over). Two launches. */
+int mz_qtab_act(const float* obs6_dev, int32_t n, int32_t max_dim, const int32_t* table_of_dev,
+                int32_t ntables, const uint8_t* active_dev, const double* q_dev,
+                int64_t* steps_done_dev, const double* eps_init_dev, const double* eps_final_dev,
+                const double* eps_decay_dev, uint64_t seed, uint64_t counter, int32_t* actions_dev,
+                int64_t* sidx_dev, void* stream);
+
+/* QAgent.update (q_agent.py:56-73) after mz_step, obs6_dev now the next observation, in float64
+ * in this order: future = terminated ? 0 : max(Q[s']); td = (reward + gamma * future) - Q[s][a];
+ * Q[s][a] = Q[s][a] + lr * td. Then cum_dev[i] += reward and, on terminated | truncated,
+ * gamma[t] += cum > 0 ? eta : -eta (update_hyperparameter(cumulative > prev_cum_rew) with
+ * prev_cum_rew zeroed every episode, off_policy_trainer.py:32,77-78), cum = 0, episodes[t] += 1,
+ * wins[t] += terminated. episode_end == 0: QAgent.update alone — cum still sums, but no gamma
+ * drift and no counters (a caller that ends episodes itself, or never calls
+ * update_hyperparameter).
+ * table_of_dev NULL: one launch, plain stores. Otherwise (shared tables) two launches: every td
+ * of the step is computed from the table and gamma as they stood before the step (lr * td into
+ * td_dev, n float64, required), then applied with one native float64 global atomic add per
+ * instance — colliding updates add; gamma and the counters take atomic adds too. Disjoint rows
+ * give the bits of the one-launch form; colliding adds arrive in no fixed order, so their sum is
+ * bitwise reproducible only when the addends commute exactly. */
+int mz_qtab_update(const float* obs6_dev, int32_t n, int32_t max_dim, const int32_t* table_of_dev,
+                   int32_t ntables, double* q_dev, const int64_t* sidx_dev,
+                   const int32_t* actions_dev, const double* reward64_dev,
+                   const uint8_t* terminated_dev, const uint8_t* truncated_dev, double* gamma_dev,
+                   const double* lr_dev, const double* eta_dev, double* cum_dev,
+                   int64_t* episodes_dev, int64_t* wins_dev, double* td_dev, int32_t episode_end,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

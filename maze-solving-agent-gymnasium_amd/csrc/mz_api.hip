@@ -1475,3 +1475,73 @@ int mz_qact(const uint32_t* bits_dev, const float* obs6_dev, const int32_t* rows
   return MZ_OK;
 }
 
+
+// ---- vectorised tabular Q-learning (mz_qtab.hip) ----------------------------------------------
+int mz_qtab_states(int32_t max_dim, int64_t* rows) {
+  if (!rows) return fail(MZ_EINVAL, "null argument");
+  if (max_dim < 5 || max_dim > MZ_MAX_DIM)
+    return fail(MZ_EINVAL, "max_dim %d outside [5, %d]", max_dim, MZ_MAX_DIM);
+  const int64_t p = max_dim;
+  *rows = 5 * p * p * p * p;
+  return MZ_OK;
+}
+
+namespace {
+int qtab_check(const void* obs6, int32_t n, int32_t max_dim, const void* table_of, int32_t ntables,
+               const void* q) {
+  if (!q) return fail(MZ_EINVAL, "null Q-table");
+  if (!obs6) return fail(MZ_EINVAL, "null observation");
+  if (n <= 0) return fail(MZ_EINVAL, "n %d must be >= 1", n);
+  if (max_dim < 5 || max_dim > MZ_MAX_DIM)
+    return fail(MZ_EINVAL, "max_dim %d outside [5, %d]", max_dim, MZ_MAX_DIM);
+  if (ntables <= 0) return fail(MZ_EINVAL, "ntables %d must be >= 1", ntables);
+  if (!table_of && ntables != n)
+    return fail(MZ_EINVAL, "no table map: ntables %d must equal n %d", ntables, n);
+  if (reinterpret_cast<uintptr_t>(q) & 15) return fail(MZ_EALIGN, "Q-table must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(obs6) & 7) return fail(MZ_EALIGN, "obs6 must be 8-byte aligned");
+  return MZ_OK;
+}
+}  // namespace
+
+int mz_qtab_act(const float* obs6_dev, int32_t n, int32_t max_dim, const int32_t* table_of_dev,
+                int32_t ntables, const uint8_t* active_dev, const double* q_dev,
+                int64_t* steps_done_dev, const double* eps_init_dev, const double* eps_final_dev,
+                const double* eps_decay_dev, uint64_t seed, uint64_t counter, int32_t* actions_dev,
+                int64_t* sidx_dev, void* stream) {
+  if (int rc = qtab_check(obs6_dev, n, max_dim, table_of_dev, ntables, q_dev)) return rc;
+  if (!steps_done_dev || !eps_init_dev || !eps_final_dev || !eps_decay_dev || !actions_dev ||
+      !sidx_dev)
+    return fail(MZ_EINVAL, "null argument");
+  int64_t rows = 0;
+  mz_qtab_states(max_dim, &rows);
+  StreamGuard g(stream);
+  MzQtabAct a{obs6_dev, n, max_dim, table_of_dev, ntables, active_dev, q_dev, rows,
+              reinterpret_cast<const long long*>(steps_done_dev), eps_init_dev, eps_final_dev,
+              eps_decay_dev, seed, counter, actions_dev, sidx_dev};
+  MZ_HIP(mz_launch_qtab_act(a, reinterpret_cast<long long*>(steps_done_dev),
+                            static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_qtab_update(const float* obs6_dev, int32_t n, int32_t max_dim, const int32_t* table_of_dev,
+                   int32_t ntables, double* q_dev, const int64_t* sidx_dev,
+                   const int32_t* actions_dev, const double* reward64_dev,
+                   const uint8_t* terminated_dev, const uint8_t* truncated_dev, double* gamma_dev,
+                   const double* lr_dev, const double* eta_dev, double* cum_dev,
+                   int64_t* episodes_dev, int64_t* wins_dev, double* td_dev, int32_t episode_end,
+                   void* stream) {
+  if (int rc = qtab_check(obs6_dev, n, max_dim, table_of_dev, ntables, q_dev)) return rc;
+  if (!sidx_dev || !actions_dev || !reward64_dev || !terminated_dev || !truncated_dev ||
+      !gamma_dev || !lr_dev || !eta_dev || !cum_dev || !episodes_dev || !wins_dev)
+    return fail(MZ_EINVAL, "null argument");
+  if (table_of_dev && !td_dev) return fail(MZ_EINVAL, "shared tables need the td workspace");
+  int64_t rows = 0;
+  mz_qtab_states(max_dim, &rows);
+  StreamGuard g(stream);
+  MzQtabUpd u{obs6_dev, n, max_dim, table_of_dev, ntables, q_dev, rows, sidx_dev, actions_dev,
+              reward64_dev, terminated_dev, truncated_dev, gamma_dev, lr_dev, eta_dev, cum_dev,
+              reinterpret_cast<long long*>(episodes_dev), reinterpret_cast<long long*>(wins_dev),
+              td_dev, episode_end != 0};
+  MZ_HIP(mz_launch_qtab_update(u, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}

@@ -136,3 +136,28 @@ hipError_t mz_launch_qact(const MzQAct& q, int relu, hipStream_t s);
 hipError_t mz_launch_qact_prepare(const float* w1, const float* w2, uint16_t* w1h, uint16_t* w1l,
                                   uint16_t* w2h, uint16_t* w2l, hipStream_t s);
 
+// ---- vectorised tabular Q-learning (mz_qtab.hip) ----------------------------------------------
+struct MzQtabAct {
+  const float* obs6; int n, P;               // plain observations [n][6], pitch of the index
+  const int32_t* table_of; int T;            // instance -> table (null: i), tables
+  const uint8_t* active;                     // [n] 0 = the instance idles (null: all act)
+  const double* q; int64_t rows;             // [T][rows][4] f64
+  const long long* steps_done;               // [T]
+  const double* eps_init; const double* eps_final; const double* eps_decay;  // [T]
+  uint64_t seed, counter;
+  int32_t* actions; int64_t* sidx;           // [n] action taken, row index acted from
+};
+struct MzQtabUpd {
+  const float* obs6; int n, P;               // the step's next observations
+  const int32_t* table_of; int T;
+  double* q; int64_t rows;
+  const int64_t* sidx; const int32_t* actions;
+  const double* reward64; const uint8_t* terminated; const uint8_t* truncated;
+  double* gamma; const double* lr; const double* eta;  // [T]
+  double* cum;                               // [n] episode's cumulative reward
+  long long* episodes; long long* wins;      // [T]
+  double* td;                                // [n] lr * td between the two shared-table passes
+  int episode_end;                           // 0: QAgent.update alone (no gamma drift, no counters)
+};
+hipError_t mz_launch_qtab_act(const MzQtabAct& a, long long* steps_done, hipStream_t s);
+hipError_t mz_launch_qtab_update(const MzQtabUpd& u, hipStream_t s);

@@ -50,7 +50,7 @@ EXPORTS = ["mz_last_error", "mz_device_count", "mz_create", "mz_destroy", "mz_lo
            "mz_head_loss_backward", "mz_head_loss_workspace_floats",
            "mz_head_loss_backward_workspace_floats", "mz_adamw_groups",
            "mz_ppo_act", "mz_ppo_scan", "mz_ppo_finish", "mz_ppo_head_loss", "mz_qact_prepare", "mz_qact",
-           "mz_qact_workspace_floats"]
+           "mz_qact_workspace_floats", "mz_qtab_states", "mz_qtab_act", "mz_qtab_update"]
 
 _lib = None
 
@@ -169,6 +169,11 @@ def load(build_if_missing=True):
     L.mz_qact_prepare.argtypes = [vp] * 7
     L.mz_qact.argtypes = [vp, vp, vp, vp, C.c_int32] + [vp] * 10 + [C.c_int32, C.c_float,
                                                                    C.c_uint64, C.c_uint64] + [vp] * 4
+    L.mz_qtab_states.argtypes = [C.c_int32, C.POINTER(C.c_int64)]
+    L.mz_qtab_act.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp, vp,
+                              C.c_uint64, C.c_uint64, vp, vp, vp]
+    L.mz_qtab_update.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32] + [vp] * 13 + \
+        [C.c_int32, vp]
     L.mz_host_alloc.argtypes = [C.c_uint64, C.c_int32, C.POINTER(vp), C.POINTER(vp)]
     L.mz_host_free.argtypes = [vp]
     for f in EXPORTS:
