@@ -723,6 +723,66 @@ int mz_qtab_update(const float* obs6_dev, int32_t n, int32_t max_dim, const int3
                    int64_t* episodes_dev, int64_t* wins_dev, double* td_dev, int32_t episode_end,
                    void* stream);
 
+/* ---- The same learner on hashed tables (mz_qhash.hip) ------------------------------------------
+ * QAgent's table is a defaultdict(lambda: np.zeros(4)) (agents/q_agent.py:8-79) that holds only
+ * the states met; a dense table holds all 5 P^4 (452 MB at 41x41, 6.9 GB at 81x81). Here each of
+ * the ntables tables is an open-addressing hash table of `capacity` slots (a power of two,
+ * 16 <= capacity <= 2^30, the same for all tables):
+ *   keys_dev     int32 [ntables][capacity]     key = the dense row index above (< 5 * 127^4 <
+ *                                              2^31 for every legal pitch); -1 = empty
+ *   vals_dev     f64   [ntables][capacity][4]  32-B aligned, zero-filled by the caller: an absent
+ *                                              key reads as the zero row (np.zeros(4))
+ *   load_dev     int32 [ntables]               occupied slots
+ *   overflow_dev int64 [ntables]               updates dropped because the table was full
+ * Hash: slot0 = (uint32(key) * 0x9E3779B1u) >> (32 - log2 capacity), then +1 mod capacity. Every
+ * probe ends after at most `capacity` slots. Table full: a lookup answers absent; an update's
+ * value is dropped and overflow_dev[t] += 1, its episode-end bookkeeping (cum, gamma +- eta,
+ * episodes, wins) still runs; no error. Keys are never deleted. Lookups and concurrent inserts
+ * never share a launch. Argument errors (capacity not such a power of two, null pointers, a
+ * negative count) are refused before any GPU call. */
+
+/* mz_qtab_act with the row fetched by lookup (QAgent.get_action, q_agent.py:44-54): read-only on
+ * the tables — acting never inserts. sidx_dev receives the dense key acted from. Two launches. */
+int mz_qtab_hash_act(const float* obs6_dev, int32_t n, int32_t max_dim,
+                     const int32_t* table_of_dev, int32_t ntables, const uint8_t* active_dev,
+                     const int32_t* keys_dev, const double* vals_dev, int64_t capacity,
+                     int64_t* steps_done_dev, const double* eps_init_dev,
+                     const double* eps_final_dev, const double* eps_decay_dev, uint64_t seed,
+                     uint64_t counter, int32_t* actions_dev, int64_t* sidx_dev, void* stream);
+
+/* mz_qtab_update on hashed tables (QAgent.update, q_agent.py:56-73, and the episode end of
+ * off_policy_trainer.py:32,77-78), the same float64 operations in the same order. table_of_dev
+ * NULL: one launch — look up s' and s, td, find or insert s, store Q[s][a] + lr * td (the key is
+ * inserted on every write, also of a zero value; load_dev[t] += 1 on a new slot). Otherwise two
+ * launches: the read-only td pass (td_dev required), then find-or-insert — a slot is claimed by
+ * a 32-bit compare-and-swap of its key from -1; a lane that loses uses the slot if it now holds
+ * its own key and probes on otherwise — and one float64 atomic add on the value. */
+int mz_qtab_hash_update(const float* obs6_dev, int32_t n, int32_t max_dim,
+                        const int32_t* table_of_dev, int32_t ntables, int32_t* keys_dev,
+                        double* vals_dev, int64_t capacity, int32_t* load_dev,
+                        int64_t* overflow_dev, const int64_t* sidx_dev, const int32_t* actions_dev,
+                        const double* reward64_dev, const uint8_t* terminated_dev,
+                        const uint8_t* truncated_dev, double* gamma_dev, const double* lr_dev,
+                        const double* eta_dev, double* cum_dev, int64_t* episodes_dev,
+                        int64_t* wins_dev, double* td_dev, int32_t episode_end, void* stream);
+
+/* Re-insert every (key, row) of the ntables tables into new_keys_dev / new_vals_dev of capacity
+ * new_capacity, which the caller has filled with -1 / zero and which must not overlap the old
+ * arrays. One lane per old slot, the same compare-and-swap claim. The load counters carry over
+ * unchanged; an entry that finds its new table full is dropped and counted in overflow_dev (size
+ * new_capacity above the largest load and none is). */
+int mz_qtab_hash_rehash(const int32_t* keys_dev, const double* vals_dev, int64_t capacity,
+                        int32_t* new_keys_dev, double* new_vals_dev, int64_t new_capacity,
+                        int32_t ntables, int64_t* overflow_dev, void* stream);
+
+/* For m (table, key) pairs — tables_dev int32 [m], query_keys_dev int64 [m] — rows_out_dev
+ * [m][4] float64 (16-B aligned; zeros if absent) and slots_out_dev int32 [m] (-1 if absent, also
+ * for a table outside [0, ntables) or a key outside [0, 2^31)). m == 0 does nothing. */
+int mz_qtab_hash_lookup(const int32_t* keys_dev, const double* vals_dev, int64_t capacity,
+                        int32_t ntables, const int32_t* tables_dev,
+                        const int64_t* query_keys_dev, int32_t m, double* rows_out_dev,
+                        int32_t* slots_out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -161,3 +161,21 @@ struct MzQtabUpd {
 };
 hipError_t mz_launch_qtab_act(const MzQtabAct& a, long long* steps_done, hipStream_t s);
 hipError_t mz_launch_qtab_update(const MzQtabUpd& u, hipStream_t s);
+hipError_t mz_launch_qtab_advance(const int32_t* table_of, const uint8_t* active, int n, int T,
+                                  long long* steps_done, hipStream_t s);
+
+// ---- hashed tables of the same learner (mz_qhash.hip) -----------------------------------------
+struct MzQhash {
+  int32_t* keys;                             // [T][C] dense state index, -1 = empty
+  double* vals;                              // [T][C][4] f64, zero until written
+  int32_t* load; long long* overflow;        // [T] occupied slots, dropped updates
+  uint32_t C; int shift;                     // capacity (a power of two), 32 - log2 C
+};
+// act / update: the dense launch's arguments with q == nullptr (rows stays 5 P^4, the key range)
+hipError_t mz_launch_qhash_act(const MzQtabAct& a, const MzQhash& h, long long* steps_done,
+                               hipStream_t s);
+hipError_t mz_launch_qhash_update(const MzQtabUpd& u, const MzQhash& h, hipStream_t s);
+hipError_t mz_launch_qhash_rehash(const MzQhash& from, const MzQhash& to, int T, hipStream_t s);
+hipError_t mz_launch_qhash_lookup(const MzQhash& h, int T, const int32_t* tables,
+                                  const int64_t* keys, int m, double* rows_out, int32_t* slots_out,
+                                  hipStream_t s);

@@ -38,89 +38,24 @@
 // Shared-table determinism: colliding adds and the +-eta adds to gamma arrive in no fixed order,
 // so results are bitwise reproducible only where the addends commute exactly (disjoint rows;
 // equal addends); otherwise they can differ in the last bits from run to run.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "mz_common.h"
-#include "mz_learner.h"
+//
+// The index, the epsilon / action choice, the TD expression and the episode end live in mz_qtab.h,
+// shared with the hashed storage (mz_qhash.hip); this file supplies the dense row fetch and store.
+#include "mz_qtab.h"
 
 namespace {
 
-constexpr int QT_T = 256;  // threads per workgroup, one instance per lane
-
-__device__ inline int qtab_coord(float v, int P) {  // a cell coordinate, never outside the pitch
-  const int x = (int)v;
-  return x < 0 ? 0 : (x >= P ? P - 1 : x);
-}
-
-// best-dir class from (br, bc): see the header comment
-__device__ inline int qtab_dir(float brf, float bcf) {
-  const int br = (int)brf, bc = (int)bcf;
-  if (br == -1 || br > 1) return 1;
-  if (br == 1 || br < -1) return 2;
-  if (bc == -1 || bc > 1) return 3;
-  if (bc == 1 || bc < -1) return 4;
-  return 0;
-}
-
-__device__ inline int64_t qtab_index(const float* obs6, int i, int P) {
-  const float2* o = reinterpret_cast<const float2*>(obs6 + (size_t)i * 6);  // 24-B rows: 8-B aligned
-  const float2 a = o[0], g = o[1], b = o[2];
-  const int64_t cell = (int64_t)qtab_coord(a.x, P) * P + qtab_coord(a.y, P);
-  const int64_t goal = (int64_t)qtab_coord(g.x, P) * P + qtab_coord(g.y, P);
-  return (cell * P * P + goal) * 5 + qtab_dir(b.x, b.y);
-}
-
-struct Row { double v[4]; };
-
 __device__ inline Row qtab_load(const double* q, int64_t rows, int t, int64_t s) {
-  const double2* p = reinterpret_cast<const double2*>(q + ((int64_t)t * rows + s) * 4);
-  const double2 lo = p[0], hi = p[1];
-  return Row{{lo.x, lo.y, hi.x, hi.y}};
-}
-
-__device__ inline double qtab_max(const Row& r) {  // np.max of the row
-  double m = r.v[0];
-#pragma unroll
-  for (int k = 1; k < 4; ++k) m = r.v[k] > m ? r.v[k] : m;
-  return m;
-}
-
-__device__ inline int qtab_table(const int32_t* table_of, int i, int T) {
-  const int t = table_of ? table_of[i] : i;
-  return (unsigned)t < (unsigned)T ? t : -1;
+  return qtab_row_at(q + ((int64_t)t * rows + s) * 4);
 }
 
 __global__ __launch_bounds__(QT_T) void k_qtab_act(MzQtabAct a) {
   const int i = blockIdx.x * QT_T + threadIdx.x;
   if (i >= a.n) return;
-  const int t = (a.active && !a.active[i]) ? -1 : qtab_table(a.table_of, i, a.T);
-  if (t < 0) {  // idle or no table: observe only (mz_step ignores a negative action)
-    a.actions[i] = -1;
-    a.sidx[i] = -1;
-    return;
-  }
+  const int t = qtab_act_table(a, i);
+  if (t < 0) return;  // idle or no table: observe only
   const int64_t s = qtab_index(a.obs6, i, a.P);
-  const Row row = qtab_load(a.q, a.rows, t, s);
-  const double x = __ddiv_rn(__dmul_rn(-1.0, (double)a.steps_done[t]), a.eps_decay[t]);
-  const double ef = a.eps_final[t];
-  const double eps = __dadd_rn(ef, __dmul_rn(__dsub_rn(a.eps_init[t], ef), exp(x)));
-  uint32_t w[4];
-  mz_philox(a.seed, MZ_QTAB_STREAM ^ ((uint64_t)(uint32_t)i << 32), a.counter, w);
-  const double u = (double)(w[0] >> 8) * (1.0 / 16777216.0);
-  int act;
-  if (u < eps) {
-    act = (int)(w[1] >> 30);
-  } else {
-    act = 0;
-    double m = row.v[0];
-#pragma unroll
-    for (int k = 1; k < 4; ++k)
-      if (row.v[k] > m) { m = row.v[k]; act = k; }
-  }
-  a.actions[i] = act;
-  a.sidx[i] = s;
+  qtab_choose(a, i, t, s, qtab_load(a.q, a.rows, t, s));
 }
 
 // steps_done[t] += 1 per acting instance. A wave whose lanes share lane 0's table adds their count
@@ -148,48 +83,20 @@ __global__ __launch_bounds__(QT_T) void k_qtab_advance(const int32_t* table_of,
   }
 }
 
-// What one instance's step contributes: the row / action it updates and lr * td.
-struct Td {
-  int t, act;
-  int64_t s;
-  double add, old;
+struct DenseFetch {
+  const double* q;
+  int64_t rows;
+  __device__ Row operator()(int t, int64_t s) const { return qtab_load(q, rows, t, s); }
 };
-
-__device__ inline bool qtab_td(const MzQtabUpd& u, int i, Td& o) {
-  o.t = qtab_table(u.table_of, i, u.T);
-  if (o.t < 0) return false;
-  o.s = u.sidx[i];
-  o.act = u.actions[i];
-  if (o.s < 0 || o.s >= u.rows || (unsigned)o.act > 3u) return false;
-  const int64_t s2 = qtab_index(u.obs6, i, u.P);
-  const Row nxt = qtab_load(u.q, u.rows, o.t, s2);
-  const Row cur = qtab_load(u.q, u.rows, o.t, o.s);
-  const double future = u.terminated[i] ? 0.0 : qtab_max(nxt);
-  const double q01 = (o.act & 1) ? cur.v[1] : cur.v[0], q23 = (o.act & 1) ? cur.v[3] : cur.v[2];
-  o.old = (o.act & 2) ? q23 : q01;
-  const double td = __dsub_rn(__dadd_rn(u.reward64[i], __dmul_rn(u.gamma[o.t], future)), o.old);
-  o.add = __dmul_rn(u.lr[o.t], td);
-  return true;
-}
 
 // independent tables (table_of NULL): nobody else touches instance i's table, gamma or counters
 __global__ __launch_bounds__(QT_T) void k_qtab_update(MzQtabUpd u) {
   const int i = blockIdx.x * QT_T + threadIdx.x;
   if (i >= u.n) return;
   Td d;
-  if (!qtab_td(u, i, d)) return;
+  if (!qtab_td(u, i, d, DenseFetch{u.q, u.rows})) return;
   u.q[((int64_t)d.t * u.rows + d.s) * 4 + d.act] = __dadd_rn(d.old, d.add);
-  const double cum = __dadd_rn(u.cum[i], u.reward64[i]);
-  const bool term = u.terminated[i] != 0;
-  if (u.episode_end && (term || u.truncated[i])) {
-    const double eta = u.eta[d.t];
-    u.gamma[d.t] = __dadd_rn(u.gamma[d.t], cum > 0.0 ? eta : -eta);
-    u.cum[i] = 0.0;
-    u.episodes[d.t] += 1;
-    u.wins[d.t] += term ? 1 : 0;
-  } else {
-    u.cum[i] = cum;
-  }
+  qtab_end_plain(u, i, d.t);
 }
 
 // shared tables, pass 1: read-only on the table and on gamma
@@ -197,7 +104,7 @@ __global__ __launch_bounds__(QT_T) void k_qtab_td(MzQtabUpd u) {
   const int i = blockIdx.x * QT_T + threadIdx.x;
   if (i >= u.n) return;
   Td d;
-  u.td[i] = qtab_td(u, i, d) ? d.add : 0.0;
+  u.td[i] = qtab_td(u, i, d, DenseFetch{u.q, u.rows}) ? d.add : 0.0;
 }
 
 // shared tables, pass 2: one f64 atomic add per instance, then the episode end
@@ -210,28 +117,24 @@ __global__ __launch_bounds__(QT_T) void k_qtab_apply(MzQtabUpd u) {
   const int act = u.actions[i];
   if (s < 0 || s >= u.rows || (unsigned)act > 3u) return;
   unsafeAtomicAdd(u.q + ((int64_t)t * u.rows + s) * 4 + act, u.td[i]);
-  const double cum = __dadd_rn(u.cum[i], u.reward64[i]);
-  const bool term = u.terminated[i] != 0;
-  if (u.episode_end && (term || u.truncated[i])) {
-    const double eta = u.eta[t];
-    unsafeAtomicAdd(u.gamma + t, cum > 0.0 ? eta : -eta);
-    u.cum[i] = 0.0;
-    atomicAdd(reinterpret_cast<unsigned long long*>(u.episodes + t), 1ull);
-    if (term) atomicAdd(reinterpret_cast<unsigned long long*>(u.wins + t), 1ull);
-  } else {
-    u.cum[i] = cum;
-  }
+  qtab_end_atomic(u, i, t);
 }
 
 }  // namespace
+
+hipError_t mz_launch_qtab_advance(const int32_t* table_of, const uint8_t* active, int n, int T,
+                                  long long* steps_done, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_qtab_advance, dim3((n + QT_T - 1) / QT_T), dim3(QT_T), 0, s, table_of,
+                     active, n, T, steps_done);
+  return hipGetLastError();
+}
 
 hipError_t mz_launch_qtab_act(const MzQtabAct& a, long long* steps_done, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
   const int blocks = (a.n + QT_T - 1) / QT_T;
   hipLaunchKernelGGL(k_qtab_act, dim3(blocks), dim3(QT_T), 0, s, a);
-  hipLaunchKernelGGL(k_qtab_advance, dim3(blocks), dim3(QT_T), 0, s, a.table_of, a.active,
-                     a.n, a.T, steps_done);
-  return hipGetLastError();
+  return mz_launch_qtab_advance(a.table_of, a.active, a.n, a.T, steps_done, s);
 }
 
 hipError_t mz_launch_qtab_update(const MzQtabUpd& u, hipStream_t s) {

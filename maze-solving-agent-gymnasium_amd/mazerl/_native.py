@@ -50,7 +50,8 @@ EXPORTS = ["mz_last_error", "mz_device_count", "mz_create", "mz_destroy", "mz_lo
            "mz_head_loss_backward", "mz_head_loss_workspace_floats",
            "mz_head_loss_backward_workspace_floats", "mz_adamw_groups",
            "mz_ppo_act", "mz_ppo_scan", "mz_ppo_finish", "mz_ppo_head_loss", "mz_qact_prepare", "mz_qact",
-           "mz_qact_workspace_floats", "mz_qtab_states", "mz_qtab_act", "mz_qtab_update"]
+           "mz_qact_workspace_floats", "mz_qtab_states", "mz_qtab_act", "mz_qtab_update",
+           "mz_qtab_hash_act", "mz_qtab_hash_update", "mz_qtab_hash_rehash", "mz_qtab_hash_lookup"]
 
 _lib = None
 
@@ -174,6 +175,12 @@ def load(build_if_missing=True):
                               C.c_uint64, C.c_uint64, vp, vp, vp]
     L.mz_qtab_update.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32] + [vp] * 13 + \
         [C.c_int32, vp]
+    L.mz_qtab_hash_act.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, vp, C.c_int64,
+                                   vp, vp, vp, vp, C.c_uint64, C.c_uint64, vp, vp, vp]
+    L.mz_qtab_hash_update.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, C.c_int64] + \
+        [vp] * 14 + [C.c_int32, vp]
+    L.mz_qtab_hash_rehash.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int32, vp, vp]
+    L.mz_qtab_hash_lookup.argtypes = [vp, vp, C.c_int64, C.c_int32, vp, vp, C.c_int32, vp, vp, vp]
     L.mz_host_alloc.argtypes = [C.c_uint64, C.c_int32, C.POINTER(vp), C.POINTER(vp)]
     L.mz_host_free.argtypes = [vp]
     for f in EXPORTS:

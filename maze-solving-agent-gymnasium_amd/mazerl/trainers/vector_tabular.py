@@ -14,11 +14,29 @@ import torch
 
 
 class VectorTabularTrainer:
-    def __init__(self, env, agent, regen_won=True, keep_flags=False):
+    def __init__(self, env, agent, regen_won=True, keep_flags=False, grow_every=0):
         """keep_flags: keep each step's terminated / truncated flags in self.terminated /
-        self.truncated (the reset that follows clears the env's own; two copies per step)."""
+        self.truncated (the reset that follows clears the env's own; two copies per step).
+        grow_every (hashed agents; 0: never): every grow_every vector steps read the largest
+        load (one synchronisation) and double the capacity C while it is above C / 2. After a
+        check every load is <= C / 2 and a table gains at most one key per instance per step, so
+        with m instances on the most-shared table a load stays <= C / 2 + grow_every * m until
+        the next check: grow_every * m <= C / 2 is required (m = 1 on independent tables), and
+        then no table ever fills and no update is dropped. A dense agent ignores grow_every."""
         if agent.env is not env:
             raise ValueError("the agent was built for another env")
+        self.grow_every = int(grow_every)
+        if self.grow_every < 0:
+            raise ValueError("grow_every must be >= 0")
+        if self.grow_every and getattr(agent, "hashed", False):
+            m = 1 if agent.table_of is None else \
+                int(torch.bincount(agent.table_of.to(torch.int64)).max())
+            if self.grow_every * m > agent.capacity // 2:
+                raise ValueError(f"grow_every {self.grow_every} x {m} instances per table "
+                                 f"exceeds capacity / 2 = {agent.capacity // 2}: a table could "
+                                 f"fill between two checks")
+        else:
+            self.grow_every = 0
         self.env, self.agent = env, agent
         self.regen_won = bool(regen_won)
         self.vector_steps = 0
@@ -46,6 +64,8 @@ class VectorTabularTrainer:
             self.truncated.copy_(env.truncated)
         env.reset_done(regen_won=self.regen_won)
         self.vector_steps += 1
+        if self.grow_every and self.vector_steps % self.grow_every == 0:
+            agent.grow()
 
     def train(self, vector_steps):
         """vector_steps steps of every instance; returns the seconds they took (one

@@ -10,6 +10,16 @@
 Prints one JSON line: env steps/s of each case, the launches per vector step of (b), and the
 ratio (b) / (a). (a) pays a launch and a sync per env step, (b) a handful of launches per 4,096
 env steps: a ratio under 100 means a host synchronisation hides in the vectorised loop.
+
+With --storage the script measures the table storages of (b) instead (no drop-in leg): for each
+of --tables (independent, shared) it runs --repeats rounds, and in every round each named storage
+once, in the order given (so `--storage dense hash` alternates them in one process), on
+--size x --size r-prim mazes; hashed tables take --capacity slots and, with --grow-every, double
+when half full. One JSON line: per case and storage the raw repeats (us per vector step, env
+steps/s, and for hashed tables the final capacity, largest load and dropped updates), their
+median, and the hashed / dense ratio of the medians where both ran. Examples:
+  qtab_rate.py --storage dense hash --capacity 256               9x9, both storages, both cases
+  qtab_rate.py --storage hash --tables independent --size 41 --capacity 4096
 """
 import argparse
 import json
@@ -40,14 +50,18 @@ def dropin(episodes):
             "env_steps_per_s": steps / secs}
 
 
-def vectorised(n, tables, warmup, steps):
+def vectorised(n, tables, warmup, steps, size=9, storage="dense", capacity=None, grow_every=0):
     import torch
     import mazerl
     from mazerl.agents.vector_q import VectorQAgent
     from mazerl.trainers.vector_tabular import VectorTabularTrainer
-    env = mazerl.VectorMazeEnv(n, 9, enrich=False, reward64=True, done_list=False)
-    agent = VectorQAgent(env, tables=tables, **HP)
-    trn = VectorTabularTrainer(env, agent, regen_won=True)
+    env = mazerl.VectorMazeEnv(n, size, enrich=False, reward64=True, done_list=False)
+    hp = dict(HP, epsilon_decay=size * size // 2)
+    if storage == "hash":
+        agent = VectorQAgent(env, tables=tables, storage="hash", capacity=capacity, **hp)
+    else:
+        agent = VectorQAgent(env, tables=tables, **hp)
+    trn = VectorTabularTrainer(env, agent, regen_won=True, grow_every=grow_every)
     for _ in range(warmup):
         trn.vector_step()
     torch.cuda.synchronize()
@@ -62,8 +76,38 @@ def vectorised(n, tables, warmup, steps):
            "seconds": round(secs, 4), "us_per_vector_step": secs / steps * 1e6,
            "env_steps_per_s": n * steps / secs, "launches_per_vector_step": trn.launches_per_step,
            "episodes": int(agent.episodes.sum()), "wins": int(agent.wins.sum())}
+    if storage == "hash":
+        out.update(storage="hash", capacity=agent.capacity, max_load=int(agent.load.max()),
+                   overflow=int(agent.overflow.sum()),
+                   table_bytes=agent.num_tables * agent.capacity * 36)
     env.close()
     return out
+
+
+def storages(a):
+    """--storage: the storages against each other, alternating, a.repeats rounds per case."""
+    res = {"size": a.size, "instances": a.instances, "warmup": a.warmup, "steps": a.steps}
+    cases = {"independent": None, "shared": 1}
+    for case in (("independent", "shared") if a.tables == "both" else (a.tables,)):
+        runs = {st: [] for st in a.storage}
+        for _ in range(a.repeats):
+            for st in a.storage:
+                grow = a.grow_every if st == "hash" else 0
+                runs[st].append(vectorised(a.instances, cases[case], a.warmup, a.steps, a.size,
+                                           st, a.capacity if st == "hash" else None, grow))
+        out = {st: {"us_per_vector_step": [round(r["us_per_vector_step"], 2) for r in rs],
+                    "median_us": float(np.median([r["us_per_vector_step"] for r in rs])),
+                    "env_steps_per_s": [round(r["env_steps_per_s"]) for r in rs],
+                    "launches_per_vector_step": rs[0]["launches_per_vector_step"],
+                    "wins": [r["wins"] for r in rs], "episodes": [r["episodes"] for r in rs]}
+               for st, rs in runs.items()}
+        if "hash" in runs:
+            for k in ("capacity", "max_load", "overflow", "table_bytes"):
+                out["hash"][k] = [r[k] for r in runs["hash"]]
+        if len(runs) == 2:
+            out["hash_over_dense_time"] = out["hash"]["median_us"] / out["dense"]["median_us"]
+        res[case] = out
+    print(json.dumps(res), flush=True)
 
 
 def main():
@@ -72,7 +116,17 @@ def main():
     ap.add_argument("--instances", type=int, default=4096)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--storage", nargs="+", choices=("dense", "hash"), default=None,
+                    help="measure these table storages against each other (no drop-in leg)")
+    ap.add_argument("--tables", choices=("independent", "shared", "both"), default="both")
+    ap.add_argument("--size", type=int, default=9, help="maze size of the --storage runs")
+    ap.add_argument("--capacity", type=int, default=256, help="slots of a hashed table")
+    ap.add_argument("--grow-every", type=int, default=0,
+                    help="hashed: check the load every this many vector steps and double")
+    ap.add_argument("--repeats", type=int, default=3)
     a = ap.parse_args()
+    if a.storage:
+        return storages(a)
     res = {"dropin_single_env": dropin(a.episodes),
            "vector_independent": vectorised(a.instances, None, a.warmup, a.steps),
            "vector_shared_one_table": vectorised(a.instances, 1, a.warmup, a.steps)}
