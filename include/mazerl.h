@@ -783,6 +783,94 @@ int mz_qtab_hash_lookup(const int32_t* keys_dev, const double* vals_dev, int64_t
                         const int64_t* query_keys_dev, int32_t m, double* rows_out_dev,
                         int32_t* slots_out_dev, void* stream);
 
+/* ---- Double Q-learning populations (mz_dqtab.hip) ----------------------------------------------
+ * Replaces, per instance, DQAgent (agents/dq_agent.py:5-73: two dicts of 4-entry float64 rows,
+ * q_a_values and q_b_values, keyed by str(obs)) under the same OffPolicyTrainer.train. Everything
+ * above holds (the index, the per-table arrays, idle instances, the hash and its probe) except
+ * the row: a state's A row and B row sit side by side, [2][4] float64 = 64 B, 64-B aligned.
+ *   dense    q_dev    [ntables][rows][2][4]
+ *   hashed   keys_dev int32 [ntables][capacity] as above (one key per state, one probe for both
+ *            tables), vals_dev [ntables][capacity][2][4]; a write to either table inserts the key.
+ * Argument errors (null pointers, a negative count, a bad pitch, a capacity that is not a power
+ * of two in [16, 2^30], a misaligned table) are refused before any GPU call. */
+
+/* DQAgent.get_action (dq_agent.py:35-46): mz_qtab_act on the A row — acting reads Q_A only; the
+ * same MZ_QTAB_STREAM draw, the same steps_done advance. Two launches. */
+int mz_dqtab_act(const float* obs6_dev, int32_t n, int32_t max_dim, const int32_t* table_of_dev,
+                 int32_t ntables, const uint8_t* active_dev, const double* q_dev,
+                 int64_t* steps_done_dev, const double* eps_init_dev, const double* eps_final_dev,
+                 const double* eps_decay_dev, uint64_t seed, uint64_t counter, int32_t* actions_dev,
+                 int64_t* sidx_dev, void* stream);
+
+/* DQAgent.update (dq_agent.py:48-66) after mz_step, then mz_qtab_update's episode end
+ * (dq_agent.py:69-73 is QAgent's update_hyperparameter). Draws mz_philox(seed, MZ_DQTAB_STREAM ^
+ * (i << 32), ucounter), ucounter the caller's count of update calls:
+ *   (w0 >> 8) * 2^-24 < 0.5 -> table A is updated, else B (:57);
+ *   best = get_action(next_obs) (:58, :62), the inner eps-greedy choice on Q_A[s'] in either case:
+ *   eps from steps_done_dev[t] as this call finds it (after the act's advance), u2 = (w1 >> 8) *
+ *   2^-24 < eps -> best = w2 >> 30, else the first maximum of Q_A[s'];
+ *   updating A: td = (reward + gamma * Q_B[s'][best]) - Q_A[s][a]; Q_A[s][a] = Q_A[s][a] + lr * td
+ *   (:59-60), updating B: the same with A and B swapped (:63-64). No terminated factor, as there.
+ * took_dev (uint8 [n], required) receives 1 where a td was computed; a last launch adds these
+ * inner get_actions to steps_done_dev (steps_done grows by 2 per training step), after every
+ * lane read the old value.
+ * coin_dev (uint8 [n]; 0 = A, 1 = B; NULL: draw) and next_action_dev (int32 [n] in 0..3, outside:
+ * the instance idles; NULL: the inner choice) replace the draws, for replaying the reference; with
+ * next_action_dev no eps is evaluated, steps_done still advances.
+ * table_of_dev NULL: two launches. Otherwise three: a read-only pass writes lr * td into td_dev
+ * (float64 [n]) and the chosen table into which_dev (uint8 [n]), both required then; a second
+ * does one float64 atomic add per instance into the chosen table's element, and the episode end
+ * with atomic adds. */
+int mz_dqtab_update(const float* obs6_dev, int32_t n, int32_t max_dim, const int32_t* table_of_dev,
+                    int32_t ntables, double* q_dev, const int64_t* sidx_dev,
+                    const int32_t* actions_dev, const double* reward64_dev,
+                    const uint8_t* terminated_dev, const uint8_t* truncated_dev, double* gamma_dev,
+                    const double* lr_dev, const double* eta_dev, double* cum_dev,
+                    int64_t* episodes_dev, int64_t* wins_dev, double* td_dev, int32_t episode_end,
+                    int64_t* steps_done_dev, const double* eps_init_dev,
+                    const double* eps_final_dev, const double* eps_decay_dev, uint64_t seed,
+                    uint64_t ucounter, const uint8_t* coin_dev, const int32_t* next_action_dev,
+                    uint8_t* took_dev, uint8_t* which_dev, void* stream);
+
+/* mz_dqtab_act on hashed tables (dq_agent.py:35-46): the A row by lookup, absent -> zeros; acting
+ * never inserts. Two launches. */
+int mz_dqtab_hash_act(const float* obs6_dev, int32_t n, int32_t max_dim,
+                      const int32_t* table_of_dev, int32_t ntables, const uint8_t* active_dev,
+                      const int32_t* keys_dev, const double* vals_dev, int64_t capacity,
+                      int64_t* steps_done_dev, const double* eps_init_dev,
+                      const double* eps_final_dev, const double* eps_decay_dev, uint64_t seed,
+                      uint64_t counter, int32_t* actions_dev, int64_t* sidx_dev, void* stream);
+
+/* mz_dqtab_update on hashed tables (dq_agent.py:48-66): look up s' and s, the same draws and td,
+ * find or insert s (shared tables: the compare-and-swap claim of mz_qtab_hash_update, in the
+ * second pass), store or add into the chosen table's element. A full table drops the write and
+ * counts overflow_dev[t]; the dropped update still counts its get_action and its episode end. */
+int mz_dqtab_hash_update(const float* obs6_dev, int32_t n, int32_t max_dim,
+                         const int32_t* table_of_dev, int32_t ntables, int32_t* keys_dev,
+                         double* vals_dev, int64_t capacity, int32_t* load_dev,
+                         int64_t* overflow_dev, const int64_t* sidx_dev,
+                         const int32_t* actions_dev, const double* reward64_dev,
+                         const uint8_t* terminated_dev, const uint8_t* truncated_dev,
+                         double* gamma_dev, const double* lr_dev, const double* eta_dev,
+                         double* cum_dev, int64_t* episodes_dev, int64_t* wins_dev, double* td_dev,
+                         int32_t episode_end, int64_t* steps_done_dev, const double* eps_init_dev,
+                         const double* eps_final_dev, const double* eps_decay_dev, uint64_t seed,
+                         uint64_t ucounter, const uint8_t* coin_dev,
+                         const int32_t* next_action_dev, uint8_t* took_dev, uint8_t* which_dev,
+                         void* stream);
+
+/* mz_qtab_hash_rehash for the 64-B slots of DQAgent's two dicts (dq_agent.py:17-18). */
+int mz_dqtab_hash_rehash(const int32_t* keys_dev, const double* vals_dev, int64_t capacity,
+                         int32_t* new_keys_dev, double* new_vals_dev, int64_t new_capacity,
+                         int32_t ntables, int64_t* overflow_dev, void* stream);
+
+/* mz_qtab_hash_lookup for the 64-B slots (dq_agent.py:17-18): rows_out_dev [m][2][4] float64, the
+ * A row then the B row (16-B aligned; zeros if absent). */
+int mz_dqtab_hash_lookup(const int32_t* keys_dev, const double* vals_dev, int64_t capacity,
+                         int32_t ntables, const int32_t* tables_dev,
+                         const int64_t* query_keys_dev, int32_t m, double* rows_out_dev,
+                         int32_t* slots_out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

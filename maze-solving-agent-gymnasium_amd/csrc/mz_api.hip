@@ -1652,3 +1652,176 @@ int mz_qtab_hash_lookup(const int32_t* keys_dev, const double* vals_dev, int64_t
                                 slots_out_dev, static_cast<hipStream_t>(stream)));
   return MZ_OK;
 }
+
+// ---- double Q-learning on either storage (mz_dqtab.hip) ---------------------------------------
+namespace {
+int dq_align(const void* q) {
+  if (reinterpret_cast<uintptr_t>(q) & 63)
+    return fail(MZ_EALIGN, "double Q-tables must be 64-byte aligned");
+  return MZ_OK;
+}
+
+// the arguments an update has beyond mz_qtab_update's
+int dq_update_check(const void* table_of, const void* td, const void* steps_done,
+                    const void* eps_init, const void* eps_final, const void* eps_decay,
+                    const void* took, const void* which) {
+  if (!steps_done || !eps_init || !eps_final || !eps_decay || !took)
+    return fail(MZ_EINVAL, "null argument");
+  if (table_of && (!td || !which))
+    return fail(MZ_EINVAL, "shared tables need the td and which workspaces");
+  return MZ_OK;
+}
+}  // namespace
+
+int mz_dqtab_act(const float* obs6_dev, int32_t n, int32_t max_dim, const int32_t* table_of_dev,
+                 int32_t ntables, const uint8_t* active_dev, const double* q_dev,
+                 int64_t* steps_done_dev, const double* eps_init_dev, const double* eps_final_dev,
+                 const double* eps_decay_dev, uint64_t seed, uint64_t counter, int32_t* actions_dev,
+                 int64_t* sidx_dev, void* stream) {
+  if (int rc = qtab_check(obs6_dev, n, max_dim, table_of_dev, ntables, q_dev)) return rc;
+  if (int rc = dq_align(q_dev)) return rc;
+  if (!steps_done_dev || !eps_init_dev || !eps_final_dev || !eps_decay_dev || !actions_dev ||
+      !sidx_dev)
+    return fail(MZ_EINVAL, "null argument");
+  int64_t rows = 0;
+  mz_qtab_states(max_dim, &rows);
+  StreamGuard g(stream);
+  MzQtabAct a{obs6_dev, n, max_dim, table_of_dev, ntables, active_dev, q_dev, rows,
+              reinterpret_cast<const long long*>(steps_done_dev), eps_init_dev, eps_final_dev,
+              eps_decay_dev, seed, counter, actions_dev, sidx_dev};
+  MZ_HIP(mz_launch_dqtab_act(a, nullptr, reinterpret_cast<long long*>(steps_done_dev),
+                             static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_dqtab_update(const float* obs6_dev, int32_t n, int32_t max_dim, const int32_t* table_of_dev,
+                    int32_t ntables, double* q_dev, const int64_t* sidx_dev,
+                    const int32_t* actions_dev, const double* reward64_dev,
+                    const uint8_t* terminated_dev, const uint8_t* truncated_dev, double* gamma_dev,
+                    const double* lr_dev, const double* eta_dev, double* cum_dev,
+                    int64_t* episodes_dev, int64_t* wins_dev, double* td_dev, int32_t episode_end,
+                    int64_t* steps_done_dev, const double* eps_init_dev,
+                    const double* eps_final_dev, const double* eps_decay_dev, uint64_t seed,
+                    uint64_t ucounter, const uint8_t* coin_dev, const int32_t* next_action_dev,
+                    uint8_t* took_dev, uint8_t* which_dev, void* stream) {
+  if (int rc = qtab_check(obs6_dev, n, max_dim, table_of_dev, ntables, q_dev)) return rc;
+  if (int rc = dq_align(q_dev)) return rc;
+  if (!sidx_dev || !actions_dev || !reward64_dev || !terminated_dev || !truncated_dev ||
+      !gamma_dev || !lr_dev || !eta_dev || !cum_dev || !episodes_dev || !wins_dev)
+    return fail(MZ_EINVAL, "null argument");
+  if (int rc = dq_update_check(table_of_dev, td_dev, steps_done_dev, eps_init_dev, eps_final_dev,
+                               eps_decay_dev, took_dev, which_dev))
+    return rc;
+  int64_t rows = 0;
+  mz_qtab_states(max_dim, &rows);
+  StreamGuard g(stream);
+  MzDqtabUpd d{{obs6_dev, n, max_dim, table_of_dev, ntables, q_dev, rows, sidx_dev, actions_dev,
+                reward64_dev, terminated_dev, truncated_dev, gamma_dev, lr_dev, eta_dev, cum_dev,
+                reinterpret_cast<long long*>(episodes_dev), reinterpret_cast<long long*>(wins_dev),
+                td_dev, episode_end != 0},
+               reinterpret_cast<const long long*>(steps_done_dev), eps_init_dev, eps_final_dev,
+               eps_decay_dev, seed, ucounter, coin_dev, next_action_dev, took_dev, which_dev};
+  MZ_HIP(mz_launch_dqtab_update(d, nullptr, reinterpret_cast<long long*>(steps_done_dev),
+                                static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_dqtab_hash_act(const float* obs6_dev, int32_t n, int32_t max_dim,
+                      const int32_t* table_of_dev, int32_t ntables, const uint8_t* active_dev,
+                      const int32_t* keys_dev, const double* vals_dev, int64_t capacity,
+                      int64_t* steps_done_dev, const double* eps_init_dev,
+                      const double* eps_final_dev, const double* eps_decay_dev, uint64_t seed,
+                      uint64_t counter, int32_t* actions_dev, int64_t* sidx_dev, void* stream) {
+  MzQhash h;
+  if (int rc = qhash_table(keys_dev, vals_dev, capacity, ntables, &h)) return rc;
+  if (int rc = dq_align(vals_dev)) return rc;
+  if (int rc = qtab_check(obs6_dev, n, max_dim, table_of_dev, ntables, vals_dev)) return rc;
+  if (!steps_done_dev || !eps_init_dev || !eps_final_dev || !eps_decay_dev || !actions_dev ||
+      !sidx_dev)
+    return fail(MZ_EINVAL, "null argument");
+  int64_t rows = 0;
+  mz_qtab_states(max_dim, &rows);
+  StreamGuard g(stream);
+  MzQtabAct a{obs6_dev, n, max_dim, table_of_dev, ntables, active_dev, nullptr, rows,
+              reinterpret_cast<const long long*>(steps_done_dev), eps_init_dev, eps_final_dev,
+              eps_decay_dev, seed, counter, actions_dev, sidx_dev};
+  MZ_HIP(mz_launch_dqtab_act(a, &h, reinterpret_cast<long long*>(steps_done_dev),
+                             static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_dqtab_hash_update(const float* obs6_dev, int32_t n, int32_t max_dim,
+                         const int32_t* table_of_dev, int32_t ntables, int32_t* keys_dev,
+                         double* vals_dev, int64_t capacity, int32_t* load_dev,
+                         int64_t* overflow_dev, const int64_t* sidx_dev,
+                         const int32_t* actions_dev, const double* reward64_dev,
+                         const uint8_t* terminated_dev, const uint8_t* truncated_dev,
+                         double* gamma_dev, const double* lr_dev, const double* eta_dev,
+                         double* cum_dev, int64_t* episodes_dev, int64_t* wins_dev, double* td_dev,
+                         int32_t episode_end, int64_t* steps_done_dev, const double* eps_init_dev,
+                         const double* eps_final_dev, const double* eps_decay_dev, uint64_t seed,
+                         uint64_t ucounter, const uint8_t* coin_dev,
+                         const int32_t* next_action_dev, uint8_t* took_dev, uint8_t* which_dev,
+                         void* stream) {
+  MzQhash h;
+  if (int rc = qhash_table(keys_dev, vals_dev, capacity, ntables, &h)) return rc;
+  if (int rc = dq_align(vals_dev)) return rc;
+  if (int rc = qtab_check(obs6_dev, n, max_dim, table_of_dev, ntables, vals_dev)) return rc;
+  if (!load_dev || !overflow_dev || !sidx_dev || !actions_dev || !reward64_dev ||
+      !terminated_dev || !truncated_dev || !gamma_dev || !lr_dev || !eta_dev || !cum_dev ||
+      !episodes_dev || !wins_dev)
+    return fail(MZ_EINVAL, "null argument");
+  if (int rc = dq_update_check(table_of_dev, td_dev, steps_done_dev, eps_init_dev, eps_final_dev,
+                               eps_decay_dev, took_dev, which_dev))
+    return rc;
+  h.load = load_dev;
+  h.overflow = reinterpret_cast<long long*>(overflow_dev);
+  int64_t rows = 0;
+  mz_qtab_states(max_dim, &rows);
+  StreamGuard g(stream);
+  MzDqtabUpd d{{obs6_dev, n, max_dim, table_of_dev, ntables, nullptr, rows, sidx_dev, actions_dev,
+                reward64_dev, terminated_dev, truncated_dev, gamma_dev, lr_dev, eta_dev, cum_dev,
+                reinterpret_cast<long long*>(episodes_dev), reinterpret_cast<long long*>(wins_dev),
+                td_dev, episode_end != 0},
+               reinterpret_cast<const long long*>(steps_done_dev), eps_init_dev, eps_final_dev,
+               eps_decay_dev, seed, ucounter, coin_dev, next_action_dev, took_dev, which_dev};
+  MZ_HIP(mz_launch_dqtab_update(d, &h, reinterpret_cast<long long*>(steps_done_dev),
+                                static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_dqtab_hash_rehash(const int32_t* keys_dev, const double* vals_dev, int64_t capacity,
+                         int32_t* new_keys_dev, double* new_vals_dev, int64_t new_capacity,
+                         int32_t ntables, int64_t* overflow_dev, void* stream) {
+  MzQhash from, to;
+  if (int rc = qhash_table(keys_dev, vals_dev, capacity, ntables, &from)) return rc;
+  if (int rc = qhash_table(new_keys_dev, new_vals_dev, new_capacity, ntables, &to)) return rc;
+  if (int rc = dq_align(vals_dev)) return rc;
+  if (int rc = dq_align(new_vals_dev)) return rc;
+  if (!overflow_dev) return fail(MZ_EINVAL, "null argument");
+  if (keys_dev == new_keys_dev || vals_dev == new_vals_dev)
+    return fail(MZ_EINVAL, "rehash needs fresh arrays");
+  to.overflow = reinterpret_cast<long long*>(overflow_dev);
+  StreamGuard g(stream);
+  MZ_HIP(mz_launch_dqhash_rehash(from, to, ntables, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_dqtab_hash_lookup(const int32_t* keys_dev, const double* vals_dev, int64_t capacity,
+                         int32_t ntables, const int32_t* tables_dev,
+                         const int64_t* query_keys_dev, int32_t m, double* rows_out_dev,
+                         int32_t* slots_out_dev, void* stream) {
+  MzQhash h;
+  if (int rc = qhash_table(keys_dev, vals_dev, capacity, ntables, &h)) return rc;
+  if (int rc = dq_align(vals_dev)) return rc;
+  if (m < 0) return fail(MZ_EINVAL, "m %d must be >= 0", m);
+  if (m == 0) return MZ_OK;
+  if (!tables_dev || !query_keys_dev || !rows_out_dev || !slots_out_dev)
+    return fail(MZ_EINVAL, "null argument");
+  if (reinterpret_cast<uintptr_t>(rows_out_dev) & 15)
+    return fail(MZ_EALIGN, "rows_out must be 16-byte aligned");
+  StreamGuard g(stream);
+  MZ_HIP(mz_launch_dqhash_lookup(h, ntables, tables_dev, query_keys_dev, m, rows_out_dev,
+                                 slots_out_dev, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}

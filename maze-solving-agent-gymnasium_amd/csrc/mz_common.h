@@ -164,6 +164,7 @@ __host__ __device__ inline void mz_philox(uint64_t key, uint64_t ctr_hi, uint64_
 #define MZ_REPLAY_STREAM 0x72706c79ull  // 'rply': replay sample rows
 #define MZ_PPO_STREAM 0x70706f21ull  // 'ppo!': PPO policy draws
 #define MZ_QTAB_STREAM 0x71746162ull  // 'qtab': tabular Q-learning exploration draws
+#define MZ_DQTAB_STREAM 0x64717462ull  // 'dqtb': double Q-learning update draws (coin, inner action)
 
 // Sequential draw stream (one per maze): draw k = word (k & 3) of philox(key, {GEN, k >> 2}).
 struct MzRng {

@@ -179,3 +179,27 @@ hipError_t mz_launch_qhash_rehash(const MzQhash& from, const MzQhash& to, int T,
 hipError_t mz_launch_qhash_lookup(const MzQhash& h, int T, const int32_t* tables,
                                   const int64_t* keys, int m, double* rows_out, int32_t* slots_out,
                                   hipStream_t s);
+
+// ---- double Q-learning on either storage (mz_dqtab.hip) ---------------------------------------
+// A state's A row and B row sit side by side, [2][4] f64 = 64 B: MzQtabAct::q / MzQtabUpd::q are
+// [T][rows][2][4] and MzQhash::vals is [T][C][2][4] (64-B aligned).
+struct MzDqtabUpd {
+  MzQtabUpd u;                               // u.td: lr * td between the two shared-table passes
+  const long long* steps_done;               // [T] as the update finds it (after the act's advance)
+  const double* eps_init; const double* eps_final; const double* eps_decay;  // [T]
+  uint64_t seed, ucounter;                   // ucounter: the agent's count of update calls
+  const uint8_t* coin;                       // [n] 0 = A, 1 = B (null: draw)
+  const int32_t* next_action;                // [n] in 0..3 (null: the inner eps-greedy choice)
+  uint8_t* took;                             // [n] 1 where a td was computed
+  uint8_t* which;                            // [n] the table updated, between the shared passes
+};
+// act: k_qtab_act on the A row, then the advance. update: independent tables one launch, shared
+// tables two; then mz_launch_qtab_advance(table_of, took, ...) for the inner get_actions.
+hipError_t mz_launch_dqtab_act(const MzQtabAct& a, const MzQhash* h, long long* steps_done,
+                               hipStream_t s);
+hipError_t mz_launch_dqtab_update(const MzDqtabUpd& d, const MzQhash* h, long long* steps_done,
+                                  hipStream_t s);
+hipError_t mz_launch_dqhash_rehash(const MzQhash& from, const MzQhash& to, int T, hipStream_t s);
+hipError_t mz_launch_dqhash_lookup(const MzQhash& h, int T, const int32_t* tables,
+                                   const int64_t* keys, int m, double* rows_out,
+                                   int32_t* slots_out, hipStream_t s);

@@ -1,5 +1,5 @@
-// mz_qtab.h — device helpers shared by the two storages of the vectorised tabular learner:
-// mz_qtab.hip (dense tables) and mz_qhash.hip (hashed tables). The state index, the epsilon
+// mz_qtab.h — device helpers shared by the vectorised tabular learners: mz_qtab.hip (dense tables),
+// mz_qhash.hip (hashed tables) and mz_dqtab.hip (double Q-learning on either). The state index, the epsilon
 // expression, the action choice, the TD expression and the episode end are written once, here, so
 // that the float64 operation order (__dmul_rn / __dadd_rn ...) cannot drift between the storages:
 // a storage only supplies how a row is fetched and where the new value goes.
@@ -70,25 +70,33 @@ __device__ inline int qtab_act_table(const MzQtabAct& a, int i) {
   return t;
 }
 
+// eps = final + (init - final) * exp(-1.0 * steps_done / decay), the reference's expression order
+__device__ inline double qtab_eps(long long steps_done, double init, double ef, double decay) {
+  const double x = __ddiv_rn(__dmul_rn(-1.0, (double)steps_done), decay);
+  return __dadd_rn(ef, __dmul_rn(__dsub_rn(init, ef), exp(x)));
+}
+
+__device__ inline int qtab_argmax(const Row& row) {  // np.argmax: the row's first maximum
+  int act = 0;
+  double m = row.v[0];
+#pragma unroll
+  for (int k = 1; k < 4; ++k)
+    if (row.v[k] > m) { m = row.v[k]; act = k; }
+  return act;
+}
+
+__device__ inline double qtab_pick(const Row& r, int k) {  // r.v[k] by selects (no scratch)
+  const double q01 = (k & 1) ? r.v[1] : r.v[0], q23 = (k & 1) ? r.v[3] : r.v[2];
+  return (k & 2) ? q23 : q01;
+}
+
 // get_action from the fetched row of state s: eps, one Philox draw, the row's first maximum.
 __device__ inline void qtab_choose(const MzQtabAct& a, int i, int t, int64_t s, const Row& row) {
-  const double x = __ddiv_rn(__dmul_rn(-1.0, (double)a.steps_done[t]), a.eps_decay[t]);
-  const double ef = a.eps_final[t];
-  const double eps = __dadd_rn(ef, __dmul_rn(__dsub_rn(a.eps_init[t], ef), exp(x)));
+  const double eps = qtab_eps(a.steps_done[t], a.eps_init[t], a.eps_final[t], a.eps_decay[t]);
   uint32_t w[4];
   mz_philox(a.seed, MZ_QTAB_STREAM ^ ((uint64_t)(uint32_t)i << 32), a.counter, w);
   const double u = (double)(w[0] >> 8) * (1.0 / 16777216.0);
-  int act;
-  if (u < eps) {
-    act = (int)(w[1] >> 30);
-  } else {
-    act = 0;
-    double m = row.v[0];
-#pragma unroll
-    for (int k = 1; k < 4; ++k)
-      if (row.v[k] > m) { m = row.v[k]; act = k; }
-  }
-  a.actions[i] = act;
+  a.actions[i] = u < eps ? (int)(w[1] >> 30) : qtab_argmax(row);
   a.sidx[i] = s;
 }
 
@@ -112,8 +120,7 @@ __device__ inline bool qtab_td(const MzQtabUpd& u, int i, Td& o, Fetch&& fetch) 
   const Row nxt = fetch(o.t, s2);
   const Row cur = fetch(o.t, o.s);
   const double future = u.terminated[i] ? 0.0 : qtab_max(nxt);
-  const double q01 = (o.act & 1) ? cur.v[1] : cur.v[0], q23 = (o.act & 1) ? cur.v[3] : cur.v[2];
-  o.old = (o.act & 2) ? q23 : q01;
+  o.old = qtab_pick(cur, o.act);
   const double td = __dsub_rn(__dadd_rn(u.reward64[i], __dmul_rn(u.gamma[o.t], future)), o.old);
   o.add = __dmul_rn(u.lr[o.t], td);
   return true;

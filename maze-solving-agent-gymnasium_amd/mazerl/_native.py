@@ -51,7 +51,9 @@ EXPORTS = ["mz_last_error", "mz_device_count", "mz_create", "mz_destroy", "mz_lo
            "mz_head_loss_backward_workspace_floats", "mz_adamw_groups",
            "mz_ppo_act", "mz_ppo_scan", "mz_ppo_finish", "mz_ppo_head_loss", "mz_qact_prepare", "mz_qact",
            "mz_qact_workspace_floats", "mz_qtab_states", "mz_qtab_act", "mz_qtab_update",
-           "mz_qtab_hash_act", "mz_qtab_hash_update", "mz_qtab_hash_rehash", "mz_qtab_hash_lookup"]
+           "mz_qtab_hash_act", "mz_qtab_hash_update", "mz_qtab_hash_rehash", "mz_qtab_hash_lookup",
+           "mz_dqtab_act", "mz_dqtab_update", "mz_dqtab_hash_act", "mz_dqtab_hash_update",
+           "mz_dqtab_hash_rehash", "mz_dqtab_hash_lookup"]
 
 _lib = None
 
@@ -181,6 +183,15 @@ def load(build_if_missing=True):
         [vp] * 14 + [C.c_int32, vp]
     L.mz_qtab_hash_rehash.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int32, vp, vp]
     L.mz_qtab_hash_lookup.argtypes = [vp, vp, C.c_int64, C.c_int32, vp, vp, C.c_int32, vp, vp, vp]
+    # the double Q-learner: the single learner's arguments; an update adds (steps_done, the three
+    # eps arrays, seed, ucounter, coin, next_action, took, which) in front of the stream
+    dq_tail = [vp] * 4 + [C.c_uint64, C.c_uint64] + [vp] * 5
+    L.mz_dqtab_act.argtypes = L.mz_qtab_act.argtypes
+    L.mz_dqtab_update.argtypes = L.mz_qtab_update.argtypes[:-1] + dq_tail
+    L.mz_dqtab_hash_act.argtypes = L.mz_qtab_hash_act.argtypes
+    L.mz_dqtab_hash_update.argtypes = L.mz_qtab_hash_update.argtypes[:-1] + dq_tail
+    L.mz_dqtab_hash_rehash.argtypes = L.mz_qtab_hash_rehash.argtypes
+    L.mz_dqtab_hash_lookup.argtypes = L.mz_qtab_hash_lookup.argtypes
     L.mz_host_alloc.argtypes = [C.c_uint64, C.c_int32, C.POINTER(vp), C.POINTER(vp)]
     L.mz_host_free.argtypes = [vp]
     for f in EXPORTS:

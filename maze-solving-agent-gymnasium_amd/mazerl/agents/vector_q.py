@@ -21,6 +21,8 @@ at the reference's maze sizes. Acting never inserts; an update inserts its state
 table drops the value update and counts it in `overflow` — size `capacity` for the states a
 learner meets, or let VectorTabularTrainer(grow_every=...) double it when it is half full.
 """
+import math
+
 import torch
 
 from .. import _native as N
@@ -85,6 +87,12 @@ def hash_slot(key, capacity):
 
 
 class VectorQAgent:
+    # what VectorDoubleQAgent (vector_dq.py) changes: a state's values ([4]; there [2, 4]), the
+    # entry points' prefix and the checkpoint formats
+    _ROW = (4,)
+    _ABI = "mz_qtab"
+    _FORMATS = (_FORMAT, _FORMAT_HASH)  # dense, hashed
+
     def __init__(self, env, tables=None, learning_rate=0.1, initial_epsilon=0.95,
                  epsilon_decay=40.0, final_epsilon=0.05, discount_factor=0.7, eta=0.01, seed=0,
                  max_bytes=8 << 30, storage="dense", capacity=None):
@@ -103,12 +111,13 @@ class VectorQAgent:
             capacity = _check_capacity(capacity)
         elif capacity is not None:
             raise ValueError("capacity belongs to storage='hash'")
+        name = type(self).__name__
         if getattr(env, "enrich", True):
-            raise ValueError("VectorQAgent needs plain observations: VectorMazeEnv(enrich=False)")
+            raise ValueError(f"{name} needs plain observations: VectorMazeEnv(enrich=False)")
         if getattr(env, "reward64", None) is None:
-            raise ValueError("VectorQAgent needs the float64 reward: VectorMazeEnv(reward64=True)")
+            raise ValueError(f"{name} needs the float64 reward: VectorMazeEnv(reward64=True)")
         if getattr(env, "_host", None) is not None:
-            raise ValueError("VectorQAgent needs device outputs (host_scalars=False)")
+            raise ValueError(f"{name} needs device outputs (host_scalars=False)")
         self.env = env
         self.device = env.device
         self.lib = env.lib
@@ -134,9 +143,10 @@ class VectorQAgent:
         if storage == "hash":
             self._check_bytes(capacity)
         else:
-            nbytes = T * self.rows * 32
+            nbytes = T * self.rows * self._row_bytes
             if nbytes > self.max_bytes:
-                raise MemoryError(f"{T} tables x {self.rows} rows x 32 B = {nbytes} B exceeds "
+                raise MemoryError(f"{T} tables x {self.rows} rows x {self._row_bytes} B = "
+                                  f"{nbytes} B exceeds "
                                   f"max_bytes = {self.max_bytes}")
         dev = self.device
         self.table_of = None if table_of is None else table_of.to(dev, torch.int32).contiguous()
@@ -146,7 +156,7 @@ class VectorQAgent:
             self.load = torch.zeros(T, dtype=torch.int32, device=dev)
             self.overflow = torch.zeros(T, dtype=torch.int64, device=dev)
         else:
-            self.q = torch.zeros(T, self.rows, 4, dtype=torch.float64, device=dev)
+            self.q = torch.zeros(T, self.rows, *self._ROW, dtype=torch.float64, device=dev)
 
         def per_table(v, name):
             t = torch.as_tensor(v, dtype=torch.float64).reshape(-1)
@@ -177,17 +187,25 @@ class VectorQAgent:
     def hashed(self):
         return self.storage == "hash"
 
+    @property
+    def _row_bytes(self):
+        return 8 * math.prod(self._ROW)
+
+    def _fn(self, name):
+        return getattr(self.lib, self._ABI + name)
+
     def _check_bytes(self, capacity):
         T = self.num_tables
-        nbytes = T * capacity * 36 + T * 12
+        slot = 4 + self._row_bytes
+        nbytes = T * capacity * slot + T * 12
         if nbytes > self.max_bytes:
-            raise MemoryError(f"{T} tables x {capacity} slots x 36 B + counters = {nbytes} B "
+            raise MemoryError(f"{T} tables x {capacity} slots x {slot} B + counters = {nbytes} B "
                               f"exceeds max_bytes = {self.max_bytes}")
 
     def _fresh(self, capacity):
         T, dev = self.num_tables, self.device
         return (torch.full((T, capacity), -1, dtype=torch.int32, device=dev),
-                torch.zeros(T, capacity, 4, dtype=torch.float64, device=dev))
+                torch.zeros(T, capacity, *self._ROW, dtype=torch.float64, device=dev))
 
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
@@ -207,10 +225,10 @@ class VectorQAgent:
                 self.counter & 0xFFFFFFFFFFFFFFFF, self.actions.data_ptr(), self.sidx.data_ptr(),
                 self._stream())
         if self.hashed:
-            N.check(self.lib.mz_qtab_hash_act(*head, self.keys.data_ptr(), self.vals.data_ptr(),
-                                              self.capacity, *tail))
+            N.check(self._fn("_hash_act")(*head, self.keys.data_ptr(), self.vals.data_ptr(),
+                                          self.capacity, *tail))
         else:
-            N.check(self.lib.mz_qtab_act(*head, self.q.data_ptr(), *tail))
+            N.check(self._fn("_act")(*head, self.q.data_ptr(), *tail))
         self.counter += 1
         return self.actions
 
@@ -258,9 +276,9 @@ class VectorQAgent:
         if t.numel() != k.numel():
             raise ValueError("one table per key")
         m = int(k.numel())
-        rows = torch.zeros(m, 4, dtype=torch.float64, device=dev)
+        rows = torch.zeros(m, *self._ROW, dtype=torch.float64, device=dev)
         slots = torch.full((m,), -1, dtype=torch.int32, device=dev)
-        N.check(self.lib.mz_qtab_hash_lookup(
+        N.check(self._fn("_hash_lookup")(
             self.keys.data_ptr(), self.vals.data_ptr(), self.capacity, self.num_tables,
             t.data_ptr(), k.data_ptr(), m, rows.data_ptr(), slots.data_ptr(), self._stream()))
         return rows, slots
@@ -275,7 +293,7 @@ class VectorQAgent:
             keys = self.keys[t][idx].to(torch.int64)
             rows = self.vals[t][idx]
         else:
-            keys = torch.nonzero(self.q[t].ne(0).any(1)).reshape(-1)
+            keys = torch.nonzero(self.q[t].ne(0).flatten(1).any(1)).reshape(-1)
             rows = self.q[t][keys]
         order = torch.argsort(keys)
         return keys[order], rows[order]
@@ -285,7 +303,7 @@ class VectorQAgent:
         if not self.hashed:
             return self.q[int(table)].clone()
         keys, rows = self.items(table)
-        out = torch.zeros(self.rows, 4, dtype=torch.float64, device=self.device)
+        out = torch.zeros(self.rows, *self._ROW, dtype=torch.float64, device=self.device)
         out[keys] = rows
         return out
 
@@ -300,7 +318,7 @@ class VectorQAgent:
             raise ValueError(f"capacity {capacity} must exceed the largest load, {top}")
         self._check_bytes(capacity)
         keys, vals = self._fresh(capacity)
-        N.check(self.lib.mz_qtab_hash_rehash(
+        N.check(self._fn("_hash_rehash")(
             self.keys.data_ptr(), self.vals.data_ptr(), self.capacity, keys.data_ptr(),
             vals.data_ptr(), capacity, self.num_tables, self.overflow.data_ptr(), self._stream()))
         self.keys, self.vals, self.capacity = keys, vals, capacity
@@ -325,13 +343,15 @@ class VectorQAgent:
                "eps_final", "eps_decay", "sidx", "actions")
     _TENSORS = ("q",) + _COMMON                                  # format /1, dense
     _TENSORS_HASH = ("keys", "vals", "load", "overflow") + _COMMON  # format /2, hashed
+    _COUNTERS = ("seed", "counter")  # host integers
 
     def state_dict(self):
         names = self._TENSORS_HASH if self.hashed else self._TENSORS
         sd = {k: getattr(self, k).clone() for k in names}
-        sd.update(format=_FORMAT_HASH if self.hashed else _FORMAT, seed=self.seed,
-                  counter=self.counter, max_dim=self.max_dim, num_tables=self.num_tables,
+        sd.update(format=self._FORMATS[self.hashed], max_dim=self.max_dim,
+                  num_tables=self.num_tables,
                   table_of=None if self.table_of is None else self.table_of.clone())
+        sd.update({k: getattr(self, k) for k in self._COUNTERS})
         if self.hashed:
             sd["capacity"] = self.capacity
         return sd
@@ -340,9 +360,9 @@ class VectorQAgent:
         """Dense agents load format /1, hashed agents format /2 (the saved capacity replaces
         this agent's)."""
         fmt = sd.get("format")
-        if fmt not in (_FORMAT, _FORMAT_HASH):
-            raise ValueError("not a VectorQAgent state_dict")
-        if fmt != (_FORMAT_HASH if self.hashed else _FORMAT):
+        if fmt not in self._FORMATS:
+            raise ValueError(f"not a {type(self).__name__} state_dict")
+        if fmt != self._FORMATS[self.hashed]:
             raise ValueError(f"a {fmt} state_dict does not load into a {self.storage} agent")
         if sd["max_dim"] != self.max_dim or sd["num_tables"] != self.num_tables or \
                 (sd["table_of"] is None) != (self.table_of is None) or \
@@ -351,7 +371,7 @@ class VectorQAgent:
         if self.hashed:
             c = _check_capacity(sd["capacity"])
             if tuple(sd["keys"].shape) != (self.num_tables, c) or \
-                    tuple(sd["vals"].shape) != (self.num_tables, c, 4):
+                    tuple(sd["vals"].shape) != (self.num_tables, c, *self._ROW):
                 raise ValueError("the saved agent's tables do not match its capacity")
             if c != self.capacity:
                 self._check_bytes(c)
@@ -363,4 +383,5 @@ class VectorQAgent:
             self.table_of.copy_(sd["table_of"])
         for k in (self._TENSORS_HASH if self.hashed else self._TENSORS):
             getattr(self, k).copy_(sd[k])
-        self.seed, self.counter = int(sd["seed"]), int(sd["counter"])
+        for k in self._COUNTERS:
+            setattr(self, k, int(sd[k]))

@@ -50,10 +50,12 @@ class VectorTabularTrainer:
     def launches_per_step(self):
         """Device launches one vector_step() issues: act + steps_done advance, the env step (and
         the memset of its done count, for an env with a done list), the update (two passes on
-        shared tables), the flag copies of keep_flags, the reset."""
+        shared tables; an agent with update_launches: that many), the flag copies of keep_flags,
+        the reset."""
         env = self.env
         return 2 + 1 + int(env._out.done_count is not None) + \
-            (1 if self.agent.table_of is None else 2) + (2 if self.terminated is not None else 0) + 1
+            getattr(self.agent, "update_launches", 1 if self.agent.table_of is None else 2) + \
+            (2 if self.terminated is not None else 0) + 1
 
     def vector_step(self):
         env, agent = self.env, self.agent

@@ -20,6 +20,13 @@ steps/s, and for hashed tables the final capacity, largest load and dropped upda
 median, and the hashed / dense ratio of the medians where both ran. Examples:
   qtab_rate.py --storage dense hash --capacity 256               9x9, both storages, both cases
   qtab_rate.py --storage hash --tables independent --size 41 --capacity 4096
+
+With --agent (and --storage) the learners are measured against each other in the same way: q is
+VectorQAgent, double is VectorDoubleQAgent (two tables per state, one more launch per vector
+step). In every round each storage runs each named agent once, in the order given; the JSON line
+then holds one entry per "storage:agent" and the double / q ratio of the medians per storage.
+  qtab_rate.py --agent q double --storage dense --tables independent
+  qtab_rate.py --agent q double --storage hash --capacity 65536 --tables shared
 """
 import argparse
 import json
@@ -50,17 +57,22 @@ def dropin(episodes):
             "env_steps_per_s": steps / secs}
 
 
-def vectorised(n, tables, warmup, steps, size=9, storage="dense", capacity=None, grow_every=0):
+def vectorised(n, tables, warmup, steps, size=9, storage="dense", capacity=None, grow_every=0,
+               agent="q"):
     import torch
     import mazerl
-    from mazerl.agents.vector_q import VectorQAgent
+    from mazerl.agents import VectorDoubleQAgent, VectorQAgent
     from mazerl.trainers.vector_tabular import VectorTabularTrainer
     env = mazerl.VectorMazeEnv(n, size, enrich=False, reward64=True, done_list=False)
     hp = dict(HP, epsilon_decay=size * size // 2)
+    double = agent == "double"
+    cls = VectorDoubleQAgent if double else VectorQAgent
+    if double:  # 4,096 dense double tables at 9x9 are 8.6 GB, just above the default limit
+        hp["max_bytes"] = 16 << 30
     if storage == "hash":
-        agent = VectorQAgent(env, tables=tables, storage="hash", capacity=capacity, **hp)
+        agent = cls(env, tables=tables, storage="hash", capacity=capacity, **hp)
     else:
-        agent = VectorQAgent(env, tables=tables, **hp)
+        agent = cls(env, tables=tables, **hp)
     trn = VectorTabularTrainer(env, agent, regen_won=True, grow_every=grow_every)
     for _ in range(warmup):
         trn.vector_step()
@@ -79,7 +91,7 @@ def vectorised(n, tables, warmup, steps, size=9, storage="dense", capacity=None,
     if storage == "hash":
         out.update(storage="hash", capacity=agent.capacity, max_load=int(agent.load.max()),
                    overflow=int(agent.overflow.sum()),
-                   table_bytes=agent.num_tables * agent.capacity * 36)
+                   table_bytes=agent.num_tables * agent.capacity * (68 if double else 36))
     env.close()
     return out
 
@@ -89,23 +101,31 @@ def storages(a):
     res = {"size": a.size, "instances": a.instances, "warmup": a.warmup, "steps": a.steps}
     cases = {"independent": None, "shared": 1}
     for case in (("independent", "shared") if a.tables == "both" else (a.tables,)):
-        runs = {st: [] for st in a.storage}
+        agents = a.agent or ["q"]
+        name = (lambda st, ag: f"{st}:{ag}") if a.agent else (lambda st, ag: st)
+        runs = {name(st, ag): [] for st in a.storage for ag in agents}
         for _ in range(a.repeats):
             for st in a.storage:
                 grow = a.grow_every if st == "hash" else 0
-                runs[st].append(vectorised(a.instances, cases[case], a.warmup, a.steps, a.size,
-                                           st, a.capacity if st == "hash" else None, grow))
+                for ag in agents:
+                    runs[name(st, ag)].append(
+                        vectorised(a.instances, cases[case], a.warmup, a.steps, a.size, st,
+                                   a.capacity if st == "hash" else None, grow, ag))
         out = {st: {"us_per_vector_step": [round(r["us_per_vector_step"], 2) for r in rs],
                     "median_us": float(np.median([r["us_per_vector_step"] for r in rs])),
                     "env_steps_per_s": [round(r["env_steps_per_s"]) for r in rs],
                     "launches_per_vector_step": rs[0]["launches_per_vector_step"],
                     "wins": [r["wins"] for r in rs], "episodes": [r["episodes"] for r in rs]}
                for st, rs in runs.items()}
-        if "hash" in runs:
-            for k in ("capacity", "max_load", "overflow", "table_bytes"):
-                out["hash"][k] = [r[k] for r in runs["hash"]]
-        if len(runs) == 2:
+        for key, rs in runs.items():
+            if key.startswith("hash"):
+                for k in ("capacity", "max_load", "overflow", "table_bytes"):
+                    out[key][k] = [r[k] for r in rs]
+        if not a.agent and len(runs) == 2:
             out["hash_over_dense_time"] = out["hash"]["median_us"] / out["dense"]["median_us"]
+        if a.agent and set(a.agent) == {"q", "double"}:
+            out["double_over_q_time"] = {st: out[f"{st}:double"]["median_us"] /
+                                         out[f"{st}:q"]["median_us"] for st in a.storage}
         res[case] = out
     print(json.dumps(res), flush=True)
 
@@ -118,6 +138,8 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--storage", nargs="+", choices=("dense", "hash"), default=None,
                     help="measure these table storages against each other (no drop-in leg)")
+    ap.add_argument("--agent", nargs="+", choices=("q", "double"), default=None,
+                    help="with --storage: measure these learners against each other")
     ap.add_argument("--tables", choices=("independent", "shared", "both"), default="both")
     ap.add_argument("--size", type=int, default=9, help="maze size of the --storage runs")
     ap.add_argument("--capacity", type=int, default=256, help="slots of a hashed table")
@@ -125,6 +147,8 @@ def main():
                     help="hashed: check the load every this many vector steps and double")
     ap.add_argument("--repeats", type=int, default=3)
     a = ap.parse_args()
+    if a.agent and not a.storage:
+        ap.error("--agent needs --storage")
     if a.storage:
         return storages(a)
     res = {"dropin_single_env": dropin(a.episodes),
