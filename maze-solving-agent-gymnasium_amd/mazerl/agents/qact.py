@@ -71,6 +71,8 @@ class QAct:
         self._ver = ver
 
     def _run(self, obs6, bits, rows, count, n, greedy, q_out):
+        if n == 0:  # nothing to evaluate (an empty tensor has no pointer to hand to the library)
+            return
         self.refresh(force=False)
         assert bits.dtype == torch.int32 and bits.shape[1] == 22 and bits.is_contiguous()
         obs6 = obs6.contiguous()

@@ -90,24 +90,15 @@ def test_qact_rows_sized_on_the_device():
         _check(q2, net((obs6, bits)))
 
 
-def _lowbias32(x):
-    x = x.astype(np.uint64) & 0xFFFFFFFF
-    x ^= x >> 16
-    x = (x * 0x7FEB352D) & 0xFFFFFFFF
-    x ^= x >> 15
-    x = (x * 0x846CA68B) & 0xFFFFFFFF
-    x ^= x >> 16
-    return x
-
-
 def test_qact_ddqn_dropout_masks():
     """DDQN acts in train mode (Dropout(0.2) after the conv activation): the
     kernel's keep decisions are a counter hash of (seed, counter, row, channel pair, pooled
     position) feeding a 4-draw xorshift32 stream per 2x2 window;
-    rebuilt here, applied to the f32 torch stem (conv -> LeakyReLU -> mask * 1/(1-p) -> MaxPool)
-    the Q values agree to the same tolerance, and P(drop) = 13107/65536."""
+    rebuilt by qact_model.keep_masks, applied to the f32 torch stem (conv -> LeakyReLU -> mask *
+    1/(1-p) -> MaxPool) the Q values agree to the same tolerance, and P(drop) = 13107/65536."""
     from mazerl.agents.nets import QNet
     from mazerl.agents.qact import QAct
+    from qact_model import drop_fraction, keep_masks
     from test_stem import _window
     torch.manual_seed(13)
     net = QNet(variant="ddqn").cuda().train()
@@ -115,29 +106,9 @@ def test_qact_ddqn_dropout_masks():
     n = bits.shape[0]
     qa = QAct(net, seed=77)
     q = qa(obs6, bits)  # counter 0
-    k = (77 * 0x9E3779B97F4A7C15 + 0 * 0xD1B54A32D192ED03 + 1) & (2**64 - 1)
-    key = np.uint64((k ^ (k >> 32)) & 0xFFFFFFFF)
-    rkey = _lowbias32(key ^ _lowbias32(np.arange(n, dtype=np.uint64)))  # [n]
-    # per (row, channel pair, pooled position) one xorshift32 stream of 4 draws, seeded from the
-    # (row, pair) base and the position: draw r (= 2 dy + dx) -> low half: even channel, high
-    # half: odd channel
-    base = _lowbias32(rkey[:, None] ^ np.arange(16, dtype=np.uint64)[None]) | 1  # [n, 16]
-    keep = np.zeros((n, 49, 32, 2, 2), bool)
-    for qi in range(49):
-        st = _lowbias32(base ^ np.uint64((qi * 0x9E3779B9) & 0xFFFFFFFF)) | 1
-        for r in range(4):
-            st ^= (st << 13) & 0xFFFFFFFF
-            st ^= st >> 17
-            st ^= (st << 5) & 0xFFFFFFFF
-            keep[:, qi, 0::2, r >> 1, r & 1] = (st & 0xFFFF) >= 13107
-            keep[:, qi, 1::2, r >> 1, r & 1] = (st >> 16) >= 13107
-    assert abs(1 - keep.mean() - 13107 / 65536) < 0.002
-    m = np.zeros((n, 32, 15, 15), np.float32)
-    qy, qx = np.arange(49) // 7, np.arange(49) % 7
-    kk = keep.transpose(0, 2, 1, 3, 4)  # [n, c, q, dy, dx]
-    for qi in range(49):
-        y, x = 2 * qy[qi], 2 * qx[qi]
-        m[:, :, y:y + 2, x:x + 2] = kk[:, :, qi]
+    keep = keep_masks(77, 0, np.arange(n), 0.2)  # bool [n, 32, 15, 15], tests/qact_model.py
+    assert abs(drop_fraction(keep) - 13107 / 65536) < 0.002
+    m = keep.astype(np.float32)
     mask = torch.from_numpy(m).cuda()
     conv = net.conv[0]
     with torch.no_grad():
