@@ -639,6 +639,50 @@ int mz_ppo_head_loss(const float* logits_dev, int32_t ldl, const float* value_de
                      float* scratch_dev, float* loss_dev, float* dlogits_dev, int32_t ldg,
                      float* dvalue_dev, int32_t ldvg, void* stream);
 
+/* ---- REINFORCE on the device (VectorReinforceTrainer) ----------------------------------------
+ * RFAgent (agents/rf_agent.py:51-129) under ValueBasedTrainer.train (lib/trainers/
+ * value_based_trainer.py:25-92), per instance. The [B][L] episode records, mz_ppo_scan and the
+ * update pool are the PPO rollout's; these three entry points are REINFORCE's own arithmetic.
+ * Each refuses a null pointer, B, L or b < 0, a temperature that is not > 0 and a row stride < 4
+ * with MZ_EINVAL before any GPU call; B == 0 / b == 0 is a no-op. */
+
+/* select_action (:73-86) from the f32 policy logits [B][ldl]: softmax(logits / temperature) as
+ * torch forms it for a 4-wide row, one draw per instance (inverse CDF of a Philox uniform keyed
+ * by (seed, counter, instance): P(a) = softmax(logits / temperature)[a], torch.multinomial's
+ * distribution); records obs6, the 22 window-bit words and the action (int64) at
+ * [i][t_dev[i]] where 0 <= t_dev[i] < L (nothing is recorded otherwise; the draw happens either
+ * way) and writes the action to act_out_dev (int32, mz_step's input). No log-prob and no value
+ * are recorded: the update recomputes the forward. */
+int mz_rf_act(const float* logits_dev, int32_t ldl, float temperature, const float* obs6_dev,
+              const uint32_t* bits_dev, int32_t B, int32_t L, uint64_t seed, uint64_t counter,
+              const int32_t* t_dev, float* rec_s6_dev, uint32_t* rec_w_dev, int64_t* rec_a_dev,
+              int32_t* act_out_dev, void* stream);
+
+/* After mz_ppo_scan, for every listed episode: get_returns (:88-99: R = r + gamma R backwards in
+ * float64, float32, (R - mean) / (std + 1e-6), unbiased std) and optimize_model's baseline
+ * (:109-110: adv = R - mean(R)) -- sums in float64, mean / std rounded to float32 -- and the
+ * episode's rows (obs6, window bits, action, adv, the episode's length on every row) into the
+ * pool columns at its rows; *episodes_dev += the episodes pooled. Rows past `capacity` are not
+ * written (the caller checks *pool_fill_dev <= capacity). One workgroup per episode. */
+int mz_rf_finish(const double* rec_r_dev, const float* rec_s6_dev, const uint32_t* rec_w_dev,
+                 const int64_t* rec_a_dev, int32_t B, int32_t L, const int32_t* fin_id_dev,
+                 const int64_t* fin_off_dev, const int32_t* fin_len_dev,
+                 const int32_t* fin_count_dev, double gamma, int64_t capacity, float* pool_s6_dev,
+                 uint32_t* pool_w_dev, int64_t* pool_a_dev, float* pool_adv_dev,
+                 int32_t* pool_len_dev, int32_t* episodes_dev, void* stream);
+
+/* optimize_model's loss (:101-118) over b pool rows of 4 logits (row stride ldl), as the mean
+ * over the E = *episodes_dev pooled episodes of the per-episode loss: with z = x / temperature,
+ * p = softmax(z), q = p + 1e-10, l = log q and T = len_dev[row],
+ *   f = (1 / E) (-adv l_a - (entropy_coef / T) (-sum_k q_k l_k))
+ * loss_dev[0] = sum of f over the rows (float64 sum in a fixed order, stored as f32) and
+ * dlogits_dev (row stride ldg) = d f / d x, in one launch. With E = 1 and the rows of one whole
+ * episode this is the reference's loss. */
+int mz_rf_head_loss(const float* logits_dev, int32_t ldl, const int64_t* action_dev,
+                    const float* adv_dev, const int32_t* len_dev, const int32_t* episodes_dev,
+                    int32_t b, float temperature, float entropy_coef, float* loss_dev,
+                    float* dlogits_dev, int32_t ldg, void* stream);
+
 /* ---- The DQN / DDQN acting forward, f32-accurate on the bf16 MFMA (mz_qact.hip) -------------
  * Replaces, per acting row, source_net(state).max(1)[1] (dqn_agent.py:113-116; the nets of
  * dqn_agent.py:19-57 / ddqn_agent.py:18-52 at the reference's sizes: Conv2d(3, 32, 3, p 1),

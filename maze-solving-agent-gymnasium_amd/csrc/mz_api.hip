@@ -1433,6 +1433,65 @@ int mz_ppo_head_loss(const float* logits_dev, int32_t ldl, const float* value_de
   return MZ_OK;
 }
 
+int mz_rf_act(const float* logits_dev, int32_t ldl, float temperature, const float* obs6_dev,
+              const uint32_t* bits_dev, int32_t B, int32_t L, uint64_t seed, uint64_t counter,
+              const int32_t* t_dev, float* rec_s6_dev, uint32_t* rec_w_dev, int64_t* rec_a_dev,
+              int32_t* act_out_dev, void* stream) {
+  if (!logits_dev || !obs6_dev || !bits_dev || !t_dev || !rec_s6_dev || !rec_w_dev ||
+      !rec_a_dev || !act_out_dev)
+    return fail(MZ_EINVAL, "mz_rf_act: null pointer");
+  if (B < 0 || L < 0) return fail(MZ_EINVAL, "mz_rf_act: B %d, L %d", B, L);
+  if (!(temperature > 0.0f)) return fail(MZ_EINVAL, "mz_rf_act: temperature %g", temperature);
+  if (ldl < 4) return fail(MZ_EINVAL, "mz_rf_act: logits row stride %d < 4", ldl);
+  if (B == 0) return MZ_OK;
+  StreamGuard g(stream);
+  MzRfAct q{logits_dev, ldl, temperature, obs6_dev, bits_dev, B, L, seed, counter, t_dev,
+            rec_s6_dev, rec_w_dev, rec_a_dev, act_out_dev};
+  MZ_HIP(mz_launch_rf_act(q, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_rf_finish(const double* rec_r_dev, const float* rec_s6_dev, const uint32_t* rec_w_dev,
+                 const int64_t* rec_a_dev, int32_t B, int32_t L, const int32_t* fin_id_dev,
+                 const int64_t* fin_off_dev, const int32_t* fin_len_dev,
+                 const int32_t* fin_count_dev, double gamma, int64_t capacity, float* pool_s6_dev,
+                 uint32_t* pool_w_dev, int64_t* pool_a_dev, float* pool_adv_dev,
+                 int32_t* pool_len_dev, int32_t* episodes_dev, void* stream) {
+  if (!rec_r_dev || !rec_s6_dev || !rec_w_dev || !rec_a_dev || !fin_id_dev || !fin_off_dev ||
+      !fin_len_dev || !fin_count_dev || !pool_s6_dev || !pool_w_dev || !pool_a_dev ||
+      !pool_adv_dev || !pool_len_dev || !episodes_dev)
+    return fail(MZ_EINVAL, "mz_rf_finish: null pointer");
+  if (B < 0 || L < 0 || capacity < 0)
+    return fail(MZ_EINVAL, "mz_rf_finish: B %d, L %d, capacity %lld", B, L, (long long)capacity);
+  if (B == 0) return MZ_OK;
+  StreamGuard g(stream);
+  MzRfFinish q{rec_r_dev, rec_s6_dev, rec_w_dev, rec_a_dev, B, L, fin_id_dev, fin_off_dev,
+               fin_len_dev, fin_count_dev, gamma, capacity, pool_s6_dev, pool_w_dev, pool_a_dev,
+               pool_adv_dev, pool_len_dev, episodes_dev};
+  MZ_HIP(mz_launch_rf_finish(q, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_rf_head_loss(const float* logits_dev, int32_t ldl, const int64_t* action_dev,
+                    const float* adv_dev, const int32_t* len_dev, const int32_t* episodes_dev,
+                    int32_t b, float temperature, float entropy_coef, float* loss_dev,
+                    float* dlogits_dev, int32_t ldg, void* stream) {
+  if (!logits_dev || !action_dev || !adv_dev || !len_dev || !episodes_dev || !loss_dev ||
+      !dlogits_dev)
+    return fail(MZ_EINVAL, "mz_rf_head_loss: null pointer");
+  if (b < 0) return fail(MZ_EINVAL, "mz_rf_head_loss: b %d", b);
+  if (!(temperature > 0.0f))
+    return fail(MZ_EINVAL, "mz_rf_head_loss: temperature %g", temperature);
+  if (ldl < 4 || ldg < 4)
+    return fail(MZ_EINVAL, "mz_rf_head_loss: row strides %d / %d < 4", ldl, ldg);
+  if (b == 0) return MZ_OK;
+  StreamGuard g(stream);
+  MzRfHead q{logits_dev, ldl, action_dev, adv_dev, len_dev, episodes_dev, b, temperature,
+             entropy_coef, loss_dev, dlogits_dev, ldg};
+  MZ_HIP(mz_launch_rf_head(q, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
 int mz_qact_prepare(const float* fc1_w_dev, const float* fc2_w_dev, uint16_t* w1_hi_dev,
                     uint16_t* w1_lo_dev, uint16_t* w2_hi_dev, uint16_t* w2_lo_dev, void* stream) {
   if (!fc1_w_dev || !fc2_w_dev || !w1_hi_dev || !w1_lo_dev || !w2_hi_dev || !w2_lo_dev)

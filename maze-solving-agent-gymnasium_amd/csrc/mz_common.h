@@ -163,6 +163,7 @@ __host__ __device__ inline void mz_philox(uint64_t key, uint64_t ctr_hi, uint64_
 #define MZ_ACT_STREAM 0x61637421ull  // 'act!': exploration draws
 #define MZ_REPLAY_STREAM 0x72706c79ull  // 'rply': replay sample rows
 #define MZ_PPO_STREAM 0x70706f21ull  // 'ppo!': PPO policy draws
+#define MZ_RF_STREAM 0x72666121ull  // 'rfa!': REINFORCE policy draws
 #define MZ_QTAB_STREAM 0x71746162ull  // 'qtab': tabular Q-learning exploration draws
 #define MZ_DQTAB_STREAM 0x64717462ull  // 'dqtb': double Q-learning update draws (coin, inner action)
 

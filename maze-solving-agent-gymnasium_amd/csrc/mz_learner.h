@@ -1,5 +1,5 @@
 // mz_learner.h — launchers of the learner / trainer kernels (mz_stem, mz_optim, mz_qnet,
-// mz_trainer, mz_ppo, mz_qact), used by the C ABI (mz_api.hip).
+// mz_trainer, mz_ppo, mz_reinforce, mz_qact), used by the C ABI (mz_api.hip).
 #pragma once
 #include "mz_kernels.h"
 
@@ -117,6 +117,33 @@ struct MzPpoHead {  // fused loss of one minibatch (4 actions)
   float* loss; float* dlogits; int ldg; float* dvalue; int ldvg;
 };
 hipError_t mz_launch_ppo_head(const MzPpoHead& q, float clip, hipStream_t s);
+
+// ---- REINFORCE (mz_reinforce.hip); the records, k_ppo_scan and the pool are PPO's -------------
+struct MzRfAct {
+  const float* logits; int ldl; float tau;  // policy logits [B][ldl >= 4], f32; temperature
+  const float* obs6; const uint32_t* bits;
+  int B, L;
+  uint64_t seed, counter;
+  const int32_t* t;
+  float* b_s6; uint32_t* b_w; int64_t* b_a;  // [B][L] records
+  int32_t* act_out;
+};
+struct MzRfFinish {
+  const double* b_r; const float* b_s6; const uint32_t* b_w; const int64_t* b_a; int B, L;
+  const int32_t* fin_id; const int64_t* fin_off; const int32_t* fin_len; const int32_t* fin_count;
+  double gamma; int64_t cap;
+  float* p_s6; uint32_t* p_w; int64_t* p_a; float* p_adv; int32_t* p_len;
+  int32_t* episodes;                         // += the episodes pooled
+};
+struct MzRfHead {
+  const float* logits; int ldl;
+  const int64_t* action; const float* adv; const int32_t* len; const int32_t* episodes;
+  int b; float tau, coef;
+  float* loss; float* dlogits; int ldg;
+};
+hipError_t mz_launch_rf_act(const MzRfAct& q, hipStream_t s);
+hipError_t mz_launch_rf_finish(const MzRfFinish& q, hipStream_t s);
+hipError_t mz_launch_rf_head(const MzRfHead& q, hipStream_t s);
 
 // ---- f32-accurate acting forward on the bf16 MFMA (mz_qact.hip) ------------------------------
 struct MzQAct {

@@ -49,7 +49,8 @@ EXPORTS = ["mz_last_error", "mz_device_count", "mz_create", "mz_destroy", "mz_lo
            "mz_replay_sample_idx", "mz_q_loss", "mz_q_loss_backward", "mz_head_loss",
            "mz_head_loss_backward", "mz_head_loss_workspace_floats",
            "mz_head_loss_backward_workspace_floats", "mz_adamw_groups",
-           "mz_ppo_act", "mz_ppo_scan", "mz_ppo_finish", "mz_ppo_head_loss", "mz_qact_prepare", "mz_qact",
+           "mz_ppo_act", "mz_ppo_scan", "mz_ppo_finish", "mz_ppo_head_loss", "mz_rf_act", "mz_rf_finish",
+           "mz_rf_head_loss", "mz_qact_prepare", "mz_qact",
            "mz_qact_workspace_floats", "mz_qtab_states", "mz_qtab_act", "mz_qtab_update",
            "mz_qtab_hash_act", "mz_qtab_hash_update", "mz_qtab_hash_rehash", "mz_qtab_hash_lookup",
            "mz_dqtab_act", "mz_dqtab_update", "mz_dqtab_hash_act", "mz_dqtab_hash_update",
@@ -169,6 +170,12 @@ def load(build_if_missing=True):
                                    C.c_float, vp, vp, vp, C.c_int32, vp, C.c_int32, vp]
     L.mz_ppo_finish.argtypes = [vp] * 6 + [C.c_int32, C.c_int32] + [vp] * 4 + \
         [C.c_double, C.c_int64] + [vp] * 7
+    L.mz_rf_act.argtypes = [vp, C.c_int32, C.c_float, vp, vp, C.c_int32, C.c_int32, C.c_uint64,
+                            C.c_uint64] + [vp] * 6
+    L.mz_rf_finish.argtypes = [vp] * 4 + [C.c_int32, C.c_int32] + [vp] * 4 + \
+        [C.c_double, C.c_int64] + [vp] * 7
+    L.mz_rf_head_loss.argtypes = [vp, C.c_int32, vp, vp, vp, vp, C.c_int32, C.c_float, C.c_float,
+                                  vp, vp, C.c_int32, vp]
     L.mz_qact_prepare.argtypes = [vp] * 7
     L.mz_qact.argtypes = [vp, vp, vp, vp, C.c_int32] + [vp] * 10 + [C.c_int32, C.c_float,
                                                                    C.c_uint64, C.c_uint64] + [vp] * 4

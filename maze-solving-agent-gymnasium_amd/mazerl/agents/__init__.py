@@ -1,6 +1,7 @@
-"""The agents. The vectorised tabular populations are exported here by name; they are imported on
-first use, so importing a sibling module stays as light as it was."""
-_EXPORTS = {"VectorQAgent": "vector_q", "VectorDoubleQAgent": "vector_dq"}
+"""The agents. The vectorised tabular populations and the REINFORCE drop-in are exported here by
+name; they are imported on first use, so importing a sibling module stays as light as it was."""
+_EXPORTS = {"VectorQAgent": "vector_q", "VectorDoubleQAgent": "vector_dq", "RFAgent": "rf_agent",
+            "PolicyNetwork": "rf_agent"}
 __all__ = sorted(_EXPORTS)
 
 
