@@ -59,6 +59,53 @@ def test_fused_head_matches_unfused(variant, flat, b):
         torch.testing.assert_close(x, y, rtol=2e-4, atol=1e-6, msg=n)
 
 
+@pytest.mark.parametrize("flat", ["grads", "flat-adjacent", "flat-apart"])
+@pytest.mark.parametrize("variant", ["dqn", "ddqn"])
+@pytest.mark.parametrize("b", [5, 17])
+@pytest.mark.parametrize("hidden", [8, 520])
+def test_fused_head_through_autograd_matches_float64_net(hidden, b, variant, flat):
+    """q_loss through _HeadLossFn at head widths other than 512 (H = 4: most lanes hold no column;
+    H = 260: one full trip of the 256-column loop and a 4-column tail) and batch sizes that fill
+    neither the forward's 4-row nor the backward's 16-row workgroups, against a float64 copy of the
+    nets on the expanded windows: the loss (rel 1e-5) and the gradients of fc.0, fc.2 and fc.4
+    (rtol 1e-4, atol 1e-5 x scale: the f32-versus-f64 tolerances of test_learner_overlap.py).
+    conv.0's gradients are discontinuous near a pool tie and belong to test_stem.py. With flat
+    gradients, both branches of _HeadLossFn.backward: fc3's bias segment right behind its weight's
+    (one column sum into both), and apart from it."""
+    import mazerl.agents.dqn as D
+    from mazerl.agents.flat import flatten_grads, grad_segment
+    from mazerl.agents.nets import QNet
+    from test_stem import _close, _window
+    torch.manual_seed(5)
+    src = QNet(3, 6, 4, 32, hidden, variant).cuda().eval()
+    tgt = QNet(3, 6, 4, 32, hidden, variant).cuda().eval()
+    ref, reft = copy.deepcopy(src).double(), copy.deepcopy(tgt).double()
+    state, a, r, nxt = _batch(b, 13)
+    fc3 = src.fc[4]
+    if flat != "grads":
+        flatten_grads(src)
+        if flat == "flat-apart":
+            fc3.bias._grad_seg = (torch.zeros(4, device="cuda"), 0)
+        gw, gb = grad_segment(fc3.weight), grad_segment(fc3.bias)
+        assert (gb.data_ptr() == gw.data_ptr() + 16 * (hidden // 2)) == (flat == "flat-adjacent")
+    dbl = variant == "ddqn"
+    assert D._head_ok(src, tgt, state, a, r)  # the fused head route
+    loss = D.q_loss(src, tgt, state, a, r, nxt, 0.7, dbl)
+    assert isinstance(loss.grad_fn, D._HeadLossFn._backward_cls)
+    loss.backward()
+    wide = lambda s: (s[0].double(), _window(s[1].cpu()).cuda().double())  # noqa: E731
+    loss_ref = D.q_loss(ref, reft, wide(state), a, r.double(), wide(nxt), 0.7, dbl)
+    loss_ref.backward()
+    torch.cuda.synchronize()
+    assert float(loss) == pytest.approx(float(loss_ref), rel=1e-5)
+    for (name, p), pr in zip(src.named_parameters(), ref.parameters()):
+        if name.startswith("fc."):
+            assert _close(p.grad, pr.grad.float(), 1e-4, 1e-5), name
+    if flat != "grads":
+        assert fc3.weight.grad.data_ptr() == gw.data_ptr()
+        assert fc3.bias.grad.data_ptr() == gb.data_ptr()
+
+
 def test_fused_head_loss_is_deterministic():
     """Two launches on the same rows give the same loss and gradients bit for bit (the loss and
     the fc3 gradient sums run in a fixed order: per block, then over blocks)."""

@@ -82,6 +82,69 @@ def test_q_loss_matches_reference_gpu(fx, case):
     _compare(fx, case, src, loss, "cuda")
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["dqn_full", "ddqn_full"])
+def test_production_update_matches_reference_gpu(fx, case):
+    """The update as VectorDQNLearner runs it — packed int32 windows through the HIP stem, the
+    fused head + loss, gradients written into the flat buffer, the one-launch clamp + AdamW with
+    write_grad off — against the reference's optimize_model fixture, with _compare's tolerances:
+    once eagerly and once as a captured graph replayed from the restored state, the two bit for
+    bit the same. (write_grad off leaves the unclamped gradient behind; the fixture's is clamped
+    to +-1, which this batch's gradients never reach: asserted.)"""
+    from mazerl.agents import dqn as D
+    from mazerl.agents.flat import FlatAdamW, flatten_grads, flatten_params, grads_are_flat
+    variant, h, hid, n, gamma, lr, train = U.CASES[case]
+    assert not train
+    src, tgt = QNet(3, 6, 4, h, hid, variant), QNet(3, 6, 4, h, hid, variant)
+    U.fill_params(src, 11)
+    U.fill_params(tgt, 22)
+    src.cuda().eval()
+    tgt.cuda().eval()
+    flatten_params(tgt)
+    opt = FlatAdamW(src, lr, write_grad=False)
+    flat_g = flatten_grads(src)
+    s6, w, a, r, s6n, wn = U.make_batch(n, 33)
+    random.seed(44)
+    perm = random.sample(range(n), n)
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x[perm])).cuda()  # noqa: E731
+    state = (t(s6), U.pack_windows(w[perm]).cuda())
+    nxt = (t(s6n), U.pack_windows(wn[perm]).cuda())
+    assert state[1].dtype == torch.int32 and tuple(state[1].shape) == (n, 22)
+    action = t(a)
+    reward = torch.tensor(tuple(float(x) for x in r[perm])).cuda()
+    assert D._head_ok(src, tgt, state, action, reward)  # the fused head route
+    bufs = (src._flat_params, opt.exp_avg, opt.exp_avg_sq, opt._step_buf)
+    saved = [x.clone() for x in bufs]
+
+    def update():
+        loss = q_loss(src, tgt, state, action, reward, nxt, gamma, variant == "ddqn")
+        assert isinstance(loss.grad_fn, D._HeadLossFn._backward_cls)
+        learner_update(src, opt, loss)
+        return loss.detach()
+
+    def result(loss):
+        torch.cuda.synchronize()
+        assert grads_are_flat(src) and float(opt.step_t) == 1.0
+        assert float(flat_g.abs().max()) < 1.0  # unclamped == clamped
+        return [loss.clone(), flat_g.clone()] + [x.clone() for x in bufs]
+
+    eager = result(update())
+    _compare(fx, case, src, float(eager[0]), "cuda")
+    opt.zero_grad(set_to_none=True)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        loss_g = update()
+    with torch.no_grad():
+        for x, y in zip(bufs, saved):
+            x.copy_(y)
+        flat_g.zero_()
+    graph.replay()
+    replayed = result(loss_g)
+    for x, y in zip(eager, replayed):
+        assert torch.equal(x.view(torch.int32), y.view(torch.int32))
+    _compare(fx, case, src, float(replayed[0]), "cuda")
+
+
 def test_architecture_counts():
     """2,140,548 parameters, 4,665,024 FLOP per sample forward."""
     assert count_params(QNet(variant="dqn")) == 2_140_548
