@@ -683,6 +683,81 @@ int mz_rf_head_loss(const float* logits_dev, int32_t ldl, const int64_t* action_
                     int32_t b, float temperature, float entropy_coef, float* loss_dev,
                     float* dlogits_dev, int32_t ldg, void* stream);
 
+/* ---- The recurrent DQN on the device (VectorRecurrentDQNTrainer) -----------------------------
+ * agents/lstm_dqn_agent.py: nn.LSTMCell(6, 32) + nn.Linear(32, 4) over obs6, trained from whole
+ * episodes. params_dev is a HOST array of six device pointers in state_dict order
+ * (lstm_cell.weight_ih [128][6], weight_hh [128][32], bias_ih [128], bias_hh [128], fc.weight
+ * [4][32], fc.bias [4]; torch's layouts, gate order i, f, g, o). A gate pre-activation is
+ * (bias_ih + bias_hh), then the 6 input terms, then the 32 recurrent terms, one fmaf each; a q
+ * value is fc.bias then 32 fmaf. The reward records [B][L] (float64), t_dev and the finished
+ * episodes' list are mz_ppo_scan's. Every entry point refuses a null pointer, B < 1, E < 1,
+ * hidden != 32 and capacity < E with MZ_EINVAL before any GPU call. */
+
+/* One acting step of B instances: from (h, c) (h_dev / c_dev, [32][B] f32, updated in place; taken
+ * as zero where t_dev[i] == 0) and x = obs6_dev[i] the cell and the head, then the action: one
+ * Philox draw per instance keyed by (seed, counter, instance) — word 0 (24 bits) < epsilon
+ * explores, and the action is then floor(word 1 * explore_actions / 2^32); else the first argmax
+ * of q. Where 0 <= t_dev[i] < L, x goes to rec_x_dev[i][t] ([B][L + 1][6]) and the action to
+ * rec_a_dev[i][t] ([B][L] int32); where t_dev[i] is outside, the action is still produced but
+ * nothing is recorded and (h, c) stay as they were. L == 0 is the evaluation mode: no records
+ * (rec pointers may be NULL) and every instance's state advances. act_out_dev: int32 [B];
+ * q_out_dev: f32 [B][4] or NULL. */
+int mz_drqn_act(const float* const* params_dev, int32_t hidden, const float* obs6_dev, int32_t B,
+                int32_t L, float epsilon, int32_t explore_actions, uint64_t seed, uint64_t counter,
+                const int32_t* t_dev, float* h_dev, float* c_dev, float* rec_x_dev,
+                int32_t* rec_a_dev, int32_t* act_out_dev, float* q_out_dev, void* stream);
+
+/* After mz_ppo_scan, for its k-th listed episode (instance i, n steps): obs6_dev[i] (the
+ * observation after the last step) into rec_x_dev[i][n], and the episode into ring slot
+ * (head + k) mod capacity: n + 1 rows of 8 words (x[6] f32, action i32, reward f32 = (float) of
+ * the float64 record; row n holds x_n only), mem_len_dev[slot] = n, mem_term_dev[slot] =
+ * term_dev[i] != 0. Then ring_dev (int64: head, count) moves on by the listed episodes. With
+ * more listed episodes than slots the last `capacity` of them stay. mz_ppo_scan does not list
+ * 1-step episodes, so none reaches the memory. */
+int mz_drqn_store(const float* obs6_dev, const uint8_t* term_dev, int32_t B, int32_t L,
+                  const int32_t* fin_id_dev, const int32_t* fin_len_dev,
+                  const int32_t* fin_count_dev, float* rec_x_dev, const int32_t* rec_a_dev,
+                  const double* rec_r_dev, int64_t capacity, uint32_t* mem_dev,
+                  int32_t* mem_len_dev, int32_t* mem_term_dev, int64_t* ring_dev, void* stream);
+
+/* E distinct slots of the filled part of the ring, every E-subset equally likely (Philox keyed by
+ * (seed, counter)), and the batch directory: dir_slot / dir_len [E] int32, dir_off [E] int64 =
+ * the exclusive scan of (len + 1) (an episode's first row in the update's row buffers), dir_tot
+ * int64 [2] = (rows = sum (len + 1), steps = sum len). `filled` is the caller's knowledge of the
+ * ring's count (the device's count is at least that); E > filled is refused. */
+int mz_drqn_sample(uint64_t seed, uint64_t counter, int32_t E, int32_t L, int64_t capacity,
+                   int64_t filled, const int64_t* ring_dev, const int32_t* mem_len_dev,
+                   int32_t* dir_slot_dev, int32_t* dir_len_dev, int64_t* dir_off_dev,
+                   int64_t* dir_tot_dev, void* stream);
+
+/* The net unrolled from zero state over each directory episode, one wave per episode. Row buffers
+ * hold E (L + 1) rows; episode e uses rows dir_off[e] .. dir_off[e] + len (the last is a guard
+ * row only the target writes). target != 0: x_0 .. x_n, qmax_dev[row] = max_a Q'_t (the other
+ * outputs may be NULL). target == 0: x_0 .. x_{n-1}; reads qmax_dev; per step stash_dev[row][192]
+ * (gates i, f, g, o after their nonlinearity, c, h), qa_dev = Q_t[a_t], y_dev = r_t + gamma
+ * qmax[t + 1] (r_t alone at the last step of a terminated episode), d_dev = 2 (Q_t[a_t] - y_t) /
+ * steps; ep_loss_dev[e] (float64) = the episode's sum of squared residuals in time order. */
+int mz_drqn_seq_forward(const float* const* params_dev, int32_t hidden, int32_t target, int32_t E,
+                        int32_t L, int64_t capacity, float gamma, const uint32_t* mem_dev,
+                        const int32_t* mem_term_dev, const int32_t* dir_slot_dev,
+                        const int32_t* dir_len_dev, const int64_t* dir_off_dev,
+                        const int64_t* dir_tot_dev, float* qmax_dev, float* stash_dev,
+                        float* qa_dev, float* y_dev, float* d_dev, double* ep_loss_dev,
+                        void* stream);
+
+/* Back-propagation through time of loss = sum of squared residuals / steps from the source
+ * forward's stash and d_dev: one wave per episode writes its gradient to gpart_dev [E][5252] (flat
+ * state_dict order), then per parameter the partials are summed over the episodes in index order
+ * (float64, rounded once) into grads_dev (a HOST array of six device pointers, state_dict order;
+ * overwritten, not accumulated) and loss_dev[0] = sum of ep_loss / steps. No atomics: the same
+ * inputs give the same bits. */
+int mz_drqn_seq_backward(const float* const* params_dev, int32_t hidden, int32_t E, int32_t L,
+                         int64_t capacity, const uint32_t* mem_dev, const int32_t* dir_slot_dev,
+                         const int32_t* dir_len_dev, const int64_t* dir_off_dev,
+                         const int64_t* dir_tot_dev, const float* stash_dev, const float* d_dev,
+                         const double* ep_loss_dev, float* gpart_dev, float* const* grads_dev,
+                         float* loss_dev, void* stream);
+
 /* ---- The DQN / DDQN acting forward, f32-accurate on the bf16 MFMA (mz_qact.hip) -------------
  * Replaces, per acting row, source_net(state).max(1)[1] (dqn_agent.py:113-116; the nets of
  * dqn_agent.py:19-57 / ddqn_agent.py:18-52 at the reference's sizes: Conv2d(3, 32, 3, p 1),

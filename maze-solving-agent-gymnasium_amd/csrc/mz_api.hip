@@ -1492,6 +1492,123 @@ int mz_rf_head_loss(const float* logits_dev, int32_t ldl, const int64_t* action_
   return MZ_OK;
 }
 
+// ---- recurrent DQN (mz_drqn.hip) ---------------------------------------------------------------
+static bool drqn_net(const float* const* params_dev, MzDrqnNet* p) {
+  if (!params_dev) return false;
+  for (int k = 0; k < 6; ++k)
+    if (!params_dev[k]) return false;
+  *p = MzDrqnNet{params_dev[0], params_dev[1], params_dev[2], params_dev[3], params_dev[4],
+                 params_dev[5]};
+  return true;
+}
+
+int mz_drqn_act(const float* const* params_dev, int32_t hidden, const float* obs6_dev, int32_t B,
+                int32_t L, float epsilon, int32_t explore_actions, uint64_t seed, uint64_t counter,
+                const int32_t* t_dev, float* h_dev, float* c_dev, float* rec_x_dev,
+                int32_t* rec_a_dev, int32_t* act_out_dev, float* q_out_dev, void* stream) {
+  MzDrqnNet p;
+  if (!drqn_net(params_dev, &p) || !obs6_dev || !t_dev || !h_dev || !c_dev || !act_out_dev ||
+      (L > 0 && (!rec_x_dev || !rec_a_dev)))
+    return fail(MZ_EINVAL, "mz_drqn_act: null pointer");
+  if (hidden != MZ_DRQN_HIDDEN) return fail(MZ_EINVAL, "mz_drqn_act: hidden %d != 32", hidden);
+  if (B < 1 || L < 0) return fail(MZ_EINVAL, "mz_drqn_act: B %d, L %d", B, L);
+  if (!(epsilon >= 0.0f && epsilon <= 1.0f) || explore_actions < 1 || explore_actions > 4)
+    return fail(MZ_EINVAL, "mz_drqn_act: epsilon %g, explore_actions %d", epsilon,
+                explore_actions);
+  StreamGuard g(stream);
+  MzDrqnAct q{p, obs6_dev, B, L, epsilon, explore_actions, seed, counter, t_dev, h_dev, c_dev,
+              h_dev, c_dev, rec_x_dev, rec_a_dev, act_out_dev, q_out_dev};
+  MZ_HIP(mz_launch_drqn_act(q, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_drqn_store(const float* obs6_dev, const uint8_t* term_dev, int32_t B, int32_t L,
+                  const int32_t* fin_id_dev, const int32_t* fin_len_dev,
+                  const int32_t* fin_count_dev, float* rec_x_dev, const int32_t* rec_a_dev,
+                  const double* rec_r_dev, int64_t capacity, uint32_t* mem_dev,
+                  int32_t* mem_len_dev, int32_t* mem_term_dev, int64_t* ring_dev, void* stream) {
+  if (!obs6_dev || !term_dev || !fin_id_dev || !fin_len_dev || !fin_count_dev || !rec_x_dev ||
+      !rec_a_dev || !rec_r_dev || !mem_dev || !mem_len_dev || !mem_term_dev || !ring_dev)
+    return fail(MZ_EINVAL, "mz_drqn_store: null pointer");
+  if (B < 1 || L < 1 || capacity < 1)
+    return fail(MZ_EINVAL, "mz_drqn_store: B %d, L %d, capacity %lld", B, L, (long long)capacity);
+  StreamGuard g(stream);
+  MzDrqnStore q{obs6_dev, term_dev, B, L, fin_id_dev, fin_len_dev, fin_count_dev, rec_x_dev,
+                rec_a_dev, rec_r_dev, capacity, mem_dev, mem_len_dev, mem_term_dev, ring_dev};
+  MZ_HIP(mz_launch_drqn_store(q, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_drqn_sample(uint64_t seed, uint64_t counter, int32_t E, int32_t L, int64_t capacity,
+                   int64_t filled, const int64_t* ring_dev, const int32_t* mem_len_dev,
+                   int32_t* dir_slot_dev, int32_t* dir_len_dev, int64_t* dir_off_dev,
+                   int64_t* dir_tot_dev, void* stream) {
+  if (!ring_dev || !mem_len_dev || !dir_slot_dev || !dir_len_dev || !dir_off_dev || !dir_tot_dev)
+    return fail(MZ_EINVAL, "mz_drqn_sample: null pointer");
+  if (E < 1 || E > 8192 || L < 1 || capacity < E || filled > capacity || filled < E)
+    return fail(MZ_EINVAL, "mz_drqn_sample: E %d (1..8192), L %d, capacity %lld, filled %lld", E,
+                L, (long long)capacity, (long long)filled);
+  StreamGuard g(stream);
+  MzDrqnSample q{seed, counter, E, L, capacity, ring_dev, mem_len_dev, dir_slot_dev, dir_len_dev,
+                 dir_off_dev, dir_tot_dev};
+  MZ_HIP(mz_launch_drqn_sample(q, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+static int drqn_seq_args(const char* who, int32_t hidden, int32_t E, int32_t L, int64_t capacity) {
+  if (hidden != MZ_DRQN_HIDDEN) return fail(MZ_EINVAL, "%s: hidden %d != 32", who, hidden);
+  if (E < 1 || L < 1 || capacity < E)
+    return fail(MZ_EINVAL, "%s: E %d, L %d, capacity %lld", who, E, L, (long long)capacity);
+  return MZ_OK;
+}
+
+int mz_drqn_seq_forward(const float* const* params_dev, int32_t hidden, int32_t target, int32_t E,
+                        int32_t L, int64_t capacity, float gamma, const uint32_t* mem_dev,
+                        const int32_t* mem_term_dev, const int32_t* dir_slot_dev,
+                        const int32_t* dir_len_dev, const int64_t* dir_off_dev,
+                        const int64_t* dir_tot_dev, float* qmax_dev, float* stash_dev,
+                        float* qa_dev, float* y_dev, float* d_dev, double* ep_loss_dev,
+                        void* stream) {
+  MzDrqnNet p;
+  if (!drqn_net(params_dev, &p) || !mem_dev || !mem_term_dev || !dir_slot_dev || !dir_len_dev ||
+      !dir_off_dev || !dir_tot_dev || !qmax_dev ||
+      (!target && (!stash_dev || !qa_dev || !y_dev || !d_dev || !ep_loss_dev)))
+    return fail(MZ_EINVAL, "mz_drqn_seq_forward: null pointer");
+  if (int rc = drqn_seq_args("mz_drqn_seq_forward", hidden, E, L, capacity)) return rc;
+  StreamGuard g(stream);
+  MzDrqnSeq q{p, target ? 1 : 0, E, L, capacity, gamma, mem_dev, mem_term_dev, dir_slot_dev,
+              dir_len_dev, dir_off_dev, dir_tot_dev, qmax_dev, stash_dev, qa_dev, y_dev, d_dev,
+              ep_loss_dev, nullptr};
+  MZ_HIP(mz_launch_drqn_seq_forward(q, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_drqn_seq_backward(const float* const* params_dev, int32_t hidden, int32_t E, int32_t L,
+                         int64_t capacity, const uint32_t* mem_dev, const int32_t* dir_slot_dev,
+                         const int32_t* dir_len_dev, const int64_t* dir_off_dev,
+                         const int64_t* dir_tot_dev, const float* stash_dev, const float* d_dev,
+                         const double* ep_loss_dev, float* gpart_dev, float* const* grads_dev,
+                         float* loss_dev, void* stream) {
+  MzDrqnNet p;
+  if (!drqn_net(params_dev, &p) || !mem_dev || !dir_slot_dev || !dir_len_dev || !dir_off_dev ||
+      !dir_tot_dev || !stash_dev || !d_dev || !ep_loss_dev || !gpart_dev || !grads_dev ||
+      !loss_dev)
+    return fail(MZ_EINVAL, "mz_drqn_seq_backward: null pointer");
+  for (int k = 0; k < 6; ++k)
+    if (!grads_dev[k]) return fail(MZ_EINVAL, "mz_drqn_seq_backward: null gradient segment");
+  if (int rc = drqn_seq_args("mz_drqn_seq_backward", hidden, E, L, capacity)) return rc;
+  StreamGuard g(stream);
+  MzDrqnSeq q{p, 0, E, L, capacity, 0.0f, mem_dev, nullptr, dir_slot_dev, dir_len_dev,
+              dir_off_dev, dir_tot_dev, nullptr, const_cast<float*>(stash_dev), nullptr, nullptr,
+              const_cast<float*>(d_dev), nullptr, gpart_dev};
+  MZ_HIP(mz_launch_drqn_seq_backward(q, static_cast<hipStream_t>(stream)));
+  MzDrqnReduce r{E, gpart_dev, ep_loss_dev, dir_len_dev, dir_tot_dev,
+                 {grads_dev[0], grads_dev[1], grads_dev[2], grads_dev[3], grads_dev[4],
+                  grads_dev[5]}, loss_dev};
+  MZ_HIP(mz_launch_drqn_reduce(r, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
 int mz_qact_prepare(const float* fc1_w_dev, const float* fc2_w_dev, uint16_t* w1_hi_dev,
                     uint16_t* w1_lo_dev, uint16_t* w2_hi_dev, uint16_t* w2_lo_dev, void* stream) {
   if (!fc1_w_dev || !fc2_w_dev || !w1_hi_dev || !w1_lo_dev || !w2_hi_dev || !w2_lo_dev)

@@ -1,0 +1,540 @@
+// mz_drqn.hip — the recurrent DQN (agents/lstm_dqn_agent.py: nn.LSTMCell(6, 32) + nn.Linear(32, 4)
+// over obs6) on the device: the acting step with its per-instance (h, c), the episode replay
+// memory, and the sequence forward / TD target / back-propagation through time of an update.
+//
+// The net (5,252 parameters, torch's layouts and gate order i, f, g, o):
+//   z = (bias_ih + bias_hh) + W_ih x + W_hh h      [128]
+//   c' = sigmoid(z_f) c + sigmoid(z_i) tanh(z_g),  h' = sigmoid(z_o) tanh(c'),  q = fc_b + fc_w h'
+// ACCUMULATION ORDER, the same in every kernel here: a gate pre-activation starts from the f32 sum
+// bias_ih + bias_hh, then takes the 6 input terms k = 0..5, then the 32 recurrent terms k = 0..31,
+// one fmaf each; a q value starts from fc_b and takes the 32 terms k = 0..31, one fmaf each.
+// sigmoid(z) = 1 / (1 + expf(-z)); tanh is tanhf.
+//
+// Per vector step (trainers/drqn_trainer.py VectorRecurrentDQNTrainer):
+//   k_drqn_act    four lanes per instance, eight units each. The parameters are staged in LDS once
+//                 per workgroup; the old h is held in registers, c streams through; both live
+//                 in HBM as [32][B] so a wave's loads and stores coalesce. One Philox
+//                 draw per instance decides explore / greedy and the uniform action. Records
+//                 (x_t, a_t) at t[i]; zero state where t[i] == 0. L == 0 is the evaluation mode:
+//                 nothing is recorded and every instance's state advances.
+//   (mz_step, k_ppo_scan)   the reward record, t[i] += 1, the finished episodes' list
+//   k_drqn_store  one workgroup per finished episode: x_n into the record, the episode into the
+//                 ring slot (head + k) mod capacity; k_drqn_ring advances head and count.
+// Per update:
+//   k_drqn_sample    one wave: E distinct slots of the filled ring (Floyd's subset sampling), the
+//                    batch directory (slot, length, row offset, totals).
+//   k_drqn_seq_fwd   one wave per episode. Lane l = (unit u = l & 31, half = l >> 5) owns gate rows
+//                    (i_u, f_u) or (g_u, o_u): its 2 x 38 weights stay in registers for the whole
+//                    episode, h goes round through LDS. Target mode writes max_a Q'_t; source mode
+//                    stashes (i, f, g, o, c, h) per step (768 B a row), and writes Q_t[a_t], y_t,
+//                    the scaled residual 2 (Q_t[a_t] - y_t) / sum n and the episode's sum of
+//                    squared residuals (float64, time order).
+//   k_drqn_seq_bwd   one wave per episode, same lane layout: BPTT from the stash; the weight
+//                    gradients accumulate in registers over the time loop and are written once,
+//                    as the episode's partial in the flat parameter order.
+//   k_drqn_reduce    per parameter the partials summed over the episodes in index order (float64,
+//                    rounded once) into the net's gradient segments; the loss (float64, episode
+//                    order). No float atomics anywhere: two runs give the same bits.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "mz_common.h"
+#include "mz_learner.h"
+
+namespace {
+
+constexpr int WAVE = 64;
+constexpr int H = MZ_DRQN_HIDDEN;  // 32
+constexpr int G4 = 4 * H;          // 128 gate rows
+constexpr int NX = 6;
+constexpr int ACT_T = 64;          // k_drqn_act threads: one wave, so the workgroups spread over the CUs
+constexpr int ROW = MZ_DRQN_ROW_WORDS;  // 8 words per replay row: x[6], action, reward
+constexpr int STASH = MZ_DRQN_STASH;    // 192 floats per stashed step
+// offsets into the flat parameter order
+constexpr int P_WIH = 0, P_WHH = P_WIH + G4 * NX, P_BIH = P_WHH + G4 * H, P_BHH = P_BIH + G4,
+              P_FCW = P_BHH + G4, P_FCB = P_FCW + 4 * H;
+static_assert(P_FCB + 4 == MZ_DRQN_PARAMS, "parameter count");
+
+__device__ inline float sigmoidf_(float z) { return 1.0f / (1.0f + expf(-z)); }
+
+// LDS image of the parameters for k_drqn_act: per gate row 40 floats (bias, 6 x, pad, 32 h) so a
+// row starts 16-B aligned; then fc (4 x 32) and fc_b
+constexpr int AROW = 40;
+constexpr int A_FC = G4 * AROW, A_FCB = A_FC + 4 * H, A_TOT = A_FCB + 4;
+#ifndef MZ_DRQN_ACT_PARTS
+#define MZ_DRQN_ACT_PARTS 4  // threads per instance (1, 2 or 4; profiles/exp_lstm_dqn_probe.py)
+#endif
+constexpr int PARTS = MZ_DRQN_ACT_PARTS;
+constexpr int IPB = ACT_T / PARTS;  // instances per workgroup
+static_assert(PARTS == 1 || PARTS == 2 || PARTS == 4, "threads per instance");
+
+// Thread (j = tid % IPB, part = tid / IPB) of instance i = block * IPB + j computes the units
+// u = part, part + PARTS, ...: the parts of one instance sit IPB lanes apart, so a wave's loads of
+// h / c ([32][B]) stay coalesced, and their weight rows sit AROW = 40 floats apart in LDS, which
+// puts the (up to 4) distinct 16-B addresses of a wave's ds_read_b128 on different banks. Every
+// thread holds the instance's whole old h in registers. The new h goes round through LDS for the
+// head: part a computes q[a] (a + PARTS, ...) in the fixed order, part 0 draws and records.
+__global__ __launch_bounds__(ACT_T) void k_drqn_act(MzDrqnAct q) {
+  __shared__ __attribute__((aligned(16))) float w[A_TOT];
+  __shared__ float hq[IPB][H + 1];
+  __shared__ float qs[IPB][4];
+  for (int e = threadIdx.x; e < G4; e += ACT_T) {
+    float* d = w + e * AROW;
+    d[0] = q.p.b_ih[e] + q.p.b_hh[e];
+    for (int k = 0; k < NX; ++k) d[1 + k] = q.p.w_ih[e * NX + k];
+    for (int k = 0; k < H; ++k) d[8 + k] = q.p.w_hh[e * H + k];
+    d[7] = 0.0f;
+  }
+  for (int e = threadIdx.x; e < 4 * H; e += ACT_T) w[A_FC + e] = q.p.fc_w[e];
+  if (threadIdx.x < 4) w[A_FCB + threadIdx.x] = q.p.fc_b[threadIdx.x];
+  __syncthreads();
+  const int j = threadIdx.x % IPB, part = threadIdx.x / IPB;
+  const int i = blockIdx.x * IPB + j;
+  const bool live = i < q.B;
+  const int ii = live ? i : q.B - 1;  // a tail thread shadows the last instance and writes nothing
+  const size_t B = (size_t)q.B;
+  const int t = q.t[ii];
+  const bool eval = q.L == 0;
+  const bool rec = live && t >= 0 && t < q.L;
+  const bool adv = live && (rec || eval);  // the state advances
+  const bool zero = t == 0;
+  float x[NX], h[H];
+#pragma unroll
+  for (int k = 0; k < NX; ++k) x[k] = q.obs6[(size_t)ii * NX + k];
+#pragma unroll
+  for (int k = 0; k < H; ++k) h[k] = zero ? 0.0f : q.h[k * B + ii];
+  // every part has read the old h before any part stores a new one (h_out may alias h)
+  __syncthreads();
+  for (int u = part; u < H; u += PARTS) {
+    float z[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const float4* r = reinterpret_cast<const float4*>(w + (g * H + u) * AROW);
+      const float4 r0 = r[0], r1 = r[1];
+      float acc = r0.x;
+      acc = fmaf(r0.y, x[0], acc);
+      acc = fmaf(r0.z, x[1], acc);
+      acc = fmaf(r0.w, x[2], acc);
+      acc = fmaf(r1.x, x[3], acc);
+      acc = fmaf(r1.y, x[4], acc);
+      acc = fmaf(r1.z, x[5], acc);
+#pragma unroll
+      for (int k4 = 0; k4 < H / 4; ++k4) {
+        const float4 v = r[2 + k4];
+        acc = fmaf(v.x, h[4 * k4 + 0], acc);
+        acc = fmaf(v.y, h[4 * k4 + 1], acc);
+        acc = fmaf(v.z, h[4 * k4 + 2], acc);
+        acc = fmaf(v.w, h[4 * k4 + 3], acc);
+      }
+      z[g] = acc;
+    }
+    const float c0 = zero ? 0.0f : q.c[u * B + ii];
+    const float c1 = sigmoidf_(z[1]) * c0 + sigmoidf_(z[0]) * tanhf(z[2]);
+    const float h1 = sigmoidf_(z[3]) * tanhf(c1);
+    if (adv) {
+      q.c_out[u * B + i] = c1;
+      q.h_out[u * B + i] = h1;
+    }
+    hq[j][u] = h1;
+  }
+  __syncthreads();
+  for (int a = part; a < 4; a += PARTS) {
+    float acc = w[A_FCB + a];
+#pragma unroll
+    for (int k = 0; k < H; ++k) acc = fmaf(w[A_FC + a * H + k], hq[j][k], acc);
+    qs[j][a] = acc;
+  }
+  __syncthreads();
+  if (part != 0 || !live) return;
+  const float qv[4] = {qs[j][0], qs[j][1], qs[j][2], qs[j][3]};
+  // greedy: the first maximum (torch.max's index); a NaN row acts 0
+  int a = 0;
+#pragma unroll
+  for (int k = 1; k < 4; ++k)
+    if (qv[k] > qv[a]) a = k;
+  uint32_t r[4];
+  mz_philox(q.seed, MZ_DRQN_STREAM ^ ((uint64_t)(uint32_t)i << 32), q.counter, r);
+  const float uni = (float)(r[0] >> 8) * (1.0f / 16777216.0f);  // [0, 1), 24 bits
+  if (uni < q.eps) a = (int)(((uint64_t)r[1] * (uint64_t)q.explore) >> 32);
+  if (rec) {
+    float* dst = q.rec_x + ((size_t)i * (q.L + 1) + t) * NX;
+#pragma unroll
+    for (int k = 0; k < NX; ++k) dst[k] = x[k];
+    q.rec_a[(size_t)i * q.L + t] = a;
+  }
+  q.act_out[i] = a;
+  if (q.q_out) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) q.q_out[(size_t)i * 4 + k] = qv[k];
+  }
+}
+
+// ---- replay memory ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_drqn_store(MzDrqnStore q) {
+  const int nfin = min(max(*q.fin_count, 0), q.B);
+  const int64_t head = q.ring[0];
+  // more finished episodes than slots: the last `capacity` stay (a deque's maxlen)
+  const int first = nfin > q.cap ? nfin - (int)q.cap : 0;
+  for (int k = first + blockIdx.x; k < nfin; k += gridDim.x) {
+    const int i = q.fin_id[k], n = q.fin_len[k];
+    if (i < 0 || i >= q.B || n < 1 || n > q.L || head < 0 || head >= q.cap) continue;
+    const int64_t slot = (head + k) % q.cap;
+    float* rx = q.rec_x + (size_t)i * (q.L + 1) * NX;
+    if (threadIdx.x < NX) rx[(size_t)n * NX + threadIdx.x] = q.obs6[(size_t)i * NX + threadIdx.x];
+    __syncthreads();
+    uint32_t* dst = q.mem + (size_t)slot * (q.L + 1) * ROW;
+    const int32_t* ra = q.rec_a + (size_t)i * q.L;
+    const double* rr = q.rec_r + (size_t)i * q.L;
+    for (int e = threadIdx.x; e < (n + 1) * ROW; e += blockDim.x) {
+      const int t = e / ROW, j = e % ROW;
+      uint32_t v = 0;
+      if (j < NX) v = __float_as_uint(rx[(size_t)t * NX + j]);
+      else if (t < n) v = j == NX ? (uint32_t)ra[t] : __float_as_uint((float)rr[t]);
+      dst[e] = v;
+    }
+    if (threadIdx.x == 0) {
+      q.mem_len[slot] = n;
+      q.mem_term[slot] = q.term[i] != 0 ? 1 : 0;
+    }
+    __syncthreads();
+  }
+}
+
+// after k_drqn_store (same stream): head and count move on by the stored episodes
+__global__ void k_drqn_ring(const int32_t* fin_count, int B, int64_t cap, int64_t* ring) {
+  const int64_t nfin = min(max(*fin_count, 0), B);
+  const int64_t head = ring[0], count = ring[1];
+  if (head < 0 || head >= cap) return;
+  ring[0] = (head + nfin) % cap;
+  ring[1] = count + nfin < cap ? count + nfin : cap;
+}
+
+// E distinct slots, every E-subset of the filled slots equally likely (Floyd): for j = n - E .. n - 1
+// draw v uniform in [0, j]; take v unless already taken, else j. The draw is the high word of
+// u32 * (j + 1) (bias below 2^-32 (j + 1)). While count < capacity the filled slots are 0 ..
+// count - 1; afterwards all of them.
+__global__ __launch_bounds__(WAVE) void k_drqn_sample(MzDrqnSample q) {
+  extern __shared__ int32_t chosen[];  // [E]
+  const int lane = threadIdx.x;
+  int64_t n64 = q.ring[1];
+  if (n64 > q.cap) n64 = q.cap;
+  const int n = (int)n64;
+  if (n < q.E) {  // the host checked its own count: nothing to train on
+    for (int e = lane; e < q.E; e += WAVE) {
+      q.d_slot[e] = 0;
+      q.d_len[e] = 0;
+      q.d_off[e] = 0;
+    }
+    if (lane == 0) q.d_tot[0] = q.d_tot[1] = 0;
+    return;
+  }
+  for (int m = 0; m < q.E; ++m) {
+    const int j = n - q.E + m;
+    uint32_t r[4];
+    mz_philox(q.seed, MZ_DRQN_SAMPLE_STREAM ^ ((uint64_t)(uint32_t)m << 32), q.counter, r);
+    const int v = (int)(((uint64_t)r[0] * (uint64_t)(j + 1)) >> 32);
+    bool hit = false;
+    for (int e = lane; e < m; e += WAVE) hit |= chosen[e] == v;
+    const int pick = __any(hit) ? j : v;
+    __syncthreads();
+    if (lane == 0) chosen[m] = pick;
+    __syncthreads();
+  }
+  if (lane == 0) {
+    int64_t rows = 0, steps = 0;
+    for (int e = 0; e < q.E; ++e) {
+      const int s = chosen[e];
+      int len = q.mem_len[s];
+      if (len < 1 || len > q.L) len = 0;  // (never: the store writes 1..L)
+      q.d_slot[e] = s;
+      q.d_len[e] = len;
+      q.d_off[e] = rows;
+      rows += len + 1;
+      steps += len;
+    }
+    q.d_tot[0] = rows;
+    q.d_tot[1] = steps;
+  }
+}
+
+// ---- the sequence forward --------------------------------------------------------------------
+__global__ __launch_bounds__(WAVE) void k_drqn_seq_fwd(MzDrqnSeq q) {
+  __shared__ __attribute__((aligned(16))) float hs[H];
+  const int e = blockIdx.x;
+  const int lane = threadIdx.x, u = lane & (H - 1), half = lane >> 5;
+  const int n = q.d_len[e], slot = q.d_slot[e];
+  const int64_t off = q.d_off[e];
+  if (n < 1 || n > q.L || slot < 0 || slot >= q.cap || off < 0 ||
+      off + n + 1 > (int64_t)q.E * (q.L + 1))
+    return;
+  const uint32_t* ep = q.mem + (size_t)slot * (q.L + 1) * ROW;
+  const int r0 = half * 2 * H + u, r1 = r0 + H;  // (i_u, f_u) or (g_u, o_u)
+  float b0 = q.p.b_ih[r0] + q.p.b_hh[r0], b1 = q.p.b_ih[r1] + q.p.b_hh[r1];
+  float wx0[NX], wx1[NX], wh0[H], wh1[H], fw[H];
+#pragma unroll
+  for (int k = 0; k < NX; ++k) {
+    wx0[k] = q.p.w_ih[r0 * NX + k];
+    wx1[k] = q.p.w_ih[r1 * NX + k];
+  }
+#pragma unroll
+  for (int k = 0; k < H; ++k) {
+    wh0[k] = q.p.w_hh[r0 * H + k];
+    wh1[k] = q.p.w_hh[r1 * H + k];
+    fw[k] = q.p.fc_w[(lane & 3) * H + k];
+  }
+  const float fb = q.p.fc_b[lane & 3];
+  float hb[H];
+#pragma unroll
+  for (int k = 0; k < H; ++k) hb[k] = 0.0f;
+  float c = 0.0f;
+  const int steps = q.target ? n + 1 : n;
+  const float inv = q.target ? 0.0f : (float)(1.0 / (double)q.d_tot[1]);
+  const bool term = q.mem_term[slot] != 0;
+  double sq = 0.0;
+  for (int t = 0; t < steps; ++t) {
+    const uint4 ra = *reinterpret_cast<const uint4*>(ep + (size_t)t * ROW);
+    const uint4 rb = *reinterpret_cast<const uint4*>(ep + (size_t)t * ROW + 4);
+    const float x[NX] = {__uint_as_float(ra.x), __uint_as_float(ra.y), __uint_as_float(ra.z),
+                         __uint_as_float(ra.w), __uint_as_float(rb.x), __uint_as_float(rb.y)};
+    float z0 = b0, z1 = b1;
+#pragma unroll
+    for (int k = 0; k < NX; ++k) {
+      z0 = fmaf(wx0[k], x[k], z0);
+      z1 = fmaf(wx1[k], x[k], z1);
+    }
+#pragma unroll
+    for (int k = 0; k < H; ++k) {
+      z0 = fmaf(wh0[k], hb[k], z0);
+      z1 = fmaf(wh1[k], hb[k], z1);
+    }
+    const float v0 = half ? tanhf(z0) : sigmoidf_(z0);  // g or i
+    const float v1 = sigmoidf_(z1);                     // o or f
+    const float p0 = __shfl_xor(v0, 32), p1 = __shfl_xor(v1, 32);
+    const float gi = half ? p0 : v0, gf = half ? p1 : v1, gg = half ? v0 : p0, go = half ? v1 : p1;
+    c = gf * c + gi * gg;
+    const float h = go * tanhf(c);
+    __syncthreads();
+    if (!half) hs[u] = h;
+    __syncthreads();
+#pragma unroll
+    for (int k4 = 0; k4 < H / 4; ++k4) {
+      const float4 v = reinterpret_cast<const float4*>(hs)[k4];
+      hb[4 * k4 + 0] = v.x;
+      hb[4 * k4 + 1] = v.y;
+      hb[4 * k4 + 2] = v.z;
+      hb[4 * k4 + 3] = v.w;
+    }
+    float qa = fb;  // q[lane & 3]
+#pragma unroll
+    for (int k = 0; k < H; ++k) qa = fmaf(fw[k], hb[k], qa);
+    const float q0 = __shfl(qa, 0), q1 = __shfl(qa, 1), q2 = __shfl(qa, 2), q3 = __shfl(qa, 3);
+    const int64_t R = off + t;
+    if (q.target) {
+      if (lane == 0) q.qmax[R] = fmaxf(fmaxf(q0, q1), fmaxf(q2, q3));
+      continue;
+    }
+    float* st = q.stash + (size_t)R * STASH;
+    st[r0] = v0;
+    st[r1] = v1;
+    if (!half) st[G4 + u] = c; else st[G4 + H + u] = h;
+    const int a = (int)rb.z & 3;
+    const float rew = __uint_as_float(rb.w);
+    const float qsel = a == 0 ? q0 : (a == 1 ? q1 : (a == 2 ? q2 : q3));
+    const bool last = t == n - 1;
+    const float y = (last && term) ? rew : fmaf(q.gamma, q.qmax[R + 1], rew);
+    const float d = qsel - y;
+    sq += (double)d * (double)d;
+    if (lane == 0) {
+      q.qa[R] = qsel;
+      q.y[R] = y;
+      q.d[R] = 2.0f * d * inv;
+    }
+  }
+  if (!q.target && lane == 0) q.ep_loss[e] = sq;
+}
+
+// ---- back-propagation through time -----------------------------------------------------------
+__global__ __launch_bounds__(WAVE) void k_drqn_seq_bwd(MzDrqnSeq q) {
+  __shared__ __attribute__((aligned(16))) float dzs[G4];
+  const int e = blockIdx.x;
+  const int lane = threadIdx.x, u = lane & (H - 1), half = lane >> 5;
+  const int n = q.d_len[e], slot = q.d_slot[e];
+  const int64_t off = q.d_off[e];
+  float* gp = q.gpart + (size_t)e * MZ_DRQN_PARAMS;
+  if (n < 1 || n > q.L || slot < 0 || slot >= q.cap || off < 0 ||
+      off + n + 1 > (int64_t)q.E * (q.L + 1)) {
+    for (int k = lane; k < MZ_DRQN_PARAMS; k += WAVE) gp[k] = 0.0f;
+    return;
+  }
+  const uint32_t* ep = q.mem + (size_t)slot * (q.L + 1) * ROW;
+  const int r0 = half * 2 * H + u, r1 = r0 + H;
+  // W_hh^T: this lane's unit column over its half's 64 gate rows
+  float wt[2 * H];
+#pragma unroll
+  for (int j = 0; j < 2 * H; ++j) wt[j] = q.p.w_hh[(half * 2 * H + j) * H + u];
+  float fcu[4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) fcu[a] = q.p.fc_w[a * H + u];
+  float gx0[NX], gx1[NX], gh0[H], gh1[H], gfc[4], gfb[4];
+#pragma unroll
+  for (int k = 0; k < NX; ++k) gx0[k] = gx1[k] = 0.0f;
+#pragma unroll
+  for (int k = 0; k < H; ++k) gh0[k] = gh1[k] = 0.0f;
+#pragma unroll
+  for (int a = 0; a < 4; ++a) gfc[a] = gfb[a] = 0.0f;
+  float gb0 = 0.0f, gb1 = 0.0f, dh_next = 0.0f, dc_next = 0.0f;
+  for (int t = n - 1; t >= 0; --t) {
+    const int64_t R = off + t;
+    const float* st = q.stash + (size_t)R * STASH;
+    const float gi = st[u], gf = st[H + u], gg = st[2 * H + u], go = st[3 * H + u];
+    const float ct = st[G4 + u], ht = st[G4 + H + u];
+    const float cp = t ? st[G4 + u - STASH] : 0.0f;
+    float hp[H];
+    if (t) {
+      const float4* hv = reinterpret_cast<const float4*>(st - STASH + G4 + H);
+#pragma unroll
+      for (int k4 = 0; k4 < H / 4; ++k4) {
+        const float4 v = hv[k4];
+        hp[4 * k4 + 0] = v.x;
+        hp[4 * k4 + 1] = v.y;
+        hp[4 * k4 + 2] = v.z;
+        hp[4 * k4 + 3] = v.w;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < H; ++k) hp[k] = 0.0f;
+    }
+    const uint4 ra = *reinterpret_cast<const uint4*>(ep + (size_t)t * ROW);
+    const uint4 rb = *reinterpret_cast<const uint4*>(ep + (size_t)t * ROW + 4);
+    const float x[NX] = {__uint_as_float(ra.x), __uint_as_float(ra.y), __uint_as_float(ra.z),
+                         __uint_as_float(ra.w), __uint_as_float(rb.x), __uint_as_float(rb.y)};
+    const int a = (int)rb.z & 3;
+    const float d = q.d[R];  // d loss / d Q_t[a_t], the 1 / sum n folded in
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      gfc[k] += k == a ? d * ht : 0.0f;
+      gfb[k] += k == a ? d : 0.0f;
+    }
+    const float fsel = a == 0 ? fcu[0] : (a == 1 ? fcu[1] : (a == 2 ? fcu[2] : fcu[3]));
+    const float dh = fmaf(d, fsel, dh_next);
+    const float tc = tanhf(ct);
+    const float dc = fmaf(dh * go, 1.0f - tc * tc, dc_next);
+    const float dzi = dc * gg * gi * (1.0f - gi);
+    const float dzf = dc * cp * gf * (1.0f - gf);
+    const float dzg = dc * gi * (1.0f - gg * gg);
+    const float dzo = dh * tc * go * (1.0f - go);
+    dc_next = dc * gf;
+    const float dz0 = half ? dzg : dzi, dz1 = half ? dzo : dzf;
+    gb0 += dz0;
+    gb1 += dz1;
+#pragma unroll
+    for (int k = 0; k < NX; ++k) {
+      gx0[k] = fmaf(dz0, x[k], gx0[k]);
+      gx1[k] = fmaf(dz1, x[k], gx1[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < H; ++k) {
+      gh0[k] = fmaf(dz0, hp[k], gh0[k]);
+      gh1[k] = fmaf(dz1, hp[k], gh1[k]);
+    }
+    // dh_{t-1}[u] = sum over the 128 gate rows of W_hh[row][u] dz[row]: each half its 64 rows in
+    // row order, then the two halves added
+    __syncthreads();
+    dzs[r0] = dz0;
+    dzs[r1] = dz1;
+    __syncthreads();
+    float part = 0.0f;
+#pragma unroll
+    for (int j4 = 0; j4 < 2 * H / 4; ++j4) {
+      const float4 v = reinterpret_cast<const float4*>(dzs + half * 2 * H)[j4];
+      part = fmaf(wt[4 * j4 + 0], v.x, part);
+      part = fmaf(wt[4 * j4 + 1], v.y, part);
+      part = fmaf(wt[4 * j4 + 2], v.z, part);
+      part = fmaf(wt[4 * j4 + 3], v.w, part);
+    }
+    dh_next = part + __shfl_xor(part, 32);
+  }
+#pragma unroll
+  for (int k = 0; k < NX; ++k) {
+    gp[P_WIH + r0 * NX + k] = gx0[k];
+    gp[P_WIH + r1 * NX + k] = gx1[k];
+  }
+#pragma unroll
+  for (int k = 0; k < H; ++k) {
+    gp[P_WHH + r0 * H + k] = gh0[k];
+    gp[P_WHH + r1 * H + k] = gh1[k];
+  }
+  gp[P_BIH + r0] = gb0;
+  gp[P_BIH + r1] = gb1;
+  gp[P_BHH + r0] = gb0;
+  gp[P_BHH + r1] = gb1;
+  if (!half) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a) gp[P_FCW + a * H + u] = gfc[a];
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a) gp[P_FCB + a] = gfb[a];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_drqn_reduce(MzDrqnReduce q) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < MZ_DRQN_PARAMS) {
+    double s = 0.0;
+    for (int e = 0; e < q.E; ++e) s += (double)q.gpart[(size_t)e * MZ_DRQN_PARAMS + k];
+    float* dst;
+    int o;
+    if (k < P_WHH) { dst = q.g[0]; o = k - P_WIH; }
+    else if (k < P_BIH) { dst = q.g[1]; o = k - P_WHH; }
+    else if (k < P_BHH) { dst = q.g[2]; o = k - P_BIH; }
+    else if (k < P_FCW) { dst = q.g[3]; o = k - P_BHH; }
+    else if (k < P_FCB) { dst = q.g[4]; o = k - P_FCW; }
+    else { dst = q.g[5]; o = k - P_FCB; }
+    dst[o] = (float)s;
+  }
+  if (k == 0) {
+    double s = 0.0;
+    for (int e = 0; e < q.E; ++e)
+      if (q.d_len[e] > 0) s += q.ep_loss[e];
+    const int64_t steps = q.d_tot[1];
+    *q.loss = steps > 0 ? (float)(s / (double)steps) : 0.0f;
+  }
+}
+
+}  // namespace
+
+hipError_t mz_launch_drqn_act(const MzDrqnAct& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_act, dim3((q.B + IPB - 1) / IPB), dim3(ACT_T), 0, s, q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_store(const MzDrqnStore& q, hipStream_t s) {
+  const int blocks = q.B < 2048 ? q.B : 2048;
+  hipLaunchKernelGGL(k_drqn_store, dim3(blocks), dim3(256), 0, s, q);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_drqn_ring, dim3(1), dim3(1), 0, s, q.fin_count, q.B, q.cap, q.ring);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_sample(const MzDrqnSample& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_sample, dim3(1), dim3(WAVE), (size_t)q.E * sizeof(int32_t), s, q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_seq_forward(const MzDrqnSeq& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_seq_fwd, dim3(q.E), dim3(WAVE), 0, s, q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_seq_backward(const MzDrqnSeq& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_seq_bwd, dim3(q.E), dim3(WAVE), 0, s, q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_reduce(const MzDrqnReduce& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_reduce, dim3((MZ_DRQN_PARAMS + 255) / 256), dim3(256), 0, s, q);
+  return hipGetLastError();
+}

@@ -1,5 +1,5 @@
 // mz_learner.h — launchers of the learner / trainer kernels (mz_stem, mz_optim, mz_qnet,
-// mz_trainer, mz_ppo, mz_reinforce, mz_qact), used by the C ABI (mz_api.hip).
+// mz_trainer, mz_ppo, mz_reinforce, mz_drqn, mz_qact), used by the C ABI (mz_api.hip).
 #pragma once
 #include "mz_kernels.h"
 
@@ -144,6 +144,56 @@ struct MzRfHead {
 hipError_t mz_launch_rf_act(const MzRfAct& q, hipStream_t s);
 hipError_t mz_launch_rf_finish(const MzRfFinish& q, hipStream_t s);
 hipError_t mz_launch_rf_head(const MzRfHead& q, hipStream_t s);
+
+// ---- recurrent DQN (mz_drqn.hip); the reward records and k_ppo_scan are PPO's ------------------
+#define MZ_DRQN_HIDDEN 32
+#define MZ_DRQN_PARAMS 5252     // 128 x 6 + 128 x 32 + 128 + 128 + 4 x 32 + 4
+#define MZ_DRQN_ROW_WORDS 8     // a replay row: x[6] f32, action i32, reward f32
+#define MZ_DRQN_STASH 192       // floats stashed per source step: i, f, g, o, c, h
+struct MzDrqnNet {              // torch's LSTMCell / Linear layouts, f32
+  const float *w_ih, *w_hh, *b_ih, *b_hh, *fc_w, *fc_b;
+};
+struct MzDrqnAct {
+  MzDrqnNet p;
+  const float* obs6; int B, L;               // L == 0: evaluation (no record, every state advances)
+  float eps; int explore;                    // explore: actions the uniform draw covers
+  uint64_t seed, counter;
+  const int32_t* t;
+  const float *h, *c; float *h_out, *c_out;  // [32][B]; out may alias in
+  float* rec_x; int32_t* rec_a;              // [B][L + 1][6], [B][L]
+  int32_t* act_out; float* q_out;            // [B]; [B][4] or null
+};
+struct MzDrqnStore {
+  const float* obs6; const uint8_t* term; int B, L;
+  const int32_t* fin_id; const int32_t* fin_len; const int32_t* fin_count;
+  float* rec_x; const int32_t* rec_a; const double* rec_r;
+  int64_t cap; uint32_t* mem; int32_t* mem_len; int32_t* mem_term;  // [cap][L + 1][8], [cap], [cap]
+  int64_t* ring;                             // head, count
+};
+struct MzDrqnSample {
+  uint64_t seed, counter; int E, L; int64_t cap;
+  const int64_t* ring; const int32_t* mem_len;
+  int32_t* d_slot; int32_t* d_len; int64_t* d_off; int64_t* d_tot;  // [E] x 3; rows, steps
+};
+struct MzDrqnSeq {
+  MzDrqnNet p;
+  int target, E, L; int64_t cap; float gamma;
+  const uint32_t* mem; const int32_t* mem_term;
+  const int32_t* d_slot; const int32_t* d_len; const int64_t* d_off; const int64_t* d_tot;
+  float* qmax;                               // [rows] max_a Q'_t (target: out; source: in)
+  float* stash; float* qa; float* y; float* d; double* ep_loss;  // source: out; backward: in
+  float* gpart;                              // backward: [E][MZ_DRQN_PARAMS]
+};
+struct MzDrqnReduce {
+  int E; const float* gpart; const double* ep_loss; const int32_t* d_len; const int64_t* d_tot;
+  float* g[6]; float* loss;
+};
+hipError_t mz_launch_drqn_act(const MzDrqnAct& q, hipStream_t s);
+hipError_t mz_launch_drqn_store(const MzDrqnStore& q, hipStream_t s);
+hipError_t mz_launch_drqn_sample(const MzDrqnSample& q, hipStream_t s);
+hipError_t mz_launch_drqn_seq_forward(const MzDrqnSeq& q, hipStream_t s);
+hipError_t mz_launch_drqn_seq_backward(const MzDrqnSeq& q, hipStream_t s);
+hipError_t mz_launch_drqn_reduce(const MzDrqnReduce& q, hipStream_t s);
 
 // ---- f32-accurate acting forward on the bf16 MFMA (mz_qact.hip) ------------------------------
 struct MzQAct {

@@ -1,0 +1,414 @@
+"""Vectorised recurrent DQN — the reference's LSTM agent (agents/lstm_dqn_agent.py: an
+nn.LSTMCell(6, 32) + nn.Linear(32, 4) Q-network over obs6, whole episodes in
+SequentialExperienceReplayMemory, lib/replay_memory.py:26-43) over B instances at once, on plain
+(enrich=False) or Enrich envs, euclidean or toroidal. Only obs6 is read.
+
+Per vector step, with no host round trip once the memory holds a batch (csrc/mz_drqn.hip):
+  act      mz_drqn_act: the cell and the head from each instance's (h, c) ([32][B] in HBM), the
+           eps-greedy draw, the record of (x_t, a_t) at t[i];
+  step     the env step;
+  scan     mz_ppo_scan, unchanged (the f32 reward widened to its float64 record; t[i] += 1; the
+           finished episodes' list in instance order). It drops 1-step episodes, so none reaches
+           the memory;
+  store    mz_drqn_store: x_n and each finished episode into ring slot (head + k) mod capacity;
+  reset    winners get new mazes, truncated instances restart theirs (schedule.py as REINFORCE);
+  update   when due: mz_drqn_sample (E distinct slots + the batch directory), the target net's
+           sequence forward (max_a Q'_t), the source net's (Q_t[a_t], y_t, residuals, the stash),
+           mz_drqn_seq_backward (BPTT, gradients reduced in a fixed order into the flat gradient
+           segments), then FlatAdamW (the reference's clamp_(-1, 1) + AdamW in one launch).
+
+The reference defines the net, the gate order, eps = final + (start - final) exp(-steps / decay),
+episodes as the unit of replay sampled without replacement, the MSE loss, the clamp, AdamW at
+torch's defaults, CosineAnnealingLR(T_max=30, eta_min=1e-6), the target sync by load_state_dict
+and update_steps_done; all kept. It leaves the agent unfinished (no trainer drives it,
+optimize_model zips episodes as transitions, get_action explores over randrange(2), the hidden
+state is resized to the batch and never restored). Six departures fix the semantics:
+  1. acting state: each instance carries (h, c), zero at the first step of every episode,
+     advanced once per env step with the parameters of that moment;
+  2. exploration: with probability eps a uniform action over `explore_actions` (default 4, the
+     env's action_space.n; 2 reproduces the reference's leftover);
+  3. eps clock: one step count per population, +1 per vector step (every instance has made that
+     many get_action calls); update_steps_done() halves it;
+  4. episode record: x_0 .. x_n (x_n: the observation after the last step), a_0 .. a_{n-1},
+     r_0 .. r_{n-1} (float32 of the env's reward), terminated; records are L + 1 rows,
+     L = episode_bound;
+  5. loss: over E sampled episodes, source unrolled from zero state over x_0 .. x_{n-1}, target
+     over x_0 .. x_n; y_t = r_t + gamma max_a Q'_{t+1}[a], y_{n-1} = r_{n-1} when terminated (a
+     truncated last step bootstraps from x_n); loss = mean over all sum n steps of
+     (Q_t[a_t] - y_t)^2; no gradient through y;
+  6. cadence: one update per `train_every` vector steps once the memory holds >= batch_size
+     episodes; target sync every `target_update_frequency` updates; the cosine schedule advances
+     once per update.
+Training on truncated windows, burn-in and stored recurrent state (R2D2) are out of scope.
+"""
+import ctypes as C
+import time
+
+import torch
+
+from .. import _native as N
+from ..agents.flat import FlatAdamW, copy_flat, flatten_grads, flatten_params, grad_segment
+from ..agents.lstm_dqn_agent import DQN, ETA_MIN, HIDDEN, T_MAX, epsilon_at
+from ..agents.rf_agent import cosine_lr
+from .ppo_trainer import episode_bound
+from .schedule import WinSchedule, curriculum_rule
+
+FORMAT = "mazerl.VectorRecurrentDQNTrainer/1"
+EVAL_KEY = 0x4556414C
+ROW, STASH, PARAMS = 8, 192, 5252
+U64 = 0xFFFFFFFFFFFFFFFF
+
+
+def param_ptrs(net):
+    """The host array of six device pointers the mz_drqn_* entry points take (state_dict order)."""
+    ps = list(net.parameters())
+    assert [tuple(p.shape) for p in ps] == [(128, 6), (128, 32), (128,), (128,), (4, 32), (4,)]
+    return (C.c_void_p * 6)(*[p.data_ptr() for p in ps])
+
+
+class VectorRecurrentDQNTrainer:
+    def __init__(self, env, device, lr=1e-3, starting_epsilon=0.9, final_epsilon=0.05,
+                 epsilon_decay=1000.0, discount_factor=0.99, batch_size=32, memory_size=20000,
+                 target_update_frequency=10, explore_actions=4, train_every=1, seed=0, bank=True,
+                 curriculum=False, growth=None, algorithm="r-prim", bank_candidates=1):
+        self.env = env
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("VectorRecurrentDQNTrainer runs on the GPU (libmazerl HIP kernels)")
+        if batch_size < 1 or memory_size < batch_size or train_every < 1 or \
+                target_update_frequency < 1 or explore_actions not in (1, 2, 3, 4):
+            raise ValueError("batch_size >= 1, memory_size >= batch_size, train_every >= 1, "
+                             "target_update_frequency >= 1, explore_actions in 1..4")
+        rule = curriculum_rule(curriculum)
+        self.curriculum = rule
+        self.schedule = (WinSchedule(env, rule, growth, None, algorithm)
+                         if (rule is not None or growth is not None) else None)
+        self.stopped_at = None
+        if bank:
+            dims = getattr(env, "dims_in_use", None)
+            if self.schedule is not None and self.schedule.growth is not None:
+                dims = self.schedule.sizes()
+            env.enable_bank(algorithms=[0, 1, 2] if rule else None, dims=dims,
+                            candidates=bank_candidates)
+        torch.manual_seed(seed)
+        self.source_net = DQN(6, 4, HIDDEN, self.device)
+        self.target_net = DQN(6, 4, HIDDEN, self.device)
+        flatten_params(self.target_net)
+        flatten_grads(self.source_net)
+        copy_flat(self.target_net, self.source_net)
+        for p in self.source_net.parameters():
+            p.grad = grad_segment(p)
+        self.opt = FlatAdamW(self.source_net, lr=lr, clamp=1.0)
+        self._ps, self._pt = param_ptrs(self.source_net), param_ptrs(self.target_net)
+        self._pg = (C.c_void_p * 6)(*[p.grad.data_ptr() for p in self.source_net.parameters()])
+        self.lr, self.gamma = float(lr), float(discount_factor)
+        self.starting_epsilon, self.final_epsilon = float(starting_epsilon), float(final_epsilon)
+        self.epsilon_decay = float(epsilon_decay)
+        self.batch_size, self.capacity = int(batch_size), int(memory_size)
+        self.target_update_frequency = int(target_update_frequency)
+        self.explore_actions, self.train_every = int(explore_actions), int(train_every)
+        self.seed = int(seed)
+        self.steps_done = 0   # the eps clock
+        self.counter = 0      # vector steps (the exploration draws' counter)
+        self.updates = 0
+        self.filled = 0       # the host's lower bound of the ring's count
+        B, E = env.num_envs, self.batch_size
+        self.L = L = episode_bound(env.max_dim, env.toroidal)
+        kw = dict(device=self.device)
+        i32, i64, f32 = torch.int32, torch.int64, torch.float32
+        self.h = torch.zeros(HIDDEN, B, dtype=f32, **kw)
+        self.c = torch.zeros(HIDDEN, B, dtype=f32, **kw)
+        self.t = torch.zeros(B, dtype=i32, **kw)
+        self.act_out = torch.zeros(B, dtype=i32, **kw)
+        self.rec_x = torch.zeros(B, L + 1, 6, dtype=f32, **kw)
+        self.rec_a = torch.zeros(B, L, dtype=i32, **kw)
+        self.rec_r = torch.zeros(B, L, dtype=torch.float64, **kw)
+        self.r64 = torch.zeros(B, dtype=torch.float64, **kw)
+        self.fin_id = torch.zeros(B, dtype=i32, **kw)
+        self.fin_off = torch.zeros(B, dtype=i64, **kw)
+        self.fin_len = torch.zeros(B, dtype=i32, **kw)
+        self.fin_count = torch.zeros(1, dtype=i32, **kw)
+        self.pool = torch.zeros(2, dtype=i64, **kw)  # mz_ppo_scan's row counters (unused here)
+        # episodes, wins, dropped 1-step episodes, record-buffer overflows
+        self.stats = torch.zeros(4, dtype=i64, **kw)
+        # the replay memory: fixed-stride slots of L + 1 rows of 32 B
+        self.mem = torch.zeros(self.capacity, L + 1, ROW, dtype=i32, **kw)
+        self.mem_len = torch.zeros(self.capacity, dtype=i32, **kw)
+        self.mem_term = torch.zeros(self.capacity, dtype=i32, **kw)
+        self.ring = torch.zeros(2, dtype=i64, **kw)  # head, count
+        # an update's directory and row buffers
+        rows = E * (L + 1)
+        self.d_slot = torch.zeros(E, dtype=i32, **kw)
+        self.d_len = torch.zeros(E, dtype=i32, **kw)
+        self.d_off = torch.zeros(E, dtype=i64, **kw)
+        self.d_tot = torch.zeros(2, dtype=i64, **kw)
+        self.qmax = torch.zeros(rows, dtype=f32, **kw)
+        self.stash = torch.zeros(rows, STASH, dtype=f32, **kw)
+        self.qa = torch.zeros(rows, dtype=f32, **kw)
+        self.y = torch.zeros(rows, dtype=f32, **kw)
+        self.d = torch.zeros(rows, dtype=f32, **kw)
+        self.ep_loss = torch.zeros(E, dtype=torch.float64, **kw)
+        self.gpart = torch.zeros(E, PARAMS, dtype=f32, **kw)
+        self.loss = torch.zeros(1, dtype=f32, **kw)
+        self.last_lr = None
+        self.lib = N.load()
+
+    supports_bits = True  # evaluate(): the f32 windows are never read
+
+    @property
+    def episodes(self):
+        return int(self.stats[0])
+
+    @property
+    def wins(self):
+        return int(self.stats[1])
+
+    @property
+    def algo(self):
+        return None if self.schedule is None else self.schedule.maze_algo
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def epsilon(self):
+        return epsilon_at(self.steps_done, self.starting_epsilon, self.final_epsilon,
+                          self.epsilon_decay)
+
+    def update_steps_done(self):
+        self.steps_done = self.steps_done // 2
+
+    def _act(self):
+        env = self.env
+        eps = min(max(self.epsilon(), 0.0), 1.0)
+        self.steps_done += 1
+        N.check(self.lib.mz_drqn_act(
+            self._ps, HIDDEN, env.obs6.data_ptr(), env.num_envs, self.L, eps, self.explore_actions,
+            self.seed & U64, self.counter & U64, self.t.data_ptr(), self.h.data_ptr(),
+            self.c.data_ptr(), self.rec_x.data_ptr(), self.rec_a.data_ptr(),
+            self.act_out.data_ptr(), None, self._stream()))
+        self.counter += 1
+
+    def _scan_store(self):
+        env, B, L, st = self.env, self.env.num_envs, self.L, self._stream()
+        self.r64.copy_(env.reward)
+        N.check(self.lib.mz_ppo_scan(
+            self.r64.data_ptr(), env.terminated.data_ptr(), env.truncated.data_ptr(), B, L,
+            self.t.data_ptr(), self.rec_r.data_ptr(), self.fin_id.data_ptr(),
+            self.fin_off.data_ptr(), self.fin_len.data_ptr(), self.fin_count.data_ptr(),
+            self.pool[0:].data_ptr(), self.pool[1:].data_ptr(), self.stats.data_ptr(), st))
+        N.check(self.lib.mz_drqn_store(
+            env.obs6.data_ptr(), env.terminated.data_ptr(), B, L, self.fin_id.data_ptr(),
+            self.fin_len.data_ptr(), self.fin_count.data_ptr(), self.rec_x.data_ptr(),
+            self.rec_a.data_ptr(), self.rec_r.data_ptr(), self.capacity, self.mem.data_ptr(),
+            self.mem_len.data_ptr(), self.mem_term.data_ptr(), self.ring.data_ptr(), st))
+
+    def sample(self):
+        """E distinct slots and the directory (d_slot, d_len, d_off, d_tot), keyed by the update
+        count."""
+        N.check(self.lib.mz_drqn_sample(
+            self.seed & U64, self.updates & U64, self.batch_size, self.L, self.capacity,
+            self.filled, self.ring.data_ptr(), self.mem_len.data_ptr(), self.d_slot.data_ptr(),
+            self.d_len.data_ptr(), self.d_off.data_ptr(), self.d_tot.data_ptr(), self._stream()))
+
+    def update(self, lr):
+        """One optimizer step on the directory's episodes at learning rate `lr`; the loss stays on
+        the device (self.loss)."""
+        E, L, st = self.batch_size, self.L, self._stream()
+        dirs = (self.d_slot.data_ptr(), self.d_len.data_ptr(), self.d_off.data_ptr(),
+                self.d_tot.data_ptr())
+        self.opt.param_groups[0]["lr"].fill_(float(lr))
+        N.check(self.lib.mz_drqn_seq_forward(
+            self._pt, HIDDEN, 1, E, L, self.capacity, self.gamma, self.mem.data_ptr(),
+            self.mem_term.data_ptr(), *dirs, self.qmax.data_ptr(), None, None, None, None, None,
+            st))
+        N.check(self.lib.mz_drqn_seq_forward(
+            self._ps, HIDDEN, 0, E, L, self.capacity, self.gamma, self.mem.data_ptr(),
+            self.mem_term.data_ptr(), *dirs, self.qmax.data_ptr(), self.stash.data_ptr(),
+            self.qa.data_ptr(), self.y.data_ptr(), self.d.data_ptr(), self.ep_loss.data_ptr(), st))
+        N.check(self.lib.mz_drqn_seq_backward(
+            self._ps, HIDDEN, E, L, self.capacity, self.mem.data_ptr(), *dirs,
+            self.stash.data_ptr(), self.d.data_ptr(), self.ep_loss.data_ptr(),
+            self.gpart.data_ptr(), self._pg, self.loss.data_ptr(), st))
+        self.opt.step()
+
+    def _update(self):
+        if self.updates % 256 == 0 and int(self.stats[3]):  # (one look every 256 updates)
+            raise RuntimeError(f"recurrent DQN episode records overflowed L = {self.L} steps "
+                               "(mz_ppo_scan stats[3])")
+        self.last_lr = cosine_lr(self.updates, self.lr, T_MAX, ETA_MIN)
+        self.sample()
+        self.update(self.last_lr)
+        self.updates += 1
+        if self.updates % self.target_update_frequency == 0:
+            copy_flat(self.target_net, self.source_net)
+
+    def vector_step(self):
+        env = self.env
+        self._act()
+        env.step(self.act_out)
+        self._scan_store()
+        sch = self.schedule
+        if sch is not None:
+            won = env.terminated.bool()
+            sch.before_reset(won)
+        env.reset_done(regen_won=True)
+        if sch is not None:
+            sch.after_reset(won)
+        if self.filled < self.batch_size:  # (only until the first batch exists: one sync a step)
+            self.filled = int(self.ring[1])
+        if self.filled >= self.batch_size and self.counter % self.train_every == 0:
+            self._update()
+
+    def train(self, vector_steps, log_every=0, log=print):
+        t0 = time.perf_counter()
+        sch = self.schedule
+        for k in range(vector_steps):
+            self.vector_step()
+            if sch is not None and sch.growth is not None and (k + 1) % 32 == 0 and sch.all_retired():
+                self.stopped_at = k + 1
+                break
+            if log_every and (k + 1) % log_every == 0 and log:
+                log(dict(step=k + 1, episodes=self.episodes, wins=self.wins, updates=self.updates,
+                         loss=float(self.loss), seconds=round(time.perf_counter() - t0, 2)))
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    # ---- evaluation (vector_trainer.evaluate) ---------------------------------------------------
+    def evaluator(self):
+        """A learner for vector_trainer.evaluate: greedy actions from a per-row (h, c) that starts
+        at zero (evaluate plays one episode per row) and advances once per greedy() call."""
+        return _Evaluator(self)
+
+    def greedy(self, obs6, window=None, bits=None):
+        """The greedy action of every row, carrying (h, c) per row between calls; the state is
+        zeroed by reset_greedy() or when the number of rows changes. For an evaluation of its own
+        state use evaluator()."""
+        ev = getattr(self, "_eval", None)
+        if ev is None:
+            ev = self._eval = _Evaluator(self)
+        return ev.greedy(obs6, window, bits)
+
+    def reset_greedy(self):
+        if getattr(self, "_eval", None) is not None:
+            self._eval.reset()
+
+    # ---- checkpoint / resume (mazerl/checkpoint.py) -------------------------------------------
+    _REC = ("rec_x", "rec_a", "rec_r")
+
+    def _live(self, L):
+        return torch.arange(L, device=self.device)[None, :] < self.t[:, None].long()
+
+    def state_dict(self):
+        """The run between two vector steps: both nets, the optimizer, (h, c), the in-flight
+        records (each instance's first t[i] rows), the filled replay slots with head and count,
+        the counters and the env."""
+        torch.cuda.synchronize(self.device)
+        o = self.opt
+        n = int(self.ring[1])
+        live = self._live(self.L)
+        return {"format": FORMAT, "L": self.L, "capacity": self.capacity,
+                "schedule": None if self.schedule is None else self.schedule.state_dict(),
+                "source": {k: v.clone() for k, v in self.source_net.state_dict().items()},
+                "target": {k: v.clone() for k, v in self.target_net.state_dict().items()},
+                "opt": {"exp_avg": o.exp_avg.clone(), "exp_avg_sq": o.exp_avg_sq.clone(),
+                        "step": o._step_buf.clone(), "lr": o.param_groups[0]["lr"].clone()},
+                "h": self.h.clone(), "c": self.c.clone(), "t": self.t.clone(),
+                "records": {"rec_x": self.rec_x[:, :self.L][live], "rec_a": self.rec_a[live],
+                            "rec_r": self.rec_r[live]},
+                "ring": self.ring.clone(), "mem": self.mem[:n].clone(),
+                "mem_len": self.mem_len[:n].clone(), "mem_term": self.mem_term[:n].clone(),
+                "stats": self.stats.clone(), "pool": self.pool.clone(), "loss": self.loss.clone(),
+                "counters": {k: getattr(self, k) for k in ("seed", "steps_done", "counter",
+                                                           "updates", "filled")},
+                "env": self.env.state_dict()}
+
+    def load_state_dict(self, sd):
+        if sd.get("format") != FORMAT or sd["L"] != self.L or sd["capacity"] != self.capacity:
+            raise ValueError("not a VectorRecurrentDQNTrainer state_dict of this shape")
+        if (sd["schedule"] is None) != (self.schedule is None):
+            raise ValueError("curriculum / growth differ from the saved trainer's")
+        self.env.load_state_dict(sd["env"])
+        if self.schedule is not None:
+            self.schedule.load_state_dict(sd["schedule"])
+        with torch.no_grad():
+            self.source_net.load_state_dict(sd["source"])
+            self.target_net.load_state_dict(sd["target"])
+        o = self.opt
+        o.exp_avg.copy_(sd["opt"]["exp_avg"])
+        o.exp_avg_sq.copy_(sd["opt"]["exp_avg_sq"])
+        o._step_buf.copy_(sd["opt"]["step"])
+        o.param_groups[0]["lr"].copy_(sd["opt"]["lr"])
+        for k in ("h", "c", "t", "ring", "stats", "pool", "loss"):
+            getattr(self, k).copy_(sd[k])
+        live = self._live(self.L)
+        self.rec_x[:, :self.L][live] = sd["records"]["rec_x"].to(self.device)
+        self.rec_a[live] = sd["records"]["rec_a"].to(self.device)
+        self.rec_r[live] = sd["records"]["rec_r"].to(self.device)
+        n = sd["mem"].shape[0]
+        self.mem[:n].copy_(sd["mem"])
+        self.mem_len[:n].copy_(sd["mem_len"])
+        self.mem_term[:n].copy_(sd["mem_term"])
+        for k, v in sd["counters"].items():
+            setattr(self, k, int(v))
+
+
+def evaluate_plain(learner, num_mazes, dim, algorithm="r-prim", seed=0x7E57, toroidal=False,
+                   device=None):
+    """vector_trainer.evaluate on plain (enrich=False) mazes, which exist from 9x9 up (an Enrich
+    env needs room for the 15x15 window): the fraction of `num_mazes` fresh mazes solved greedily
+    in one episode. `learner`: a trainer's evaluator(). Returns (rate, vector steps)."""
+    from ..vector_env import VectorMazeEnv
+    env = VectorMazeEnv(num_mazes, dim, toroidal=toroidal, enrich=False, device=device,
+                        algorithm=algorithm, seed=seed, pos=False, done_list=False)
+    finished = torch.zeros(num_mazes, dtype=torch.bool, device=env.device)
+    won = torch.zeros(num_mazes, dtype=torch.bool, device=env.device)
+    limit = episode_bound(dim, toroidal) + 1
+    k = 0
+    while k < limit:
+        acts = learner.greedy(env.obs6, None, None).to(torch.int32)
+        env.step(torch.where(finished, torch.full_like(acts, -1), acts))
+        term = env.terminated.bool()
+        won |= term & ~finished
+        finished |= term | env.truncated.bool()
+        k += 1
+        if k % 32 == 0 and bool(finished.all()):
+            break
+    rate = float(won.float().mean())
+    env.close()
+    return rate, k
+
+
+class _Evaluator:
+    supports_bits = True
+
+    def __init__(self, trainer):
+        self.trainer = trainer
+        self.n = 0
+        self.h = self.c = self.t = None
+        self.calls = 0
+
+    def reset(self):
+        if self.h is not None:
+            self.h.zero_()
+            self.c.zero_()
+            self.t.zero_()
+
+    def greedy(self, obs6, window=None, bits=None):
+        tr = self.trainer
+        n = obs6.shape[0]
+        if n != self.n:
+            kw = dict(device=obs6.device)
+            self.h = torch.zeros(HIDDEN, n, dtype=torch.float32, **kw)
+            self.c = torch.zeros(HIDDEN, n, dtype=torch.float32, **kw)
+            self.t = torch.zeros(n, dtype=torch.int32, **kw)
+            self.n = n
+        obs6 = obs6.contiguous()
+        out = torch.empty(n, dtype=torch.int32, device=obs6.device)
+        N.check(tr.lib.mz_drqn_act(
+            tr._ps, HIDDEN, obs6.data_ptr(), n, 0, 0.0, tr.explore_actions,
+            (tr.seed ^ EVAL_KEY) & U64, self.calls & U64, self.t.data_ptr(), self.h.data_ptr(),
+            self.c.data_ptr(), None, None, out.data_ptr(), None,
+            torch.cuda.current_stream(obs6.device).cuda_stream))
+        self.calls += 1
+        self.t.fill_(1)  # zero state was the first call's; from now on the carried one
+        return out.long()
