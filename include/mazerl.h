@@ -990,6 +990,52 @@ int mz_dqtab_hash_lookup(const int32_t* keys_dev, const double* vals_dev, int64_
                          const int64_t* query_keys_dev, int32_t m, double* rows_out_dev,
                          int32_t* slots_out_dev, void* stream);
 
+/* ---- Explored-maze archive (mz_archive.hip) --------------------------------------------------
+ * Replaces `env.mazes`, the list the reference env appends every maze it trains on to (the first
+ * one and each update_maze() replacement: simple_maze_env.py:34,91,
+ * simple_variable_maze_env.py:39,106), and update_visited_maze(), which puts one back for
+ * test(n, new=False) (off_policy_trainer.py:84-119). The CALLER owns all archive memory (device
+ * arrays); the handle keeps no pointer to it, so an archive outlives its handle, can be saved and
+ * can be loaded into another handle.
+ *
+ * One entry = one maze of size N <= P (P = the archive's pitch, a handle's max_dim):
+ *   bits  int32 [W], W = ceil(P * P / 32) (mz_archive_words): bit (r * N + c) & 31 of word
+ *         (r * N + c) >> 5 is 1 iff cell (r, c) is open (grid value 1 or 2) — row-major with the
+ *         entry's own N; the bits at index >= N * N and all remaining words are 0;
+ *   meta  int32 [2]: the instance's meta words, N | N << 8 | start_r << 16 | start_c << 24 and
+ *         goal_r | goal_c << 8 | max_steps << 16 (toroidal handles: the cropped coordinates, as
+ *         held);
+ *   algo  uint8: the instance's algorithm id. */
+
+/* W for pitch max_dim (5 <= max_dim <= MZ_MAX_DIM). Runs on the host (as mz_qtab_states). */
+int mz_archive_words(int32_t max_dim, int32_t* words);
+
+/* env.mazes.append(maze) (simple_maze_env.py:34,91) for every instance e with flags_dev[e] != 0
+ * (NULL: all): its current maze goes to slot count_dev[e] % slots of its ring — bits_dev
+ * [B][slots][words], meta_dev [B][slots][2], algo_dev [B][slots] — then count_dev[e] += 1 (count_dev
+ * [B], non-negative). One writer per instance, no atomics; the handle's state is only read.
+ * words must equal mz_archive_words(the handle's max_dim) and slots >= 1 (else MZ_EINVAL). One
+ * launch, asynchronous. */
+int mz_archive_push(mz_handle* h, const uint8_t* flags_dev, int32_t slots, int32_t words,
+                    int32_t* bits_dev, int32_t* meta_dev, uint8_t* algo_dev, int32_t* count_dev,
+                    void* stream);
+
+/* update_visited_maze() (off_policy_trainer.py:96-116) without the host: target j = instance
+ * env_ids_dev[j] (NULL: j; the listed ids must differ) becomes the maze of linear entry
+ * slot_dev[j] of bits_dev [entries][words], meta_dev [entries][2], algo_dev [entries] — the caller
+ * keeps 0 <= slot_dev[j] < entries; a negative slot leaves the instance alone. Built as
+ * mz_load_mazes builds an imported maze, bit for bit (distance field, cell words, plane strips,
+ * max_steps, meta, the instance reset, its last-terminated flag cleared), with the entry's
+ * algorithm id, and with targets of different sizes in one launch. One launch, asynchronous, no
+ * host copy. Every entry is validated on the device before anything is stored: N odd,
+ * 5 <= N <= the handle's max_dim (>= 15 on an euclidean enrich handle), N * N bits inside `words`
+ * (the SOURCE arrays' row length: an archive of another pitch is legal as long as N fits), start
+ * and goal inside N with both bits set, algorithm id 0..2, instance id inside the handle. A bad
+ * entry leaves its instance untouched and adds 1 to *errors_dev (int32, zeroed by the caller). */
+int mz_archive_load(mz_handle* h, const int32_t* env_ids_dev, int32_t n, const int32_t* slot_dev,
+                    int32_t words, const int32_t* bits_dev, const int32_t* meta_dev,
+                    const uint8_t* algo_dev, int32_t* errors_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

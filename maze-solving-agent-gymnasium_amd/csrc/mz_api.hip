@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/mazerl.h"
+#include "mz_archive.h"
 #include "mz_common.h"
 #include "mz_learner.h"
 #include "mz_mcclendon.h"
@@ -106,17 +107,7 @@ int fail(int code, const char* fmt, ...) {
     if (e_ != hipSuccess) return fail(MZ_EHIP, "%s: %s", #x, hipGetErrorString(e_));   \
   } while (0)
 
-struct DeviceGuard {  // run a call on the handle's device, restore the caller's afterwards
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceGuard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
+using DeviceGuard = MzDeviceGuard;  // (mz_archive.h: shared with mz_archive.hip)
 
 // Entry points that take device pointers and a stream but no handle run on the stream's device
 // (the caller's current device for the null stream), restoring the caller's device afterwards.
@@ -305,6 +296,11 @@ int bestof_run(mz_handle* h, MzCandStore& cs, const MzDev& dst, const int32_t* i
 }
 
 }  // namespace
+
+// mz_archive.h: the handle as entry points defined outside this file see it
+const MzDev& mz_handle_dev(const mz_handle* h) { return h->d; }
+int mz_handle_device(const mz_handle* h) { return h->cfg.device; }
+int mz_fail_msg(int code, const char* msg) { return fail(code, "%s", msg); }
 
 extern "C" {
 

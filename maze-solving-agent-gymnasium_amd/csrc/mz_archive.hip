@@ -1,0 +1,177 @@
+// mz_archive.hip — the explored-maze archive: keep the mazes an instance trained on, on the
+// device, and put one back.
+//
+// Reference: the env appends every maze it trains on to `env.mazes` — the first one and each
+// update_maze() replacement (simple_maze_env.py:34,91; simple_variable_maze_env.py:39,106) — and
+// test(n, new=False) replays them one by one through update_visited_maze()
+// (off_policy_trainer.py:84-119). Here a win overwrites the instance's tables, so the maze is
+// kept as what it takes to rebuild them: its open cells as a bit field, the two meta words and
+// the algorithm id (2 KB at 127 x 127 where the built tables take ~70 KB).
+//
+// The caller owns the archive memory (torch tensors): per instance a ring of `slots` entries,
+//   bits [B][slots][W] int32, W = ceil(P * P / 32): bit (r N + c) & 31 of word (r N + c) >> 5 is
+//                      1 iff cell (r, c) is open — row-major with the entry's own N, zero past N N;
+//   meta [B][slots][2] the instance's meta0 / meta1 words (mz_common.h);
+//   algo [B][slots]    its algorithm id;
+//   count [B]          pushes so far: the next push goes to slot count % slots.
+//
+//   k_archive_push  one wave per instance: 64 cells per pass, their open bits (MZ_CELL_OPEN of
+//                   the cell words) gathered by a wave ballot — two words per pass, lane k keeps
+//                   the ballot of pass k — and stored 8 B per lane, 512 B per wave instruction.
+//                   One writer per instance, no atomics; the handle's state is only read.
+//   k_archive_load  one wave per target: validates the entry (nothing is stored for a bad one:
+//                   it is counted in *errors), unpacks the bits into the build's LDS grid and
+//                   runs the import branch of mz_build_one with the entry's own N — the launch of
+//                   mz_load_mazes without its host copies and synchronisation, and with targets
+//                   of different sizes in one launch.
+#include "mz_archive.h"
+#include "mz_build.inc.h"
+
+#define WAVE 64
+#define PUSH_WAVES 4  // instances (waves) per k_archive_push workgroup
+
+namespace {
+
+__global__ __launch_bounds__(WAVE * PUSH_WAVES) void k_archive_push(
+    MzDev d, const uint8_t* __restrict__ flags, int slots, int words, int32_t* __restrict__ bits,
+    int32_t* __restrict__ meta, uint8_t* __restrict__ algo, int32_t* __restrict__ count) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int e = blockIdx.x * PUSH_WAVES + (threadIdx.x >> 6);  // wave-uniform
+  if (e >= d.B || (flags && !flags[e])) return;
+  const uint32_t m0 = d.meta0[e], m1 = d.meta1[e];
+  const int N = min((int)(m0 & 0xFF), d.P);
+  const uint32_t cnt = (uint32_t)count[e];
+  const size_t ent = (size_t)e * slots + cnt % (uint32_t)slots;
+  const uint32_t* cells = d.cells + (size_t)e * d.P * d.P;
+  uint2* out = reinterpret_cast<uint2*>(bits + ent * words);  // (8-B aligned only for even words)
+  int32_t* outw = bits + ent * words;
+  const bool wide = ((reinterpret_cast<uintptr_t>(outw) & 7u) == 0);
+  const int passes = (words + 1) / 2;  // covers every word: the ones past N * N are stored as 0
+  unsigned long long keep = 0ull;
+  for (int p = 0; p < passes; ++p) {
+    const int i = p * WAVE + lane;
+    bool open = false;
+    if (i < N * N) {
+      const int r = i / N, c = i - r * N;
+      open = (cells[r * d.P + c] & MZ_CELL_OPEN) != 0u;
+    }
+    const unsigned long long b = __ballot(open);
+    if (lane == (p & (WAVE - 1))) keep = b;
+    if ((p & (WAVE - 1)) == WAVE - 1 || p == passes - 1) {  // flush: lane k holds pass p0 + k
+      const int p0 = p & ~(WAVE - 1), q = p0 + lane;
+      if (q <= p) {
+        const uint32_t lo = (uint32_t)keep, hi = (uint32_t)(keep >> 32);
+        if (wide && 2 * q + 1 < words) {
+          out[q] = make_uint2(lo, hi);
+        } else {
+          outw[2 * q] = (int32_t)lo;
+          if (2 * q + 1 < words) outw[2 * q + 1] = (int32_t)hi;
+        }
+      }
+      keep = 0ull;
+    }
+  }
+  if (lane == 0) {
+    meta[2 * ent] = (int32_t)m0;
+    meta[2 * ent + 1] = (int32_t)m1;
+    algo[ent] = d.algo[e];
+    count[e] = (int32_t)(cnt + 1u);
+  }
+}
+
+__global__ __launch_bounds__(WAVE) void k_archive_load(
+    MzDev d, const int32_t* __restrict__ env_ids, int n, const int32_t* __restrict__ slot,
+    int words, const int32_t* __restrict__ bits, const int32_t* __restrict__ meta,
+    const uint8_t* __restrict__ algo, int32_t* errors) {
+  extern __shared__ __align__(16) uint8_t lds[];
+  const int lane = threadIdx.x;
+  const MzBuildLds L = mz_build_lds(lds, d.P);
+  for (int j = blockIdx.x; j < n; j += gridDim.x) {  // (everything below is uniform per wave)
+    const int s = slot[j];
+    if (s < 0) continue;  // leave this instance alone
+    const int e = env_ids ? env_ids[j] : j;
+    const uint32_t m0 = (uint32_t)meta[2 * (size_t)s], m1 = (uint32_t)meta[2 * (size_t)s + 1];
+    const int N = (int)(m0 & 0xFF), W = (int)((m0 >> 8) & 0xFF);
+    const int sr = (int)((m0 >> 16) & 0xFF), sc = (int)(m0 >> 24);
+    const int gr = (int)(m1 & 0xFF), gc = (int)((m1 >> 8) & 0xFF);
+    const int a = (int)algo[s];
+    const uint32_t* b = reinterpret_cast<const uint32_t*>(bits) + (size_t)s * words;
+    // the memory contract: every index the build forms below is bounded by these checks, before
+    // any store — N fits the destination's pitch and the source row, start and goal lie inside N
+    bool ok = e >= 0 && e < d.B && (N & 1) && N >= 5 && N <= d.P && W == N &&
+              mz_archive_entry_words(N) <= words && sr < N && sc < N && gr < N && gc < N &&
+              a >= 0 && a <= 2 && !(d.enrich && !d.toroidal && N < 15);
+    if (ok) {
+      const int ps = sr * N + sc, pg = gr * N + gc;
+      ok = ((b[ps >> 5] >> (ps & 31)) & 1u) && ((b[pg >> 5] >> (pg & 31)) & 1u);
+    }
+    if (!ok) {
+      if (lane == 0) atomicAdd(errors, 1);
+      continue;
+    }
+    for (int i = lane; i < N * N; i += WAVE) L.g[i] = (uint8_t)((b[i >> 5] >> (i & 31)) & 1u);
+    __syncthreads();
+    if (lane == 0) {
+      L.g[gr * N + gc] = 2;
+      d.algo[e] = (uint8_t)a;
+    }
+    __syncthreads();
+    // the import branch: its grid source is the LDS grid itself (the copy is then the identity)
+    mz_build_one(d, e, d.toroidal, false, 0, 0, N, L.g, sr, sc, gr, gc, lds);
+    __syncthreads();
+  }
+}
+
+int hip_fail(hipError_t e) { return mz_fail_msg(MZ_EHIP, hipGetErrorString(e)); }
+
+}  // namespace
+
+extern "C" {
+
+int mz_archive_words(int32_t max_dim, int32_t* words) {
+  if (!words) return mz_fail_msg(MZ_EINVAL, "null argument");
+  if (max_dim < 5 || max_dim > MZ_MAX_DIM) return mz_fail_msg(MZ_EINVAL, "max_dim outside [5, MZ_MAX_DIM]");
+  *words = mz_archive_entry_words(max_dim);
+  return MZ_OK;
+}
+
+int mz_archive_push(mz_handle* h, const uint8_t* flags_dev, int32_t slots, int32_t words,
+                    int32_t* bits_dev, int32_t* meta_dev, uint8_t* algo_dev, int32_t* count_dev,
+                    void* stream) {
+  if (!h || !bits_dev || !meta_dev || !algo_dev || !count_dev)
+    return mz_fail_msg(MZ_EINVAL, "null argument");
+  const MzDev& d = mz_handle_dev(h);
+  if (slots < 1) return mz_fail_msg(MZ_EINVAL, "slots must be >= 1");
+  if (words != mz_archive_entry_words(d.P))
+    return mz_fail_msg(MZ_EINVAL, "words must equal mz_archive_words(the handle's max_dim)");
+  MzDeviceGuard g(mz_handle_device(h));
+  hipLaunchKernelGGL(k_archive_push, dim3((d.B + PUSH_WAVES - 1) / PUSH_WAVES),
+                     dim3(WAVE * PUSH_WAVES), 0, static_cast<hipStream_t>(stream), d, flags_dev,
+                     slots, words, bits_dev, meta_dev, algo_dev, count_dev);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? MZ_OK : hip_fail(e);
+}
+
+int mz_archive_load(mz_handle* h, const int32_t* env_ids_dev, int32_t n, const int32_t* slot_dev,
+                    int32_t words, const int32_t* bits_dev, const int32_t* meta_dev,
+                    const uint8_t* algo_dev, int32_t* errors_dev, void* stream) {
+  if (!h || !slot_dev || !bits_dev || !meta_dev || !algo_dev || !errors_dev)
+    return mz_fail_msg(MZ_EINVAL, "null argument");
+  const MzDev& d = mz_handle_dev(h);
+  if (n < 0 || (!env_ids_dev && n > d.B)) return mz_fail_msg(MZ_EINVAL, "n out of range");
+  if (words < 1) return mz_fail_msg(MZ_EINVAL, "words must be >= 1");
+  if (n == 0) return MZ_OK;
+  MzDeviceGuard g(mz_handle_device(h));
+  // LDS and grid as mz_launch_build sizes an import (k_build): the square-grid build region of
+  // the destination's pitch, one wave per target, persistent over the list
+  const size_t lds = mz_import_lds(d.P, d.toroidal != 0);
+  const hipError_t ae = mz_build_lds_attr(reinterpret_cast<const void*>(k_archive_load), lds);
+  if (ae != hipSuccess) return hip_fail(ae);
+  const int grid = mz_build_launch_grid(n, lds);
+  hipLaunchKernelGGL(k_archive_load, dim3(grid), dim3(WAVE), lds, static_cast<hipStream_t>(stream),
+                     d, env_ids_dev, n, slot_dev, words, bits_dev, meta_dev, algo_dev, errors_dev);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? MZ_OK : hip_fail(e);
+}
+
+}  // extern "C"

@@ -1383,6 +1383,11 @@ int mz_build_grid(int n, size_t lds) {
 // ------------------------------------------------------------------------------------------
 // launchers (called by mz_api.hip)
 size_t mz_build_lds_size(int P) { return mz_build_lds_bytes(P); }
+// an importing build's launch geometry for kernels of other files (mz_archive.h): k_build's LDS,
+// its LDS attribute and its persistent grid, so that they cannot drift from it
+size_t mz_import_lds(int P, bool tor) { return mz_build_lds_launch(P, tor, false, MZ_PY_PHILOX); }
+hipError_t mz_build_lds_attr(const void* fn, size_t bytes) { return mz_lds_attr(fn, bytes); }
+int mz_build_launch_grid(int n, size_t lds) { return mz_build_grid(n, lds); }
 
 hipError_t mz_launch_build(const MzDev& d, const int32_t* env_ids, int32_t n, bool generate,
                            const uint8_t* algo_list, int32_t algo_all, int32_t dim, uint64_t seed,

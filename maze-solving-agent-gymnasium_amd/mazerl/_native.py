@@ -55,7 +55,8 @@ EXPORTS = ["mz_last_error", "mz_device_count", "mz_create", "mz_destroy", "mz_lo
            "mz_qact_workspace_floats", "mz_qtab_states", "mz_qtab_act", "mz_qtab_update",
            "mz_qtab_hash_act", "mz_qtab_hash_update", "mz_qtab_hash_rehash", "mz_qtab_hash_lookup",
            "mz_dqtab_act", "mz_dqtab_update", "mz_dqtab_hash_act", "mz_dqtab_hash_update",
-           "mz_dqtab_hash_rehash", "mz_dqtab_hash_lookup"]
+           "mz_dqtab_hash_rehash", "mz_dqtab_hash_lookup",
+           "mz_archive_words", "mz_archive_push", "mz_archive_load"]
 
 _lib = None
 
@@ -208,6 +209,9 @@ def load(build_if_missing=True):
     L.mz_dqtab_hash_update.argtypes = L.mz_qtab_hash_update.argtypes[:-1] + dq_tail
     L.mz_dqtab_hash_rehash.argtypes = L.mz_qtab_hash_rehash.argtypes
     L.mz_dqtab_hash_lookup.argtypes = L.mz_qtab_hash_lookup.argtypes
+    L.mz_archive_words.argtypes = [C.c_int32, c_i32p]
+    L.mz_archive_push.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
+    L.mz_archive_load.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
     L.mz_host_alloc.argtypes = [C.c_uint64, C.c_int32, C.POINTER(vp), C.POINTER(vp)]
     L.mz_host_free.argtypes = [vp]
     for f in EXPORTS:
