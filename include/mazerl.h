@@ -1036,6 +1036,34 @@ int mz_archive_load(mz_handle* h, const int32_t* env_ids_dev, int32_t n, const i
                     int32_t words, const int32_t* bits_dev, const int32_t* meta_dev,
                     const uint8_t* algo_dev, int32_t* errors_dev, void* stream);
 
+/* The explored-maze pool: ONE list for the whole population, `env.mazes` of a learner that trains
+ * on B envs at once, filled in exploration order — by call, and within a call by instance id.
+ * It keeps the first `capacity` entries and counts the rest. An entry is the archive entry above
+ * plus owner (the instance id) and stamp (the caller's, e.g. the vector step). Read one back with
+ * mz_archive_load: its slots are the entry numbers.
+ *
+ * mz_archive_pool_span: the instances one workgroup of the push covers (a multiple of 64; host
+ * only) — the sizes at which a test crosses workgroups. */
+int mz_archive_pool_span(int32_t* span);
+
+/* Let c = *count_dev before the call and F = the instances with flags_dev[i] != 0 in ascending id
+ * (NULL: all). The r-th instance of F becomes entry c + r of bits_dev [capacity][words], meta_dev
+ * [capacity][2], algo_dev / owner_dev / stamp_dev [capacity] if c + r < capacity, otherwise it is
+ * dropped; nothing at or past `capacity` is written. The new count is min(c + |F|, INT32_MAX):
+ * held = min(count, capacity), dropped = max(count - capacity, 0).
+ * THE COUNT IS A TWO-WORD COUNTER: count_dev (4-byte aligned) points at the word that holds c,
+ * one of an 8-byte-aligned pair of int32. The call only reads it and writes the new count to the
+ * OTHER word of the pair, (uintptr_t)count_dev ^ 4; the caller passes that other word to its
+ * next call. No workgroup then reads a word another one writes: the result does not depend on the
+ * order in which workgroups run, and calls issued back to back on one stream behave as sequential
+ * calls. One launch, asynchronous, no host read. The handle's state is only read.
+ * MZ_EINVAL before any launch: a null handle or array, capacity < 1, words != mz_archive_words(
+ * the handle's max_dim), a misaligned count_dev. */
+int mz_archive_push_pool(mz_handle* h, const uint8_t* flags_dev, int32_t capacity, int32_t words,
+                         int32_t* bits_dev, int32_t* meta_dev, uint8_t* algo_dev,
+                         int32_t* owner_dev, int32_t* stamp_dev, int32_t* count_dev, int32_t stamp,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,9 @@
 //                   the cell words) gathered by a wave ballot — two words per pass, lane k keeps
 //                   the ballot of pass k — and stored 8 B per lane, 512 B per wave instruction.
 //                   One writer per instance, no atomics; the handle's state is only read.
+//   k_archive_push_pool  the same entry, appended to one pool for the whole population in
+//                   instance order (its own comment below): the explored-maze pool of the DQN /
+//                   DDQN populations, mazerl.archive.MazePool.
 //   k_archive_load  one wave per target: validates the entry (nothing is stored for a bad one:
 //                   it is counted in *errors), unpacks the bits into the build's LDS grid and
 //                   runs the import branch of mz_build_one with the entry's own N — the launch of
@@ -29,19 +32,19 @@
 
 #define WAVE 64
 #define PUSH_WAVES 4  // instances (waves) per k_archive_push workgroup
+#define POOL_SPAN 1024  // instances (threads) per k_archive_push_pool workgroup: 16 waves
 
 namespace {
 
-__global__ __launch_bounds__(WAVE * PUSH_WAVES) void k_archive_push(
-    MzDev d, const uint8_t* __restrict__ flags, int slots, int words, int32_t* __restrict__ bits,
-    int32_t* __restrict__ meta, uint8_t* __restrict__ algo, int32_t* __restrict__ count) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int e = blockIdx.x * PUSH_WAVES + (threadIdx.x >> 6);  // wave-uniform
-  if (e >= d.B || (flags && !flags[e])) return;
+// One wave packs instance e into linear entry `ent` of [*, words] / [*, 2] / [*] arrays: the bit
+// field by the ballot passes described above, then the meta words and the algorithm id by lane 0.
+// Every lane of the wave must call it with the same (e, ent).
+__device__ __forceinline__ void archive_pack_entry(const MzDev& d, int e, int lane, int words,
+                                                   size_t ent, int32_t* __restrict__ bits,
+                                                   int32_t* __restrict__ meta,
+                                                   uint8_t* __restrict__ algo) {
   const uint32_t m0 = d.meta0[e], m1 = d.meta1[e];
   const int N = min((int)(m0 & 0xFF), d.P);
-  const uint32_t cnt = (uint32_t)count[e];
-  const size_t ent = (size_t)e * slots + cnt % (uint32_t)slots;
   const uint32_t* cells = d.cells + (size_t)e * d.P * d.P;
   uint2* out = reinterpret_cast<uint2*>(bits + ent * words);  // (8-B aligned only for even words)
   int32_t* outw = bits + ent * words;
@@ -75,7 +78,106 @@ __global__ __launch_bounds__(WAVE * PUSH_WAVES) void k_archive_push(
     meta[2 * ent] = (int32_t)m0;
     meta[2 * ent + 1] = (int32_t)m1;
     algo[ent] = d.algo[e];
-    count[e] = (int32_t)(cnt + 1u);
+  }
+}
+
+__global__ __launch_bounds__(WAVE * PUSH_WAVES) void k_archive_push(
+    MzDev d, const uint8_t* __restrict__ flags, int slots, int words, int32_t* __restrict__ bits,
+    int32_t* __restrict__ meta, uint8_t* __restrict__ algo, int32_t* __restrict__ count) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int e = blockIdx.x * PUSH_WAVES + (threadIdx.x >> 6);  // wave-uniform
+  if (e >= d.B || (flags && !flags[e])) return;
+  const uint32_t cnt = (uint32_t)count[e];
+  const size_t ent = (size_t)e * slots + cnt % (uint32_t)slots;
+  archive_pack_entry(d, e, lane, words, ent, bits, meta, algo);
+  if (lane == 0) count[e] = (int32_t)(cnt + 1u);
+}
+
+// Nonzero bytes of a 32-bit word: bit 7 of each byte of y is set iff that byte of x is not 0.
+__device__ __forceinline__ int nonzero_bytes(uint32_t x) {
+  const uint32_t y = (((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;
+  return __popc(y);
+}
+
+// k_archive_push_pool — one pool for the whole population, filled in instance order.
+//
+// Workgroup b owns the POOL_SPAN instances [b S, (b + 1) S). The slot of a flagged instance is
+// c + (flagged instances with a smaller id), so no workgroup waits for another:
+//   1. the workgroup counts the nonzero flags before its span itself (flags[0 .. b S): 16-B loads
+//      when the array is 16-B aligned, byte loads otherwise; at B = 65,536 at most 63 KB, out of
+//      L2) and reduces the count over its waves through LDS;
+//   2. it ranks its own S flags by a wave ballot, popcount of the lanes below, and a table of the
+//      wave counts in LDS, and writes the local ids of its flagged instances to an LDS list in
+//      rank order;
+//   3. its waves take list items in turn (wave w: items w, w + 16, ...), and pack item j into
+//      entry c + prefix + j when that is below `capacity`: anything at or past it is dropped
+//      before any address is formed. Lane 0 adds owner and stamp.
+// flags == NULL: every instance is flagged, the prefix is b S and nothing is read for it.
+//
+// The count. It is a two-word counter whose parity the caller keeps: `count_in` is read by every
+// workgroup and written by none, the other word of the pair, `count_out`, is written once, by
+// the last workgroup (its prefix + its own flagged instances is |F|), as min(c + |F|, INT32_MAX).
+// Nothing is exchanged between workgroups inside the launch — no atomic, no fence, no ticket —
+// so the result cannot depend on the order in which they run, and two launches back to back on a
+// stream are ordered by the stream alone: the second reads the word the first wrote.
+__global__ __launch_bounds__(POOL_SPAN) void k_archive_push_pool(
+    MzDev d, const uint8_t* __restrict__ flags, int capacity, int words,
+    int32_t* __restrict__ bits, int32_t* __restrict__ meta, uint8_t* __restrict__ algo,
+    int32_t* __restrict__ owner, int32_t* __restrict__ stamps, const int32_t* __restrict__ count_in,
+    int32_t* __restrict__ count_out, int32_t stamp) {
+  __shared__ int s_wave[POOL_SPAN / WAVE];      // per-wave partial sums, then per-wave flag counts
+  __shared__ uint16_t s_list[POOL_SPAN];        // local ids of the flagged instances, in order
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid >> 6;
+  const int base = blockIdx.x * POOL_SPAN;      // (< B <= INT32_MAX)
+  // 1. flagged instances before this span
+  int before = base;
+  if (flags) {
+    int part = 0;
+    if ((reinterpret_cast<uintptr_t>(flags) & 15u) == 0) {  // base is a multiple of 16
+      const uint4* f4 = reinterpret_cast<const uint4*>(flags);
+      for (int i = tid; i < base / 16; i += POOL_SPAN) {
+        const uint4 v = f4[i];
+        part += nonzero_bytes(v.x) + nonzero_bytes(v.y) + nonzero_bytes(v.z) + nonzero_bytes(v.w);
+      }
+    } else {
+      for (int i = tid; i < base; i += POOL_SPAN) part += flags[i] != 0;
+    }
+    for (int o = WAVE / 2; o > 0; o >>= 1) part += __shfl_down(part, o);
+    if (lane == 0) s_wave[wave] = part;
+    __syncthreads();
+    before = 0;
+    for (int w = 0; w < POOL_SPAN / WAVE; ++w) before += s_wave[w];
+    __syncthreads();  // s_wave is reused below
+  }
+  // 2. rank this span's flags
+  const int e = base + tid;
+  const bool mine = e < d.B && (!flags || flags[e] != 0);
+  const unsigned long long vote = __ballot(mine);
+  if (lane == 0) s_wave[wave] = __popcll(vote);
+  __syncthreads();
+  int woff = 0, here = 0;
+  for (int w = 0; w < POOL_SPAN / WAVE; ++w) {
+    const int c = s_wave[w];
+    if (w < wave) woff += c;
+    here += c;
+  }
+  if (mine) s_list[woff + __popcll(vote & ((1ull << lane) - 1ull))] = (uint16_t)tid;
+  __syncthreads();
+  // 3. pack: one wave per list item (everything below is uniform per wave)
+  const long long c0 = (long long)count_in[0] + before;  // entry of this span's first item
+  for (int j = wave; j < here; j += POOL_SPAN / WAVE) {
+    const long long ent = c0 + j;
+    if (ent >= capacity) break;  // dropped, and so is every later item of this wave
+    const int inst = base + (int)s_list[j];
+    archive_pack_entry(d, inst, lane, words, (size_t)ent, bits, meta, algo);
+    if (lane == 0) {
+      owner[ent] = inst;
+      stamps[ent] = stamp;
+    }
+  }
+  if (blockIdx.x == gridDim.x - 1 && tid == 0) {
+    const long long total = (long long)count_in[0] + before + here;
+    count_out[0] = (int32_t)(total > 0x7FFFFFFFll ? 0x7FFFFFFFll : total);
   }
 }
 
@@ -148,6 +250,35 @@ int mz_archive_push(mz_handle* h, const uint8_t* flags_dev, int32_t slots, int32
   hipLaunchKernelGGL(k_archive_push, dim3((d.B + PUSH_WAVES - 1) / PUSH_WAVES),
                      dim3(WAVE * PUSH_WAVES), 0, static_cast<hipStream_t>(stream), d, flags_dev,
                      slots, words, bits_dev, meta_dev, algo_dev, count_dev);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? MZ_OK : hip_fail(e);
+}
+
+int mz_archive_pool_span(int32_t* span) {
+  if (!span) return mz_fail_msg(MZ_EINVAL, "null argument");
+  *span = POOL_SPAN;
+  return MZ_OK;
+}
+
+int mz_archive_push_pool(mz_handle* h, const uint8_t* flags_dev, int32_t capacity, int32_t words,
+                         int32_t* bits_dev, int32_t* meta_dev, uint8_t* algo_dev,
+                         int32_t* owner_dev, int32_t* stamp_dev, int32_t* count_dev, int32_t stamp,
+                         void* stream) {
+  if (!h || !bits_dev || !meta_dev || !algo_dev || !owner_dev || !stamp_dev || !count_dev)
+    return mz_fail_msg(MZ_EINVAL, "null argument");
+  const MzDev& d = mz_handle_dev(h);
+  if (capacity < 1) return mz_fail_msg(MZ_EINVAL, "capacity must be >= 1");
+  if (words != mz_archive_entry_words(d.P))
+    return mz_fail_msg(MZ_EINVAL, "words must equal mz_archive_words(the handle's max_dim)");
+  const uintptr_t cin = reinterpret_cast<uintptr_t>(count_dev);
+  if (cin & 3u) return mz_fail_msg(MZ_EINVAL, "count_dev must be 4-byte aligned");
+  // the two-word counter: the other word of count_dev's 8-byte-aligned pair is written
+  int32_t* cout = reinterpret_cast<int32_t*>(cin ^ 4u);
+  MzDeviceGuard g(mz_handle_device(h));
+  hipLaunchKernelGGL(k_archive_push_pool, dim3((d.B + POOL_SPAN - 1) / POOL_SPAN), dim3(POOL_SPAN),
+                     0, static_cast<hipStream_t>(stream), d, flags_dev, capacity, words, bits_dev,
+                     meta_dev, algo_dev, owner_dev, stamp_dev,
+                     static_cast<const int32_t*>(count_dev), cout, stamp);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? MZ_OK : hip_fail(e);
 }

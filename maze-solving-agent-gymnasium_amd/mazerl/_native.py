@@ -56,7 +56,8 @@ EXPORTS = ["mz_last_error", "mz_device_count", "mz_create", "mz_destroy", "mz_lo
            "mz_qtab_hash_act", "mz_qtab_hash_update", "mz_qtab_hash_rehash", "mz_qtab_hash_lookup",
            "mz_dqtab_act", "mz_dqtab_update", "mz_dqtab_hash_act", "mz_dqtab_hash_update",
            "mz_dqtab_hash_rehash", "mz_dqtab_hash_lookup",
-           "mz_archive_words", "mz_archive_push", "mz_archive_load"]
+           "mz_archive_words", "mz_archive_push", "mz_archive_load",
+           "mz_archive_pool_span", "mz_archive_push_pool"]
 
 _lib = None
 
@@ -212,6 +213,9 @@ def load(build_if_missing=True):
     L.mz_archive_words.argtypes = [C.c_int32, c_i32p]
     L.mz_archive_push.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
     L.mz_archive_load.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
+    L.mz_archive_pool_span.argtypes = [c_i32p]
+    L.mz_archive_push_pool.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp,
+                                       C.c_int32, vp]
     L.mz_host_alloc.argtypes = [C.c_uint64, C.c_int32, C.POINTER(vp), C.POINTER(vp)]
     L.mz_host_free.argtypes = [vp]
     for f in EXPORTS:

@@ -21,6 +21,7 @@ import torch
 from . import _native as N
 
 _FORMAT = "mazerl.MazeArchive/1"
+_POOL_FORMAT = "mazerl.MazePool/1"
 
 
 def archive_words(max_dim):
@@ -67,6 +68,41 @@ def unpack_meta(meta):
     return (m0 & 0xFF, (m0 >> 16) & 0xFF, m0 >> 24, m1 & 0xFF, (m1 >> 8) & 0xFF, m1 >> 16)
 
 
+def _load_entries(store, env, slot, env_ids=None):
+    """MazeArchive.load / MazePool.load: one mz_archive_load launch from `store`'s bits / meta /
+    algo rows (linear entries of `store.words` words) into `env`, refusals counted in
+    store.errors."""
+    s = torch.as_tensor(slot).to(device=store.device, dtype=torch.int32).reshape(-1).contiguous()
+    ids = None
+    if env_ids is not None:
+        ids = torch.as_tensor(env_ids).to(device=store.device, dtype=torch.int32) \
+            .reshape(-1).contiguous()
+        if ids.numel() != s.numel():
+            raise ValueError("one slot per listed instance")
+    elif s.numel() > env.num_envs:
+        raise ValueError("more slots than instances")
+    if env.device != store.device:
+        raise ValueError("the archive and the env live on different devices")
+    N.check(store.lib.mz_archive_load(
+        env._h, None if ids is None else ids.data_ptr(), int(s.numel()), s.data_ptr(),
+        store.words, store.bits.data_ptr(), store.meta.data_ptr(), store.algo.data_ptr(),
+        store.errors.data_ptr(), store._stream()))
+
+
+def _entries_to_mazes(bits, meta):
+    """Host rows of bits [m, W] / meta [m, 2] in the snapshot_mazes / best_of_mazes format."""
+    info = [unpack_meta(m) for m in meta]
+    D = max((x[0] for x in info), default=0)
+    grids = np.zeros((len(info), D, D), np.uint8)
+    sg = np.zeros((len(info), 4), np.int32)
+    sizes = np.zeros(len(info), np.int32)
+    for j, (n, sr, sc, gr, gc, _) in enumerate(info):
+        grids[j, :n, :n] = unpack_grid(bits[j], n, (gr, gc))
+        sg[j] = (sr, sc, gr, gc)
+        sizes[j] = n
+    return grids, sg, sizes
+
+
 class MazeArchive:
     def __init__(self, env, slots):
         """A ring of `slots` entries for each instance of `env` (a VectorMazeEnv): bits int32
@@ -107,21 +143,7 @@ class MazeArchive:
         (entry_slot() gives them; negative: the instance is left alone). One launch, no host
         copy; the instances are reset in the handle — call env.reset() / reset_list() for their
         observations. A refused entry is counted in self.errors."""
-        s = torch.as_tensor(slot).to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
-        ids = None
-        if env_ids is not None:
-            ids = torch.as_tensor(env_ids).to(device=self.device, dtype=torch.int32) \
-                .reshape(-1).contiguous()
-            if ids.numel() != s.numel():
-                raise ValueError("one slot per listed instance")
-        elif s.numel() > env.num_envs:
-            raise ValueError("more slots than instances")
-        if env.device != self.device:
-            raise ValueError("the archive and the env live on different devices")
-        N.check(self.lib.mz_archive_load(
-            env._h, None if ids is None else ids.data_ptr(), int(s.numel()), s.data_ptr(),
-            self.words, self.bits.data_ptr(), self.meta.data_ptr(), self.algo.data_ptr(),
-            self.errors.data_ptr(), self._stream()))
+        _load_entries(self, env, slot, env_ids)
 
     # -------------------------------------------------------------------------------------------
     @property
@@ -170,16 +192,7 @@ class MazeArchive:
         sel = torch.as_tensor(lin, dtype=torch.int64, device=self.device)
         bits = self.bits.view(-1, self.words)[sel].cpu().numpy()
         meta = self.meta.view(-1, 2)[sel].cpu().numpy()
-        info = [unpack_meta(m) for m in meta]
-        D = max((x[0] for x in info), default=0)
-        grids = np.zeros((len(lin), D, D), np.uint8)
-        sg = np.zeros((len(lin), 4), np.int32)
-        sizes = np.zeros(len(lin), np.int32)
-        for j, (n, sr, sc, gr, gc, _) in enumerate(info):
-            grids[j, :n, :n] = unpack_grid(bits[j], n, (gr, gc))
-            sg[j] = (sr, sc, gr, gc)
-            sizes[j] = n
-        return grids, sg, sizes
+        return _entries_to_mazes(bits, meta)
 
     # -------------------------------------------------------------------------------------------
     _TENSORS = ("bits", "meta", "algo", "count", "errors")
@@ -206,6 +219,131 @@ class MazeArchive:
         self.check_state_dict(sd)
         for k in self._TENSORS:
             getattr(self, k).copy_(sd[k])
+
+
+def pool_span():
+    """Instances one workgroup of the pool push covers (mz_archive_pool_span; no GPU)."""
+    s = N.C.c_int32()
+    N.check(N.load().mz_archive_pool_span(N.C.byref(s)))
+    return s.value
+
+
+class MazePool:
+    """`env.mazes` of a learner that trains on B envs at once: ONE list for the whole population,
+    filled in exploration order — record() call by record() call, and within a call by instance
+    id — so that entries 0 .. n-1 are the oldest n mazes the run trained on, what the reference's
+    test(n, new=False) replays. The pool keeps the first `capacity` entries and counts the rest
+    (`dropped`). With one instance it is exactly env.mazes; with B it is deterministic to the bit.
+    An entry is a MazeArchive entry plus owner (the instance id) and stamp (record()'s).
+
+    Size it with the entry: at pitch 81, 206 words + 2 meta + algo + owner + stamp = 841 bytes,
+    0.84 GB per million entries."""
+
+    def __init__(self, env, capacity):
+        """bits int32 [C, W], meta int32 [C, 2], algo uint8 [C], owner int32 [C], stamp int32 [C],
+        the count (entries offered so far) and errors int32 [1] (entries load() refused; never
+        cleared here)."""
+        capacity = int(capacity)
+        if capacity < 1:
+            raise ValueError("capacity must be >= 1")
+        self.env, self.lib, self.device = env, env.lib, env.device
+        self.capacity, self.pitch = capacity, env.max_dim
+        self.toroidal = bool(getattr(env, "toroidal", False))
+        self.enrich = bool(getattr(env, "enrich", False))
+        self.words = archive_words(self.pitch)
+        C, dev = capacity, self.device
+        self.bits = torch.zeros(C, self.words, dtype=torch.int32, device=dev)
+        self.meta = torch.zeros(C, 2, dtype=torch.int32, device=dev)
+        self.algo = torch.zeros(C, dtype=torch.uint8, device=dev)
+        self.owner = torch.zeros(C, dtype=torch.int32, device=dev)
+        self.stamp = torch.zeros(C, dtype=torch.int32, device=dev)
+        # the push kernel's two-word counter (csrc/mz_archive.hip): a call reads word _cur and
+        # writes the other one, so no workgroup reads what another writes
+        self._count2 = torch.zeros(2, dtype=torch.int32, device=dev)
+        self._cur = 0
+        self.errors = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    # -------------------------------------------------------------------------------------------
+    def record(self, flags=None, stamp=0):
+        """env.mazes.append(maze) for the instances with flags != 0 (None: all), in ascending
+        id, each stamped `stamp`: one launch on the current stream, no host read."""
+        f = None
+        if flags is not None:
+            f = flags.to(device=self.device, dtype=torch.uint8).contiguous()
+            if f.numel() != self.env.num_envs:
+                raise ValueError("one flag per instance")
+        N.check(self.lib.mz_archive_push_pool(
+            self.env._h, None if f is None else f.data_ptr(), self.capacity, self.words,
+            self.bits.data_ptr(), self.meta.data_ptr(), self.algo.data_ptr(),
+            self.owner.data_ptr(), self.stamp.data_ptr(),
+            self._count2.data_ptr() + 4 * self._cur, int(stamp), self._stream()))
+        self._cur ^= 1
+
+    def load(self, env, slot, env_ids=None):
+        """MazeArchive.load from this pool: instance env_ids[j] (None: j) of `env` becomes entry
+        slot[j] (negative: left alone). The caller keeps slot[j] < held."""
+        _load_entries(self, env, slot, env_ids)
+
+    # -------------------------------------------------------------------------------------------
+    @property
+    def count(self):
+        """Entries offered so far (int32 0-dim device tensor; saturates at 2^31 - 1)."""
+        return self._count2[self._cur]
+
+    @property
+    def held(self):
+        """Entries the pool holds: min(count, capacity)."""
+        return self.count.clamp(max=self.capacity)
+
+    @property
+    def dropped(self):
+        """Entries offered after the pool was full: max(count - capacity, 0)."""
+        return (self.count - self.capacity).clamp(min=0)
+
+    def to_mazes(self, first=0, n=None):
+        """Held entries first .. first + n - 1 (n None: up to the last held one), oldest first, as
+        snapshot_mazes / best_of_mazes return mazes — (grids uint8 [m, D, D], start_goal int32
+        [m, 4], sizes int32 [m]) — for evaluate(learner, mazes=...) (host copies; synchronises)."""
+        first, held = int(first), int(self.held)
+        n = held - first if n is None else int(n)
+        if first < 0 or n < 0 or first + n > held:
+            raise ValueError(f"entries {first} .. {first + n - 1} of {held} held")
+        return _entries_to_mazes(self.bits[first:first + n].cpu().numpy(),
+                                 self.meta[first:first + n].cpu().numpy())
+
+    # -------------------------------------------------------------------------------------------
+    _TENSORS = ("bits", "meta", "algo", "owner", "stamp", "errors")
+    _GEOMETRY = ("pitch", "capacity", "toroidal", "enrich")
+
+    def state_dict(self):
+        sd = {k: getattr(self, k).clone() for k in self._TENSORS}
+        sd["count"] = self.count.reshape(1).clone()
+        sd.update(format=_POOL_FORMAT, **{k: getattr(self, k) for k in self._GEOMETRY})
+        return sd
+
+    def check_state_dict(self, sd):
+        """ValueError unless `sd` is a state_dict() of a pool of this pitch, capacity and
+        geometry (nothing is changed)."""
+        if not isinstance(sd, dict) or sd.get("format") != _POOL_FORMAT:
+            raise ValueError("not a MazePool state_dict")
+        for k in self._GEOMETRY:
+            if k not in sd or int(sd[k]) != int(getattr(self, k)):
+                raise ValueError(f"the saved pool's {k} {sd.get(k)} differs from this pool's "
+                                 f"{getattr(self, k)}")
+        for k in self._TENSORS + ("count",):
+            want = (1,) if k == "count" else tuple(getattr(self, k).shape)
+            if k not in sd or not torch.is_tensor(sd[k]) or tuple(sd[k].shape) != want or \
+                    sd[k].dtype != (torch.int32 if k == "count" else getattr(self, k).dtype):
+                raise ValueError(f"the saved pool's {k} has another shape or type")
+
+    def load_state_dict(self, sd):
+        self.check_state_dict(sd)
+        for k in self._TENSORS:
+            getattr(self, k).copy_(sd[k])
+        self._count2[self._cur:self._cur + 1].copy_(sd["count"])
 
 
 def instance_algorithms(env):

@@ -4,7 +4,9 @@
   torchrun --nproc-per-node 8 -m mazerl.train --envs 8192 --dim 81 --algo mixed    # 8 GPUs
 
 Prints one JSON line: training throughput (env steps/s and updates/s over all ranks) and the
-win-rate on fresh mazes (greedy and epsilon = eps_final, reference protocol Q14).
+win-rate on fresh mazes (greedy and epsilon = eps_final, reference protocol Q14). With --archive C
+the run keeps the mazes it trains on in a MazePool of C entries and the record gains the
+reference's "explored mazes" win rate, test(n, new=False) over the pool's oldest entries.
 """
 import argparse
 import json
@@ -14,7 +16,8 @@ import torch
 
 from .agents.dqn import VectorDQNLearner
 from .distributed import GradAllReduce, allreduce_sum, broadcast_params, init_from_env
-from .trainers.vector_trainer import VectorOffPolicyTrainer, best_of_mazes, evaluate, make_env
+from .trainers.vector_trainer import (VectorOffPolicyTrainer, best_of_mazes, evaluate,
+                                      evaluate_explored, make_env, steps_done_epsilon)
 
 
 def parse(argv=None):
@@ -56,7 +59,23 @@ def parse(argv=None):
                     help="checkpoint to continue from (mazerl/checkpoint.py; rank r reads "
                          "<path>.rank<r> when world > 1)")
     ap.add_argument("--save", default=None, help="checkpoint written after training (same naming)")
-    return ap.parse_args(argv)
+    ap.add_argument("--archive", type=int, default=0,
+                    help="C > 0: keep the first C mazes the run trains on (every instance's first "
+                         "maze, then each winner's new one) in a MazePool and report the win rate "
+                         "on them, the reference's test(n, new=False); 0 = off. An entry at "
+                         "--dim 81 is 841 bytes")
+    ap.add_argument("--explored-mazes", type=int, default=None,
+                    help="N: replay the pool's oldest N entries (default: all held; at most held)")
+    a = ap.parse_args(argv)
+    # refused here, before any GPU call
+    if a.archive < 0:
+        raise ValueError("--archive must be >= 0")
+    if a.explored_mazes is not None:
+        if a.explored_mazes < 1:
+            raise ValueError("--explored-mazes must be >= 1")
+        if not a.archive:
+            raise ValueError("--explored-mazes replays the pool: it needs --archive")
+    return a
 
 
 def _ck_path(path, rank, world):
@@ -92,7 +111,8 @@ def main(argv=None):
         learner.target.load_state_dict(learner.source.state_dict())
     trainer = VectorOffPolicyTrainer(env, learner, seed=a.seed + 7919 * rank,
                                      curriculum=None if a.curriculum == "none" else a.curriculum,
-                                     growth=growth, algorithm=algo, bank_candidates=a.candidates)
+                                     growth=growth, algorithm=algo, bank_candidates=a.candidates,
+                                     archive=a.archive or None)
     if a.resume:  # every rank its own shard's env / replay; the nets are identical on all ranks
         from .checkpoint import load_checkpoint
         load_checkpoint(_ck_path(a.resume, rank, world), trainer)
@@ -108,6 +128,24 @@ def main(argv=None):
     if a.save:
         from .checkpoint import save_checkpoint
         save_checkpoint(_ck_path(a.save, rank, world), trainer)
+    explored = None
+    if trainer.archive is not None:
+        # every rank replays its own pool; the (won, won, played) counts are summed over ranks
+        pool = trainer.archive
+        n = min(a.explored_mazes or pool.capacity, int(pool.held))
+        chunk = min(n, B)
+        xg, _ = evaluate_explored(learner, pool, n, eps=0.0, chunk=chunk, seed=0x7E590000)
+        xe, _ = evaluate_explored(learner, pool, n, chunk=chunk, seed=0x7E590000,
+                                  eps=steps_done_epsilon(learner, n, instances=pool.owner[:n]))
+        fill = trainer.summary()["archive"]
+        cnt = torch.tensor([round(xg * n), round(xe * n), n, fill["recorded"], fill["held"],
+                            fill["dropped"]], dtype=torch.float64, device=dev)
+        allreduce_sum(cnt)
+        cnt = cnt.tolist()
+        explored = {"win_rate_explored_greedy": cnt[0] / cnt[2],
+                    "win_rate_explored_eps": cnt[1] / cnt[2], "explored_mazes": int(cnt[2]),
+                    "archive": {"capacity": pool.capacity * world, "recorded": int(cnt[3]),
+                                "held": int(cnt[4]), "dropped": int(cnt[5])}}
     res = {}
     if rank == 0:
         eval_algo = "r-prim" if a.algo == "mixed" else a.algo
@@ -132,6 +170,8 @@ def main(argv=None):
             "candidates": a.candidates, "stopped_at": trainer.stopped_at,
             "schedule": trainer.schedule.summary() if trainer.schedule is not None else None,
         }
+        if explored is not None:
+            res.update(explored)
         print(json.dumps(res), flush=True)
     env.close()
     return res

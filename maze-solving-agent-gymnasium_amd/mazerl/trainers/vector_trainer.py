@@ -17,12 +17,17 @@ VectorOffPolicyTrainer.train() is NeuralOffPolicyTrainer.train (lib/trainers/off
   K learner updates (replay ratio), target sync / cosine step per update count.
 evaluate() is NeuralOffPolicyTrainer.test(new=True)/infer (:228-299): fresh mazes, one episode
 each, win = terminated; greedy (eps = 0) or the reference's epsilon protocol (Q14).
+archive= keeps what the reference env keeps in `env.mazes` — every instance's first maze and each
+winner's new one, in exploration order, in one MazePool (mazerl/archive.py) — and
+evaluate_explored() is test(n, new=False) over its oldest n entries (:228-263, the README's "W/R
+labirinti esplorati" column).
 """
 import os
 import time
 
 import torch
 
+from ..archive import MazePool
 from ..vector_env import ALGOS, VectorMazeEnv
 from .schedule import WinSchedule, curriculum_rule
 
@@ -32,11 +37,13 @@ class VectorOffPolicyTrainer:
     growth: None | (start, max_dim) — the variable-size envs' +4 growth per win and the max-shape
     stop (schedule.py; make the env with make_env(B, start, max_dim=max_dim)); algorithm: the
     initial mazes' algorithm (str or per-instance ids), the curriculum's base;
-    bank_candidates: best-of-C maze bank (1 = one Philox maze per slot)."""
+    bank_candidates: best-of-C maze bank (1 = one Philox maze per slot);
+    archive (None: off): an int C — a MazePool(env, C) — or a MazePool of this env: the explored
+    mazes, for evaluate_explored (one more launch and one flag copy per vector step)."""
 
     def __init__(self, env, learner, seed=0, regen_won=True, curriculum=False, allreduce_stats=None,
                  bank=True, fused=True, growth=None, algorithm="r-prim", bank_candidates=1,
-                 track_wins=False):
+                 track_wins=False, archive=None):
         self.env, self.learner = env, learner
         # inst_wins (per-instance win counts) is kept by the win schedule; track_wins keeps it
         # without one (one more launch per vector step)
@@ -52,6 +59,15 @@ class VectorOffPolicyTrainer:
                 dims = self.schedule.sizes()
             env.enable_bank(algorithms=[0, 1, 2] if rule else None, dims=dims,
                             candidates=bank_candidates)
+        self.archive = None
+        if archive is not None:
+            if isinstance(archive, MazePool):
+                if archive.env is not env:
+                    raise ValueError("the pool was built for another env")
+                self.archive = archive
+            else:
+                self.archive = MazePool(env, archive)
+            self.archive.record(stamp=0)  # the first mazes (simple_maze_env.py:34)
         self.seed = seed
         # fused: the per-step bookkeeping and the replay push as HIP launches (mz_trainer_tick,
         # mz_replay_push) instead of ~25 torch ops; False keeps the torch path (A/B, tests)
@@ -120,9 +136,19 @@ class VectorOffPolicyTrainer:
             rp.push_rest(env.actions, env.reward, env.obs6, env.window_bits)
         else:
             rp.push(s6, sw, env.actions, env.reward, env.obs6, env.window_bits)
+        arch = self.archive if self.regen_won else None
+        if arch is not None:
+            # the winners that will receive a new maze (the reset clears the flags): all of them,
+            # or under per-instance sizes those whose next size is not 0 (update_maze past
+            # max_shape appends nothing)
+            rd = env._regen_dims
+            new_maze = env.terminated.clone() if rd is None else \
+                (env.terminated.bool() & (rd > 0)).to(torch.uint8)
         env.reset_done(regen_won=self.regen_won)
         if sch is not None:  # update_maze's sizes, the max-shape stop (:202-212)
             sch.after_reset(won)
+        if arch is not None:  # env.mazes.append(maze) (simple_maze_env.py:91)
+            arch.record(new_maze, stamp=self.counter)
         # with an overlapped learner the updates run on its side stream; the next push (one row
         # per instance) is kept out of their sample range
         return L.update(self._expand, reserve=env.num_envs)
@@ -150,12 +176,28 @@ class VectorOffPolicyTrainer:
         after a load_state_dict continue exactly as further train() calls on the saved trainer
         would have."""
         L = self.learner
-        return {"format": "mazerl.VectorOffPolicyTrainer/2", "seed": self.seed,
-                "counter": self.counter, "wins": self.wins.clone(), "episodes": self.episodes.clone(),
-                "inst_wins": self.inst_wins.clone(), "curriculum": self.curriculum,
-                "regen_won": self.regen_won, "history": list(self.history),
-                "schedule": None if self.schedule is None else self.schedule.state_dict(),
-                "learner": L.state_dict(), "env": self.env.state_dict()}
+        sd = {"format": "mazerl.VectorOffPolicyTrainer/2", "seed": self.seed,
+              "counter": self.counter, "wins": self.wins.clone(), "episodes": self.episodes.clone(),
+              "inst_wins": self.inst_wins.clone(), "curriculum": self.curriculum,
+              "regen_won": self.regen_won, "history": list(self.history),
+              "schedule": None if self.schedule is None else self.schedule.state_dict(),
+              "learner": L.state_dict(), "env": self.env.state_dict()}
+        if self.archive is not None:  # (a trainer without a pool writes the keys it always wrote)
+            sd["archive"] = self.archive.state_dict()
+        return sd
+
+    def summary(self):
+        """Host-side counts (synchronises): the vector steps, the max-shape stop, the win
+        schedule's summary and the pool's fill."""
+        out = {"vector_steps": self.counter, "stopped_at": self.stopped_at,
+               "schedule": None if self.schedule is None else self.schedule.summary(),
+               "archive": None}
+        if self.archive is not None:
+            a = self.archive
+            count, held, dropped = torch.stack([a.count, a.held, a.dropped]).tolist()
+            out["archive"] = {"capacity": a.capacity, "recorded": count, "held": held,
+                              "dropped": dropped}
+        return out
 
     def load_state_dict(self, sd):
         fmt = sd.get("format")
@@ -167,6 +209,11 @@ class VectorOffPolicyTrainer:
         if sd["curriculum"] != self.curriculum or bool(sd["regen_won"]) != bool(self.regen_won) \
                 or (sd["schedule"] is None) != (self.schedule is None):
             raise ValueError("curriculum / growth / regen_won differ from the saved trainer's")
+        if ("archive" in sd) != (self.archive is not None):
+            raise ValueError("the saved trainer and this one differ in having an explored-maze "
+                             "pool (archive=)")
+        if self.archive is not None:  # (before anything changes)
+            self.archive.check_state_dict(sd["archive"])
         self.env.load_state_dict(sd["env"])
         self.learner.load_state_dict(sd["learner"])
         if self.schedule is not None:
@@ -176,6 +223,8 @@ class VectorOffPolicyTrainer:
         self.episodes.copy_(sd["episodes"])
         self.inst_wins.copy_(sd["inst_wins"])
         self.history = list(sd["history"])
+        if self.archive is not None:
+            self.archive.load_state_dict(sd["archive"])
         self._eps = None
 
     def _train(self, vector_steps, log_every, log, t0):
@@ -359,9 +408,22 @@ def evaluate(learner, num_mazes, dim, algorithm="r-prim", seed=0x7E57, eps=0.0, 
     if mazes is not None:
         load_selected(env, mazes)
     dim = max(dim) if not isinstance(dim, int) else dim
-    finished = torch.zeros(num_mazes, dtype=torch.bool, device=env.device)
-    won = torch.zeros(num_mazes, dtype=torch.bool, device=env.device)
     limit = max_vector_steps or (dim - 1) * (dim - 1) + 2  # > any max_steps
+    won, k = _play_episodes(learner, env, eps, seed, limit)
+    rate = float(won.float().mean())
+    env.close()
+    if return_won:
+        return rate, k, won.cpu().numpy()
+    return rate, k
+
+
+def _play_episodes(learner, env, eps, seed, limit):
+    """One episode per instance of a freshly reset `env` (evaluate / evaluate_explored): an
+    instance idles once its episode is over; at most `limit` vector steps. Returns (won bool [n]
+    device tensor, vector steps)."""
+    n = env.num_envs
+    finished = torch.zeros(n, dtype=torch.bool, device=env.device)
+    won = torch.zeros(n, dtype=torch.bool, device=env.device)
     k = 0
     while k < limit:
         greedy = learner.greedy(env.obs6, env.window, env.window_bits)
@@ -374,8 +436,52 @@ def evaluate(learner, num_mazes, dim, algorithm="r-prim", seed=0x7E57, eps=0.0, 
         k += 1
         if k % 32 == 0 and bool(finished.all()):
             break
-    rate = float(won.float().mean())
-    env.close()
+    return won, k
+
+
+@torch.no_grad()
+def evaluate_explored(learner, pool, n=None, eps=0.0, chunk=None, seed=0x7E57,
+                      max_vector_steps=None, return_won=False):
+    """The reference's test(n, new=False) (off_policy_trainer.py:228-263) over a MazePool: its
+    entries 0 .. n - 1 — the oldest n mazes the run trained on (n None: every held one) — one
+    episode each, win = terminated. Dense: the entries are played `chunk` at a time (None: all at
+    once), each chunk in an eval env of its own — the pool's pitch and geometry, enrich
+    observations and evaluate()'s window options — that pool.load() fills without a host copy, so
+    every instance of it plays. `eps` is a number or a callable k -> epsilon of each of the n
+    entries for the k-th action; steps_done_epsilon(learner, n, instances=pool.owner[:n]) is the
+    reference's protocol, every maze continuing its owner's epsilon. An entry the load refuses
+    would leave a generated maze in its place: pool.errors is read with the result and a
+    RuntimeError raised if it is not 0 (a corrupt pool: the result is void).
+    Returns (rate, vector steps over all chunks) or, with return_won, (rate, vector steps, won
+    bool [n] on the host)."""
+    held = int(pool.held)
+    n = held if n is None else int(n)
+    if n < 1 or n > held:
+        raise ValueError(f"n = {n}: the pool holds {held} entries")
+    chunk = n if chunk is None else int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1")
+    bits = getattr(learner, "supports_bits", False)
+    P = pool.pitch
+    limit = max_vector_steps or (P - 1) * (P - 1) + 2  # > any max_steps
+    won = torch.zeros(n, dtype=torch.bool, device=pool.device)
+    steps = 0
+    for first in range(0, n, chunk):
+        m = min(chunk, n - first)
+        env = make_env(m, P, toroidal=pool.toroidal, seed=seed, device=pool.device,
+                       done_list=False, pos=False, window=not bits, window_bits=True)
+        pool.load(env, torch.arange(first, first + m, dtype=torch.int32, device=pool.device))
+        env.reset()
+        e = (lambda k, a=first, b=first + m: eps(k)[a:b]) if callable(eps) else eps
+        w, k = _play_episodes(learner, env, e, seed, limit)
+        won[first:first + m] = w
+        steps += k
+        env.close()
+    wins, refused = torch.stack([won.sum(), pool.errors[0].to(torch.int64)]).tolist()
+    if refused:
+        raise RuntimeError(f"{refused} pool entries were refused by mz_archive_load "
+                           f"(pool.errors): the pool is corrupt, the result is void")
+    rate = wins / n
     if return_won:
-        return rate, k, won.cpu().numpy()
-    return rate, k
+        return rate, steps, won.cpu().numpy()
+    return rate, steps
