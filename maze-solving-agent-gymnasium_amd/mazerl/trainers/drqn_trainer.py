@@ -42,7 +42,6 @@ state is resized to the batch and never restored). Six departures fix the semant
 Training on truncated windows, burn-in and stored recurrent state (R2D2) are out of scope.
 """
 import ctypes as C
-import time
 
 import torch
 
@@ -50,8 +49,7 @@ from .. import _native as N
 from ..agents.flat import FlatAdamW, copy_flat, flatten_grads, flatten_params, grad_segment
 from ..agents.lstm_dqn_agent import DQN, ETA_MIN, HIDDEN, T_MAX, epsilon_at
 from ..agents.rf_agent import cosine_lr
-from .ppo_trainer import episode_bound
-from .schedule import WinSchedule, curriculum_rule
+from .episodic import EpisodicTrainer, episode_bound
 
 FORMAT = "mazerl.VectorRecurrentDQNTrainer/1"
 EVAL_KEY = 0x4556414C
@@ -66,30 +64,22 @@ def param_ptrs(net):
     return (C.c_void_p * 6)(*[p.data_ptr() for p in ps])
 
 
-class VectorRecurrentDQNTrainer:
+class VectorRecurrentDQNTrainer(EpisodicTrainer):
+    _FORMAT = FORMAT
+    _SHAPE = ("L", "capacity")
+    _REC = ("rec_x", "rec_a", "rec_r")
+    _COUNTERS = ("seed", "steps_done", "counter", "updates", "filled")
+
     def __init__(self, env, device, lr=1e-3, starting_epsilon=0.9, final_epsilon=0.05,
                  epsilon_decay=1000.0, discount_factor=0.99, batch_size=32, memory_size=20000,
                  target_update_frequency=10, explore_actions=4, train_every=1, seed=0, bank=True,
                  curriculum=False, growth=None, algorithm="r-prim", bank_candidates=1):
-        self.env = env
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("VectorRecurrentDQNTrainer runs on the GPU (libmazerl HIP kernels)")
         if batch_size < 1 or memory_size < batch_size or train_every < 1 or \
                 target_update_frequency < 1 or explore_actions not in (1, 2, 3, 4):
             raise ValueError("batch_size >= 1, memory_size >= batch_size, train_every >= 1, "
                              "target_update_frequency >= 1, explore_actions in 1..4")
-        rule = curriculum_rule(curriculum)
-        self.curriculum = rule
-        self.schedule = (WinSchedule(env, rule, growth, None, algorithm)
-                         if (rule is not None or growth is not None) else None)
-        self.stopped_at = None
-        if bank:
-            dims = getattr(env, "dims_in_use", None)
-            if self.schedule is not None and self.schedule.growth is not None:
-                dims = self.schedule.sizes()
-            env.enable_bank(algorithms=[0, 1, 2] if rule else None, dims=dims,
-                            candidates=bank_candidates)
+        super().__init__(env, device, bank=bank, curriculum=curriculum, growth=growth,
+                         algorithm=algorithm, bank_candidates=bank_candidates)
         torch.manual_seed(seed)
         self.source_net = DQN(6, 4, HIDDEN, self.device)
         self.target_net = DQN(6, 4, HIDDEN, self.device)
@@ -112,25 +102,16 @@ class VectorRecurrentDQNTrainer:
         self.counter = 0      # vector steps (the exploration draws' counter)
         self.updates = 0
         self.filled = 0       # the host's lower bound of the ring's count
-        B, E = env.num_envs, self.batch_size
-        self.L = L = episode_bound(env.max_dim, env.toroidal)
+        B, E, L = env.num_envs, self.batch_size, self.L
         kw = dict(device=self.device)
         i32, i64, f32 = torch.int32, torch.int64, torch.float32
         self.h = torch.zeros(HIDDEN, B, dtype=f32, **kw)
         self.c = torch.zeros(HIDDEN, B, dtype=f32, **kw)
-        self.t = torch.zeros(B, dtype=i32, **kw)
-        self.act_out = torch.zeros(B, dtype=i32, **kw)
         self.rec_x = torch.zeros(B, L + 1, 6, dtype=f32, **kw)
         self.rec_a = torch.zeros(B, L, dtype=i32, **kw)
         self.rec_r = torch.zeros(B, L, dtype=torch.float64, **kw)
         self.r64 = torch.zeros(B, dtype=torch.float64, **kw)
-        self.fin_id = torch.zeros(B, dtype=i32, **kw)
-        self.fin_off = torch.zeros(B, dtype=i64, **kw)
-        self.fin_len = torch.zeros(B, dtype=i32, **kw)
-        self.fin_count = torch.zeros(1, dtype=i32, **kw)
         self.pool = torch.zeros(2, dtype=i64, **kw)  # mz_ppo_scan's row counters (unused here)
-        # episodes, wins, dropped 1-step episodes, record-buffer overflows
-        self.stats = torch.zeros(4, dtype=i64, **kw)
         # the replay memory: fixed-stride slots of L + 1 rows of 32 B
         self.mem = torch.zeros(self.capacity, L + 1, ROW, dtype=i32, **kw)
         self.mem_len = torch.zeros(self.capacity, dtype=i32, **kw)
@@ -151,24 +132,6 @@ class VectorRecurrentDQNTrainer:
         self.gpart = torch.zeros(E, PARAMS, dtype=f32, **kw)
         self.loss = torch.zeros(1, dtype=f32, **kw)
         self.last_lr = None
-        self.lib = N.load()
-
-    supports_bits = True  # evaluate(): the f32 windows are never read
-
-    @property
-    def episodes(self):
-        return int(self.stats[0])
-
-    @property
-    def wins(self):
-        return int(self.stats[1])
-
-    @property
-    def algo(self):
-        return None if self.schedule is None else self.schedule.maze_algo
-
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
 
     def epsilon(self):
         return epsilon_at(self.steps_done, self.starting_epsilon, self.final_epsilon,
@@ -191,11 +154,8 @@ class VectorRecurrentDQNTrainer:
     def _scan_store(self):
         env, B, L, st = self.env, self.env.num_envs, self.L, self._stream()
         self.r64.copy_(env.reward)
-        N.check(self.lib.mz_ppo_scan(
-            self.r64.data_ptr(), env.terminated.data_ptr(), env.truncated.data_ptr(), B, L,
-            self.t.data_ptr(), self.rec_r.data_ptr(), self.fin_id.data_ptr(),
-            self.fin_off.data_ptr(), self.fin_len.data_ptr(), self.fin_count.data_ptr(),
-            self.pool[0:].data_ptr(), self.pool[1:].data_ptr(), self.stats.data_ptr(), st))
+        self._scan(self.r64, env.terminated, env.truncated, self.rec_r,
+                   self.pool[0:].data_ptr(), self.pool[1:].data_ptr())
         N.check(self.lib.mz_drqn_store(
             env.obs6.data_ptr(), env.terminated.data_ptr(), B, L, self.fin_id.data_ptr(),
             self.fin_len.data_ptr(), self.fin_count.data_ptr(), self.rec_x.data_ptr(),
@@ -243,35 +203,17 @@ class VectorRecurrentDQNTrainer:
             copy_flat(self.target_net, self.source_net)
 
     def vector_step(self):
-        env = self.env
         self._act()
-        env.step(self.act_out)
+        self.env.step(self.act_out)
         self._scan_store()
-        sch = self.schedule
-        if sch is not None:
-            won = env.terminated.bool()
-            sch.before_reset(won)
-        env.reset_done(regen_won=True)
-        if sch is not None:
-            sch.after_reset(won)
+        self._reset_winners()
         if self.filled < self.batch_size:  # (only until the first batch exists: one sync a step)
             self.filled = int(self.ring[1])
         if self.filled >= self.batch_size and self.counter % self.train_every == 0:
             self._update()
 
-    def train(self, vector_steps, log_every=0, log=print):
-        t0 = time.perf_counter()
-        sch = self.schedule
-        for k in range(vector_steps):
-            self.vector_step()
-            if sch is not None and sch.growth is not None and (k + 1) % 32 == 0 and sch.all_retired():
-                self.stopped_at = k + 1
-                break
-            if log_every and (k + 1) % log_every == 0 and log:
-                log(dict(step=k + 1, episodes=self.episodes, wins=self.wins, updates=self.updates,
-                         loss=float(self.loss), seconds=round(time.perf_counter() - t0, 2)))
-        torch.cuda.synchronize()
-        return time.perf_counter() - t0
+    def _log_fields(self):
+        return {"loss": float(self.loss)}
 
     # ---- evaluation (vector_trainer.evaluate) ---------------------------------------------------
     def evaluator(self):
@@ -293,43 +235,24 @@ class VectorRecurrentDQNTrainer:
             self._eval.reset()
 
     # ---- checkpoint / resume (mazerl/checkpoint.py) -------------------------------------------
-    _REC = ("rec_x", "rec_a", "rec_r")
-
-    def _live(self, L):
-        return torch.arange(L, device=self.device)[None, :] < self.t[:, None].long()
+    _OWN = ("h", "c", "ring", "pool", "loss")
 
     def state_dict(self):
         """The run between two vector steps: both nets, the optimizer, (h, c), the in-flight
-        records (each instance's first t[i] rows), the filled replay slots with head and count,
-        the counters and the env."""
-        torch.cuda.synchronize(self.device)
-        o = self.opt
+        records, the filled replay slots with head and count, the counters and the env
+        (_save_common)."""
+        sd, o = self._save_common(), self.opt
         n = int(self.ring[1])
-        live = self._live(self.L)
-        return {"format": FORMAT, "L": self.L, "capacity": self.capacity,
-                "schedule": None if self.schedule is None else self.schedule.state_dict(),
-                "source": {k: v.clone() for k, v in self.source_net.state_dict().items()},
-                "target": {k: v.clone() for k, v in self.target_net.state_dict().items()},
-                "opt": {"exp_avg": o.exp_avg.clone(), "exp_avg_sq": o.exp_avg_sq.clone(),
-                        "step": o._step_buf.clone(), "lr": o.param_groups[0]["lr"].clone()},
-                "h": self.h.clone(), "c": self.c.clone(), "t": self.t.clone(),
-                "records": {"rec_x": self.rec_x[:, :self.L][live], "rec_a": self.rec_a[live],
-                            "rec_r": self.rec_r[live]},
-                "ring": self.ring.clone(), "mem": self.mem[:n].clone(),
-                "mem_len": self.mem_len[:n].clone(), "mem_term": self.mem_term[:n].clone(),
-                "stats": self.stats.clone(), "pool": self.pool.clone(), "loss": self.loss.clone(),
-                "counters": {k: getattr(self, k) for k in ("seed", "steps_done", "counter",
-                                                           "updates", "filled")},
-                "env": self.env.state_dict()}
+        sd.update({k: getattr(self, k).clone() for k in self._OWN})
+        sd.update({k: getattr(self, k)[:n].clone() for k in ("mem", "mem_len", "mem_term")})
+        sd["source"] = {k: v.clone() for k, v in self.source_net.state_dict().items()}
+        sd["target"] = {k: v.clone() for k, v in self.target_net.state_dict().items()}
+        sd["opt"] = {"exp_avg": o.exp_avg.clone(), "exp_avg_sq": o.exp_avg_sq.clone(),
+                     "step": o._step_buf.clone(), "lr": o.param_groups[0]["lr"].clone()}
+        return sd
 
     def load_state_dict(self, sd):
-        if sd.get("format") != FORMAT or sd["L"] != self.L or sd["capacity"] != self.capacity:
-            raise ValueError("not a VectorRecurrentDQNTrainer state_dict of this shape")
-        if (sd["schedule"] is None) != (self.schedule is None):
-            raise ValueError("curriculum / growth differ from the saved trainer's")
-        self.env.load_state_dict(sd["env"])
-        if self.schedule is not None:
-            self.schedule.load_state_dict(sd["schedule"])
+        self._load_common(sd)
         with torch.no_grad():
             self.source_net.load_state_dict(sd["source"])
             self.target_net.load_state_dict(sd["target"])
@@ -338,18 +261,11 @@ class VectorRecurrentDQNTrainer:
         o.exp_avg_sq.copy_(sd["opt"]["exp_avg_sq"])
         o._step_buf.copy_(sd["opt"]["step"])
         o.param_groups[0]["lr"].copy_(sd["opt"]["lr"])
-        for k in ("h", "c", "t", "ring", "stats", "pool", "loss"):
+        for k in self._OWN:
             getattr(self, k).copy_(sd[k])
-        live = self._live(self.L)
-        self.rec_x[:, :self.L][live] = sd["records"]["rec_x"].to(self.device)
-        self.rec_a[live] = sd["records"]["rec_a"].to(self.device)
-        self.rec_r[live] = sd["records"]["rec_r"].to(self.device)
         n = sd["mem"].shape[0]
-        self.mem[:n].copy_(sd["mem"])
-        self.mem_len[:n].copy_(sd["mem_len"])
-        self.mem_term[:n].copy_(sd["mem_term"])
-        for k, v in sd["counters"].items():
-            setattr(self, k, int(v))
+        for k in ("mem", "mem_len", "mem_term"):
+            getattr(self, k)[:n].copy_(sd[k])
 
 
 def evaluate_plain(learner, num_mazes, dim, algorithm="r-prim", seed=0x7E57, toroidal=False,

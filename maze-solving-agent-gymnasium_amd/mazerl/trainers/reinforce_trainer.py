@@ -33,46 +33,34 @@ Two departures from the one-env reference, both forced by the batch:
     reference's step; with many instances the rows of an episode acted under older parameters
     carry no importance weight.
 """
-import time
-
 import torch
 
 from .. import _native as N
 from ..agents.flat import FlatAdamWGroups
 from ..agents.rf_agent import PolicyNetwork, cosine_lr, head_loss
-from .ppo_trainer import episode_bound
-from .schedule import WinSchedule, curriculum_rule
+from .episodic import PooledEpisodicTrainer
 
 FORMAT = "mazerl.VectorReinforceTrainer/1"
 SAMPLE_KEY = 0x5A4D504C  # evaluation draws: a key of their own beside the training draws'
 
 
-class VectorReinforceTrainer:
+class VectorReinforceTrainer(PooledEpisodicTrainer):
+    _FORMAT = FORMAT
+    _REC = ("b_s6", "b_w", "b_a", "b_r")
+    _POOL_COLS = (("p_s6", (6,), torch.float32), ("p_w", (22,), torch.int32),
+                  ("p_a", (), torch.int64), ("p_adv", (), torch.float32),
+                  ("p_len", (), torch.int32))
+    _POOL = tuple(c[0] for c in _POOL_COLS)
+    _COUNTERS = ("seed", "counter", "sample_counter", "consumed", "updates", "rows_trained")
+
     def __init__(self, env, device, lr=1e-3, gamma=0.99, update_rows=16384, batch_size=2048,
                  temperature=2.0, entropy_coef=0.01, hidden_dim=1024, h_channels=32, seed=0,
                  bank=True, curriculum=False, growth=None, algorithm="r-prim", bank_candidates=1,
                  pool_capacity=None):
         """update_rows: pool rows that make an update due (1: after every finished episode);
-        curriculum / growth / algorithm / bank_candidates: VectorPPOTrainer's (schedule.py)."""
-        self.env = env
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("VectorReinforceTrainer runs on the GPU (libmazerl HIP kernels)")
-        if env.window_bits is None or env.reward64 is None:
-            raise ValueError("VectorReinforceTrainer needs an env with window_bits=True, reward64=True")
-        from ..gemm_tuning import enable as _tuned_gemms
-        _tuned_gemms(self.device)  # the tuned f32 GEMM choices (gemm_tuning.py)
-        rule = curriculum_rule(curriculum)
-        self.curriculum = rule
-        self.schedule = (WinSchedule(env, rule, growth, None, algorithm)
-                         if (rule is not None or growth is not None) else None)
-        self.stopped_at = None
-        if bank:
-            dims = getattr(env, "dims_in_use", None)
-            if self.schedule is not None and self.schedule.growth is not None:
-                dims = self.schedule.sizes()
-            env.enable_bank(algorithms=[0, 1, 2] if rule else None, dims=dims,
-                            candidates=bank_candidates)
+        curriculum / growth / algorithm / bank_candidates: EpisodicTrainer's (schedule.py)."""
+        super().__init__(env, device, update_rows, pool_capacity, bank=bank, curriculum=curriculum,
+                         growth=growth, algorithm=algorithm, bank_candidates=bank_candidates)
         torch.manual_seed(seed)
         self.net = PolicyNetwork(3, 6, 4, h_channels, hidden_dim).to(self.device)
         self.opt = FlatAdamWGroups(self.net, [(self.net.parameters(), lr)], max_norm=1.0)
@@ -84,67 +72,19 @@ class VectorReinforceTrainer:
         self.seed = int(seed)
         self.counter = 0
         self.sample_counter = 0
-        B = env.num_envs
-        self.L = L = episode_bound(env.max_dim, env.toroidal)
+        B, L = env.num_envs, self.L
         kw = dict(device=self.device)
         # per-instance episode records [B, L]
         self.b_s6 = torch.zeros(B, L, 6, dtype=torch.float32, **kw)
         self.b_w = torch.zeros(B, L, 22, dtype=torch.int32, **kw)
         self.b_a = torch.zeros(B, L, dtype=torch.int64, **kw)
         self.b_r = torch.zeros(B, L, dtype=torch.float64, **kw)
-        self.t = torch.zeros(B, dtype=torch.int32, **kw)
-        self.act_out = torch.zeros(B, dtype=torch.int32, **kw)
-        # the update pool; the fill bound at an update is VectorPPOTrainer's (update_rows + what
-        # the vector steps between a check's issue and its use can append)
-        self.cap = int(pool_capacity or self.update_rows + 2 * B * L)
-        C = self.cap
-        self.p_s6 = torch.zeros(C, 6, dtype=torch.float32, **kw)
-        self.p_w = torch.zeros(C, 22, dtype=torch.int32, **kw)
-        self.p_a = torch.zeros(C, dtype=torch.int64, **kw)
-        self.p_adv = torch.zeros(C, dtype=torch.float32, **kw)
-        self.p_len = torch.zeros(C, dtype=torch.int32, **kw)
-        self.fin_id = torch.zeros(B, dtype=torch.int32, **kw)
-        self.fin_off = torch.zeros(B, dtype=torch.int64, **kw)
-        self.fin_len = torch.zeros(B, dtype=torch.int32, **kw)
-        self.fin_count = torch.zeros(1, dtype=torch.int32, **kw)
-        self.pool_fill = torch.zeros(1, dtype=torch.int64, **kw)
-        self.pool_total = torch.zeros(1, dtype=torch.int64, **kw)
         self.pool_episodes = torch.zeros(1, dtype=torch.int32, **kw)
-        # episodes, wins, dropped 1-step episodes, record-buffer overflows (an error, _update)
-        self.stats = torch.zeros(4, dtype=torch.int64, **kw)
-        self._total_host = torch.zeros(1, dtype=torch.int64, pin_memory=True)
-        self._total_ev = None
         self._none = torch.zeros(32, dtype=torch.int64, **kw)  # sample(): records nothing
         self.consumed = 0
         self.updates = 0
         self.rows_trained = 0
         self.last_update = None  # the last update's pool columns, episode count, lr and loss
-        self.lib = N.load()
-
-    @property
-    def supports_bits(self):
-        return True
-
-    @property
-    def episodes(self):
-        return int(self.stats[0])
-
-    @property
-    def wins(self):
-        return int(self.stats[1])
-
-    @property
-    def algo(self):
-        return None if self.schedule is None else self.schedule.maze_algo
-
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
-    _REC = ("b_s6", "b_w", "b_a", "b_r")
-    _POOL = ("p_s6", "p_w", "p_a", "p_adv", "p_len")
-
-    def _cols(self, lo, hi):
-        return tuple(getattr(self, k)[lo:hi] for k in self._POOL)
 
     @torch.no_grad()
     def _act(self):
@@ -159,38 +99,14 @@ class VectorReinforceTrainer:
         self.counter += 1
         return logits
 
-    def _scan_finish(self, reward64=None, terminated=None, truncated=None):
-        """The step's outcome (default: the env's output tensors) -> records, finished episodes
-        -> pool."""
-        env, B, L, st = self.env, self.env.num_envs, self.L, self._stream()
-        r64 = env.reward64 if reward64 is None else reward64
-        term = env.terminated if terminated is None else terminated
-        trunc = env.truncated if truncated is None else truncated
-        N.check(self.lib.mz_ppo_scan(
-            r64.data_ptr(), term.data_ptr(), trunc.data_ptr(), B, L,
-            self.t.data_ptr(), self.b_r.data_ptr(), self.fin_id.data_ptr(), self.fin_off.data_ptr(),
-            self.fin_len.data_ptr(), self.fin_count.data_ptr(), self.pool_fill.data_ptr(),
-            self.pool_total.data_ptr(), self.stats.data_ptr(), st))
+    def _finish(self):
+        """mz_rf_finish: the finished episodes' returns and baseline, their rows into the pool."""
         N.check(self.lib.mz_rf_finish(
             self.b_r.data_ptr(), self.b_s6.data_ptr(), self.b_w.data_ptr(), self.b_a.data_ptr(),
-            B, L, self.fin_id.data_ptr(), self.fin_off.data_ptr(), self.fin_len.data_ptr(),
-            self.fin_count.data_ptr(), self.gamma, self.cap, self.p_s6.data_ptr(),
-            self.p_w.data_ptr(), self.p_a.data_ptr(), self.p_adv.data_ptr(), self.p_len.data_ptr(),
-            self.pool_episodes.data_ptr(), st))
-
-    def _due(self):
-        """True when the pool held >= update_rows rows when the last check was issued (the host
-        copy of the appended total lands while the next vector step runs; it only grows, so a
-        late look never overshoots)."""
-        due = False
-        if self._total_ev is not None:
-            self._total_ev.synchronize()
-            due = int(self._total_host[0]) - self.consumed >= self.update_rows
-            self._total_ev = None
-        self._total_host.copy_(self.pool_total, non_blocking=True)
-        self._total_ev = torch.cuda.Event()
-        self._total_ev.record()
-        return due
+            self.env.num_envs, self.L, self.fin_id.data_ptr(), self.fin_off.data_ptr(),
+            self.fin_len.data_ptr(), self.fin_count.data_ptr(), self.gamma, self.cap,
+            self.p_s6.data_ptr(), self.p_w.data_ptr(), self.p_a.data_ptr(), self.p_adv.data_ptr(),
+            self.p_len.data_ptr(), self.pool_episodes.data_ptr(), self._stream()))
 
     def update(self, cols, episodes, lr):
         """One optimizer step on pool rows `cols` = (obs6, window bits, action, adv, length) of
@@ -234,34 +150,13 @@ class VectorReinforceTrainer:
         self.updates += 1
 
     def vector_step(self):
-        env = self.env
         self._act()
-        env.step(self.act_out)
+        self.env.step(self.act_out)
         self._scan_finish()
-        sch = self.schedule
-        if sch is not None:  # change_algorithm for the winners (value_based_trainer.py:72)
-            won = env.terminated.bool()
-            sch.before_reset(won)
-        env.reset_done(regen_won=True)
-        if sch is not None:  # update_maze's sizes, the max-shape stop (:74-83)
-            sch.after_reset(won)
-        if self._due():
+        # change_algorithm, update_maze's sizes (value_based_trainer.py:72-83)
+        self._reset_winners()
+        if self._due(self.update_rows):
             self._update()
-
-    def train(self, vector_steps, log_every=0, log=print):
-        t0 = time.perf_counter()
-        sch = self.schedule
-        for k in range(vector_steps):
-            self.vector_step()
-            # the max-shape stop (value_based_trainer.py:81-83) once every instance reached it
-            if sch is not None and sch.growth is not None and (k + 1) % 32 == 0 and sch.all_retired():
-                self.stopped_at = k + 1
-                break
-            if log_every and (k + 1) % log_every == 0 and log:
-                log(dict(step=k + 1, episodes=self.episodes, wins=self.wins, updates=self.updates,
-                         seconds=round(time.perf_counter() - t0, 2)))
-        torch.cuda.synchronize()
-        return time.perf_counter() - t0
 
     # ---- evaluation (vector_trainer.evaluate) ---------------------------------------------------
     @torch.no_grad()
@@ -295,57 +190,21 @@ class VectorReinforceTrainer:
     # ---- checkpoint / resume (mazerl/checkpoint.py) -------------------------------------------
     def state_dict(self):
         """The run between two vector steps: the net, the optimizer (moments, step, learning
-        rate), the in-flight episodes' records (each instance's first t[i] rows), the update
-        pool's filled rows, the counters and the env."""
-        torch.cuda.synchronize(self.device)
-        t = self.t.clone()
-        live = torch.arange(self.L, device=self.device)[None, :] < t[:, None].long()
-        fill = int(self.pool_fill.item())
-        o = self.opt
-        return {"format": FORMAT, "L": self.L, "cap": self.cap,
-                "schedule": None if self.schedule is None else self.schedule.state_dict(),
-                "net": {k: v.clone() for k, v in self.net.state_dict().items()},
-                "opt": {k: getattr(o, k).clone() for k in ("exp_avg", "exp_avg_sq", "step_t", "lr_dev")},
-                "t": t, "records": {k: getattr(self, k)[live] for k in self._REC},
-                "pool_fill": fill, "pool": {k: getattr(self, k)[:fill].clone() for k in self._POOL},
-                "pool_total": self.pool_total.clone(), "pool_episodes": self.pool_episodes.clone(),
-                "stats": self.stats.clone(),
-                # the appended total the next _due() reads (copied one vector step late)
-                "total_host": int(self._total_host[0]) if self._total_ev is not None else None,
-                "counters": {k: getattr(self, k) for k in ("seed", "counter", "sample_counter",
-                                                           "consumed", "updates", "rows_trained")},
-                "env": self.env.state_dict()}
+        rate), the in-flight episodes' records, the update pool's filled rows, the counters and
+        the env (_save_common)."""
+        sd, o = self._save_common(), self.opt
+        sd["net"] = {k: v.clone() for k, v in self.net.state_dict().items()}
+        sd["opt"] = {k: getattr(o, k).clone() for k in ("exp_avg", "exp_avg_sq", "step_t", "lr_dev")}
+        sd["pool_episodes"] = self.pool_episodes.clone()
+        return sd
 
     def load_state_dict(self, sd):
-        if sd.get("format") != FORMAT or sd["L"] != self.L or sd["cap"] != self.cap:
-            raise ValueError("not a VectorReinforceTrainer state_dict of this shape")
-        if (sd["schedule"] is None) != (self.schedule is None):
-            raise ValueError("curriculum / growth differ from the saved trainer's")
-        self.env.load_state_dict(sd["env"])
-        if self.schedule is not None:
-            self.schedule.load_state_dict(sd["schedule"])
+        self._load_common(sd)
         with torch.no_grad():
             self.net.load_state_dict(sd["net"])
         for k, v in sd["opt"].items():
             getattr(self.opt, k).copy_(v)
-        self.t.copy_(sd["t"])
-        live = torch.arange(self.L, device=self.device)[None, :] < self.t[:, None].long()
-        for k in self._REC:
-            getattr(self, k)[live] = sd["records"][k].to(self.device)
-        fill = int(sd["pool_fill"])
-        for k in self._POOL:
-            getattr(self, k)[:fill].copy_(sd["pool"][k])
-        self.pool_fill.fill_(fill)
-        self.pool_total.copy_(sd["pool_total"])
         self.pool_episodes.copy_(sd["pool_episodes"])
-        self.stats.copy_(sd["stats"])
-        for k, v in sd["counters"].items():
-            setattr(self, k, int(v))
-        self._total_ev = None
-        if sd["total_host"] is not None:  # what the saved trainer's next _due() would have read
-            self._total_host[0] = int(sd["total_host"])
-            self._total_ev = torch.cuda.Event()
-            self._total_ev.record()
 
 
 class _Sampler:

@@ -72,6 +72,46 @@ def growth_sizes(start, max_dim):
     return list(range(int(start), int(max_dim) + 1, 4))
 
 
+def make_schedule(env, curriculum, growth, learner, algorithm):
+    """(rule, WinSchedule) of a trainer's curriculum / growth arguments; the schedule is None
+    when neither is asked for."""
+    rule = curriculum_rule(curriculum)
+    if rule is None and growth is None:
+        return rule, None
+    return rule, WinSchedule(env, rule, growth, learner, algorithm)
+
+
+def enable_winner_bank(env, rule, schedule, candidates):
+    """Winners' new mazes (update_maze) copied from a bank built ahead of time on a side stream
+    (VectorMazeEnv.enable_bank: a maze build is a ~1 ms serial chain that would stall the step),
+    one bank per grid size the run can reach and, under a curriculum, per algorithm."""
+    dims = getattr(env, "dims_in_use", None)
+    if schedule is not None and schedule.growth is not None:
+        dims = schedule.sizes()
+    env.enable_bank(algorithms=[0, 1, 2] if rule else None, dims=dims, candidates=candidates)
+
+
+def reset_winners(env, schedule, regen_won=True):
+    """The end of a vector step: change_algorithm for the winners, then winners get new mazes
+    and truncated instances restart theirs, then update_maze's sizes and the retirements.
+    Returns the step's winners (None without a schedule)."""
+    if schedule is None:
+        env.reset_done(regen_won=regen_won)
+        return None
+    won = env.terminated.bool()
+    schedule.before_reset(won)
+    env.reset_done(regen_won=regen_won)
+    schedule.after_reset(won)
+    return won
+
+
+def max_shape_stop(schedule, k):
+    """The max-shape stop after vector step k (0-based): looked at every 32nd step (one
+    synchronisation, with N ranks one collective), true once every instance is retired."""
+    return schedule is not None and schedule.growth is not None and (k + 1) % 32 == 0 \
+        and schedule.all_retired()
+
+
 class WinSchedule:
     def __init__(self, env, curriculum=None, growth=None, learner=None, algorithm="r-prim"):
         self.env, self.learner = env, learner

@@ -29,7 +29,7 @@ import torch
 
 from ..archive import MazePool
 from ..vector_env import ALGOS, VectorMazeEnv
-from .schedule import WinSchedule, curriculum_rule
+from .schedule import enable_winner_bank, make_schedule, max_shape_stop
 
 
 class VectorOffPolicyTrainer:
@@ -48,17 +48,9 @@ class VectorOffPolicyTrainer:
         # inst_wins (per-instance win counts) is kept by the win schedule; track_wins keeps it
         # without one (one more launch per vector step)
         self.track_wins = bool(track_wins)
-        rule = curriculum_rule(curriculum)
-        self.schedule = (WinSchedule(env, rule, growth, learner, algorithm)
-                         if (rule is not None or growth is not None) else None)
+        rule, self.schedule = make_schedule(env, curriculum, growth, learner, algorithm)
         if regen_won and bank:
-            # winners' new mazes come from a bank refilled on a side stream (VectorMazeEnv.
-            # enable_bank): a maze build is a ~1 ms serial chain that would stall the step
-            dims = getattr(env, "dims_in_use", None)
-            if self.schedule is not None and self.schedule.growth is not None:
-                dims = self.schedule.sizes()
-            env.enable_bank(algorithms=[0, 1, 2] if rule else None, dims=dims,
-                            candidates=bank_candidates)
+            enable_winner_bank(env, rule, self.schedule, bank_candidates)
         self.archive = None
         if archive is not None:
             if isinstance(archive, MazePool):
@@ -238,7 +230,7 @@ class VectorOffPolicyTrainer:
         for k in range(vector_steps):
             loss = self.vector_step()
             # the max-shape stop (off_policy_trainer.py:210-212) once every instance reached it
-            if sch is not None and sch.growth is not None and (k + 1) % 32 == 0 and sch.all_retired():
+            if max_shape_stop(sch, k):
                 self.stopped_at = k + 1
                 break
             if log_every and (k + 1) % log_every == 0:

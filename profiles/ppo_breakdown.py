@@ -41,7 +41,7 @@ def main(B=4096, steps=300):
         t = tick("finish", t)
         env.reset_done(regen_won=True)
         t = tick("reset_regen", t)
-        if tr._due():
+        if tr._due(tr.pool_size):
             tr._update(k / steps)
         t = tick("update", t)
     tot = sum(acc.values())
