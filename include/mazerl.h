@@ -344,6 +344,28 @@ int mz_stem_backward_ex(const uint32_t* bits_dev, const uint8_t* code_dev, const
                         float* db_dev, uint64_t* rng_advance_dev, void* stream);
 int mz_stem_workspace_floats(int32_t n);
 
+/* The convolutional autoencoder that pre-trains that stem (lib/models/convolutional_autoencoder.py,
+ * train_CAE.py): decoder ConvTranspose2d(32, 3, kernel 2, stride 2, output_padding 1) -> Sigmoid
+ * over the stem's features feat_dev [n][ld] f32 (first 1,568 columns, c*49 + 7i + j; ld >= 1568),
+ * dec_w_dev [32][3][2][2], dec_b_dev [3]. mz_cae_decode writes Y [n][3][15][15] f32. */
+int mz_cae_decode(const float* feat_dev, int32_t ld, int32_t n, const float* dec_w_dev,
+                  const float* dec_b_dev, float* out_dev, void* stream);
+/* The reconstruction loss alpha * MSE(Y, X) + (1 - alpha) * (1 - SSIM(Y, X)) against the packed
+ * windows bits_dev [n][22] (bit ch*225 + r*15 + c of a sample is X[ch][r][c]); SSIM with an 11-tap
+ * Gaussian (sigma 1.5) filtered without padding (15x15 -> 5x5), C1 = 0.01^2, C2 = 0.03^2, the mean
+ * of the map (pytorch_msssim.ssim(Y, X, data_range=1) by definition). loss3_dev [3] f32 = loss,
+ * mse, ssim. With their pointers non-NULL also the gradients: gfeat_dev [n][ldg] (first 1,568
+ * columns; ldg >= 1568) = dL/dfeat, what mz_stem_backward takes; dw_dec_dev [32][3][2][2],
+ * db_dec_dev [3] (overwritten). ws_dev: mz_cae_workspace_floats(n) floats. Y stays on chip; sums
+ * over samples run in a fixed order (no atomics). Refused (nothing launched), by both entry
+ * points: a NULL required pointer, n < 1 or n > 4,194,304 (2^22: the workspace size stays an int;
+ * mz_cae_workspace_floats returns 0 outside that range), ld or ldg < 1568, alpha outside [0, 1]. */
+int mz_cae_loss(const uint32_t* bits_dev, const float* feat_dev, int32_t ld, int32_t n,
+                const float* dec_w_dev, const float* dec_b_dev, float alpha, float* loss3_dev,
+                float* gfeat_dev, int32_t ldg, float* dw_dec_dev, float* db_dec_dev, float* ws_dev,
+                void* stream);
+int mz_cae_workspace_floats(int32_t n);
+
 /* The learner's parameter update: grad.clamp_(-clamp, clamp) on every parameter, then one
  * torch.optim.AdamW step (dqn_agent.py:152-157, ddqn_agent.py:148-152: AdamW(lr) with the
  * defaults betas (0.9, 0.999), eps 1e-8, weight_decay 1e-2 — the eager single-tensor formula)

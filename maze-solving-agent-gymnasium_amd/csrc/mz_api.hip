@@ -622,6 +622,34 @@ int mz_stem_backward(const uint32_t* bits_dev, const uint8_t* code_dev, const fl
                              db_dev, nullptr, stream);
 }
 
+int mz_cae_workspace_floats(int32_t n) { return n > 0 && n <= MZ_CAE_MAX_N ? mz_cae_ws_floats(n) : 0; }
+
+int mz_cae_decode(const float* feat_dev, int32_t ld, int32_t n, const float* dec_w_dev,
+                  const float* dec_b_dev, float* out_dev, void* stream) {
+  if (!feat_dev || !dec_w_dev || !dec_b_dev || !out_dev) return fail(MZ_EINVAL, "bad arguments");
+  if (n < 1 || n > MZ_CAE_MAX_N) return fail(MZ_EINVAL, "sample count %d", n);
+  if (ld < 1568) return fail(MZ_EINVAL, "feature stride %d", ld);
+  MZ_HIP(mz_launch_cae_decode(feat_dev, ld, n, dec_w_dev, dec_b_dev, out_dev,
+                              static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_cae_loss(const uint32_t* bits_dev, const float* feat_dev, int32_t ld, int32_t n,
+                const float* dec_w_dev, const float* dec_b_dev, float alpha, float* loss3_dev,
+                float* gfeat_dev, int32_t ldg, float* dw_dec_dev, float* db_dec_dev, float* ws_dev,
+                void* stream) {
+  if (!bits_dev || !feat_dev || !dec_w_dev || !dec_b_dev || !loss3_dev || !ws_dev)
+    return fail(MZ_EINVAL, "bad arguments");
+  if (n < 1 || n > MZ_CAE_MAX_N) return fail(MZ_EINVAL, "sample count %d", n);
+  if (ld < 1568) return fail(MZ_EINVAL, "feature stride %d", ld);
+  if (ldg < 1568) return fail(MZ_EINVAL, "gradient stride %d", ldg);
+  if (!(alpha >= 0.0f && alpha <= 1.0f)) return fail(MZ_EINVAL, "alpha %g", (double)alpha);
+  MZ_HIP(mz_launch_cae_loss(bits_dev, feat_dev, ld, n, dec_w_dev, dec_b_dev, alpha, loss3_dev,
+                            gfeat_dev, ldg, dw_dec_dev, db_dec_dev, ws_dev,
+                            static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
 int mz_adamw_flat(float* param_dev, float* exp_avg_dev, float* exp_avg_sq_dev,
                   const float* const* grads_dev, const int64_t* seg_len, int32_t nseg,
                   const float* lr_dev, float* step_dev, double beta1, double beta2, double eps,

@@ -10,6 +10,14 @@ hipError_t mz_launch_stem_fwd(const uint32_t* bits, const float* obs6, int n, co
 hipError_t mz_launch_stem_bwd(const uint32_t* bits, const uint8_t* code, const float* g, int ld,
                               int n, float drop_p, float* partial, float* dw, float* db,
                               hipStream_t s, uint64_t* advance = nullptr);
+// ---- the autoencoder's decoder + reconstruction loss (mz_cae.hip)
+#define MZ_CAE_MAX_N (1 << 22)  // samples per call (the workspace size stays an int)
+int mz_cae_ws_floats(int n);
+hipError_t mz_launch_cae_decode(const float* feat, int ld, int n, const float* w, const float* b,
+                                float* out, hipStream_t s);
+hipError_t mz_launch_cae_loss(const uint32_t* bits, const float* feat, int ld, int n, const float* w,
+                              const float* b, float alpha, float* loss3, float* gfeat, int ldg,
+                              float* dw, float* db, float* ws, hipStream_t s);
 #define MZ_OPT_MAX_SEGS 16
 
 hipError_t mz_launch_adamw(float* p, float* m, float* v, const float* const* grads,

@@ -57,7 +57,8 @@ EXPORTS = ["mz_last_error", "mz_device_count", "mz_create", "mz_destroy", "mz_lo
            "mz_dqtab_act", "mz_dqtab_update", "mz_dqtab_hash_act", "mz_dqtab_hash_update",
            "mz_dqtab_hash_rehash", "mz_dqtab_hash_lookup",
            "mz_archive_words", "mz_archive_push", "mz_archive_load",
-           "mz_archive_pool_span", "mz_archive_push_pool"]
+           "mz_archive_pool_span", "mz_archive_push_pool",
+           "mz_cae_decode", "mz_cae_loss", "mz_cae_workspace_floats"]
 
 _lib = None
 
@@ -157,6 +158,10 @@ def load(build_if_missing=True):
         L.mz_stem_backward_ex.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_float, vp, vp, vp,
                                           vp, vp]
     L.mz_stem_workspace_floats.argtypes = [C.c_int32]
+    L.mz_cae_decode.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp]
+    L.mz_cae_loss.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_float, vp, vp, C.c_int32,
+                              vp, vp, vp, vp]
+    L.mz_cae_workspace_floats.argtypes = [C.c_int32]
     L.mz_qact_workspace_floats.argtypes = [C.c_int32]
     L.mz_leaky_relu_bf16.argtypes = [vp, C.c_int64, C.c_float, vp]
     L.mz_colsum_f32.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]

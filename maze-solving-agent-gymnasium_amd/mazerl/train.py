@@ -7,6 +7,8 @@ Prints one JSON line: training throughput (env steps/s and updates/s over all ra
 win-rate on fresh mazes (greedy and epsilon = eps_final, reference protocol Q14). With --archive C
 the run keeps the mazes it trains on in a MazePool of C entries and the record gains the
 reference's "explored mazes" win rate, test(n, new=False) over the pool's oldest entries.
+--stem PATH starts the conv stem from an encoder pre-trained by python -m mazerl.train_cae (off
+by default).
 """
 import argparse
 import json
@@ -66,6 +68,11 @@ def parse(argv=None):
                          "--dim 81 is 841 bytes")
     ap.add_argument("--explored-mazes", type=int, default=None,
                     help="N: replay the pool's oldest N entries (default: all held; at most held)")
+    ap.add_argument("--stem", default=None,
+                    help="start the Q-networks' conv stem from a saved encoder: a state_dict "
+                         "written by python -m mazerl.train_cae (loaded with weights_only), or a "
+                         "module pickled by the reference's train_CAE.py (full unpickling as the "
+                         "fallback: only files you trust); default: the nets' own init")
     a = ap.parse_args(argv)
     # refused here, before any GPU call
     if a.archive < 0:
@@ -106,6 +113,9 @@ def main(argv=None):
                                updates_per_step=a.updates_per_step, target_every=a.target_every,
                                allreduce=GradAllReduce() if world > 1 else None, seed=a.seed,
                                overlap=bool(a.overlap), acting=a.acting)
+    if a.stem:  # source and target stems <- the pre-trained encoder, acting weights refreshed
+        from .cae import load_stem
+        load_stem(learner, a.stem)
     if world > 1:
         broadcast_params(learner.source)
         learner.target.load_state_dict(learner.source.state_dict())
