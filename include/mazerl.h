@@ -780,6 +780,89 @@ int mz_drqn_seq_backward(const float* const* params_dev, int32_t hidden, int32_t
                          const double* ep_loss_dev, float* gpart_dev, float* const* grads_dev,
                          float* loss_dev, void* stream);
 
+/* ---- Populations of recurrent DQN learners (VectorRecurrentDQNPopulation) ---------------------
+ * P independent learners of agents/lstm_dqn_agent.py (nn.LSTMCell(6, 32) + nn.Linear(32, 4),
+ * whole episodes from SequentialExperienceReplayMemory, lib/replay_memory.py:26-43) advanced by
+ * the same launches over B = P b instances; learner p owns instances [p b, (p + 1) b). Each is,
+ * bit for bit, what the single-learner entry points above compute on its block: the same device
+ * code runs on learner p's rows. params_dev (and the gradient, the AdamW moments) is ONE device
+ * buffer, flat [P][5252] f32, a row in state_dict order (weight_ih, weight_hh, bias_ih, bias_hh,
+ * fc.weight, fc.bias). Per-learner scalars are device arrays of P; due_dev (int32 [P], NULL: all)
+ * marks the learners an update touches: nothing of a learner with due_dev[p] == 0 is written.
+ * Every entry point refuses a null pointer, P < 1, b < 1, E < 1, hidden != 32 and capacity < E
+ * with MZ_EINVAL before any GPU call. */
+
+/* mz_drqn_act for every learner: instance i of learner p acts from row p of params_dev with
+ * eps_dev[p], its Philox draw keyed by (seed_dev[p], counter, i - p b). A workgroup stages one
+ * learner's parameters, so the grid is P x ceil(b / 16). h_dev / c_dev stay [32][P b]; t_dev,
+ * the records, act_out_dev and q_out_dev are indexed by the global instance as in mz_drqn_act,
+ * with the same rules for t_dev and L == 0. */
+int mz_drqn_pop_act(const float* params_dev, int32_t hidden, int32_t P, int32_t b,
+                    const float* obs6_dev, int32_t L, const float* eps_dev,
+                    int32_t explore_actions, const uint64_t* seed_dev, uint64_t counter,
+                    const int32_t* t_dev, float* h_dev, float* c_dev, float* rec_x_dev,
+                    int32_t* rec_a_dev, int32_t* act_out_dev, float* q_out_dev, void* stream);
+
+/* mz_drqn_store for every learner, after mz_ppo_scan over all P b instances: the finished list
+ * is in instance order, so learner p's episodes are a contiguous run of it, and the k-th of that
+ * run goes into slot (head_p + k) mod capacity of learner p's ring (the last `capacity` of a
+ * longer run stay). mem_dev [P][capacity][L + 1][8] words, mem_len_dev / mem_term_dev
+ * [P][capacity], ring_dev int64 [P][2]. A learner with no finished episode has nothing written. */
+int mz_drqn_pop_store(const float* obs6_dev, const uint8_t* term_dev, int32_t P, int32_t b,
+                      int32_t L, const int32_t* fin_id_dev, const int32_t* fin_len_dev,
+                      const int32_t* fin_count_dev, float* rec_x_dev, const int32_t* rec_a_dev,
+                      const double* rec_r_dev, int64_t capacity, uint32_t* mem_dev,
+                      int32_t* mem_len_dev, int32_t* mem_term_dev, int64_t* ring_dev,
+                      void* stream);
+
+/* mz_drqn_sample per due learner, one wave each, keyed by (seed_dev[p], counter_dev[p]) over
+ * learner p's filled slots; the directories are [P][E] (dir_tot [P][2]). min_filled is the
+ * caller's knowledge of the smallest ring count among the due learners; E > min_filled is
+ * refused. */
+int mz_drqn_pop_sample(const uint64_t* seed_dev, const uint64_t* counter_dev,
+                       const int32_t* due_dev, int32_t P, int32_t E, int32_t L, int64_t capacity,
+                       int64_t min_filled, const int64_t* ring_dev, const int32_t* mem_len_dev,
+                       int32_t* dir_slot_dev, int32_t* dir_len_dev, int64_t* dir_off_dev,
+                       int64_t* dir_tot_dev, void* stream);
+
+/* mz_drqn_seq_forward per due learner: one wave per (learner, episode). The row buffers are
+ * [P][E (L + 1)] (stash_dev [P][E (L + 1)][192], ep_loss_dev [P][E]); dir_off counts rows within
+ * the learner's own buffer. gamma_dev: f32 [P] (source mode; may be NULL with target != 0). */
+int mz_drqn_pop_seq_forward(const float* params_dev, int32_t hidden, int32_t target, int32_t P,
+                            int32_t E, int32_t L, int64_t capacity, const float* gamma_dev,
+                            const int32_t* due_dev, const uint32_t* mem_dev,
+                            const int32_t* mem_term_dev, const int32_t* dir_slot_dev,
+                            const int32_t* dir_len_dev, const int64_t* dir_off_dev,
+                            const int64_t* dir_tot_dev, float* qmax_dev, float* stash_dev,
+                            float* qa_dev, float* y_dev, float* d_dev, double* ep_loss_dev,
+                            void* stream);
+
+/* mz_drqn_seq_backward per due learner: gpart_dev [P][E][5252]; each learner's E partials are
+ * summed in episode order (float64, rounded once) into row p of grads_dev (flat [P][5252],
+ * overwritten) and loss_dev[p]. No atomics. */
+int mz_drqn_pop_seq_backward(const float* params_dev, int32_t hidden, int32_t P, int32_t E,
+                             int32_t L, int64_t capacity, const int32_t* due_dev,
+                             const uint32_t* mem_dev, const int32_t* dir_slot_dev,
+                             const int32_t* dir_len_dev, const int64_t* dir_off_dev,
+                             const int64_t* dir_tot_dev, const float* stash_dev,
+                             const float* d_dev, const double* ep_loss_dev, float* gpart_dev,
+                             float* grads_dev, float* loss_dev, void* stream);
+
+/* The target sync (lstm_dqn_agent.py update_target: target.load_state_dict(source.state_dict()))
+ * of the learners with mask_dev[p] != 0: row p of dst_dev <- row p of src_dev ([P][5252]). */
+int mz_drqn_pop_sync(const float* src_dev, float* dst_dev, const int32_t* mask_dev, int32_t P,
+                     void* stream);
+
+/* mz_adamw_flat's clamp + AdamW (dqn_agent.py:152-157) over rows [P][n] (n a multiple of 4, the
+ * buffers 16-byte aligned): row p at lr_dev[p] with step count step_dev[p] (f32, advanced by
+ * one), the element arithmetic shared with mz_adamw_flat, so one row gives the same bits. A row
+ * with due_dev[p] == 0 keeps its parameters, moments, gradient and step count. */
+int mz_adamw_pop(float* param_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_dev,
+                 int32_t P, int64_t n, const float* lr_dev, float* step_dev,
+                 const int32_t* due_dev, double beta1, double beta2, double eps,
+                 double weight_decay, float clamp, float grad_scale, int32_t write_grad,
+                 void* stream);
+
 /* ---- The DQN / DDQN acting forward, f32-accurate on the bf16 MFMA (mz_qact.hip) -------------
  * Replaces, per acting row, source_net(state).max(1)[1] (dqn_agent.py:113-116; the nets of
  * dqn_agent.py:19-57 / ddqn_agent.py:18-52 at the reference's sizes: Conv2d(3, 32, 3, p 1),

@@ -1633,6 +1633,154 @@ int mz_drqn_seq_backward(const float* const* params_dev, int32_t hidden, int32_t
   return MZ_OK;
 }
 
+// ---- populations of recurrent DQN learners (mz_drqn.hip k_drqn_pop_*) ----------------------------
+static int drqn_pop_args(const char* who, int32_t hidden, int32_t P, int64_t per, const char* what) {
+  if (hidden != MZ_DRQN_HIDDEN) return fail(MZ_EINVAL, "%s: hidden %d != 32", who, hidden);
+  if (P < 1 || P > 65535 || per < 1 || (int64_t)P * per > 0x7fffffffll)
+    return fail(MZ_EINVAL, "%s: learners %d (1..65535), %s %lld", who, P, what, (long long)per);
+  return MZ_OK;
+}
+
+int mz_drqn_pop_act(const float* params_dev, int32_t hidden, int32_t P, int32_t b,
+                    const float* obs6_dev, int32_t L, const float* eps_dev,
+                    int32_t explore_actions, const uint64_t* seed_dev, uint64_t counter,
+                    const int32_t* t_dev, float* h_dev, float* c_dev, float* rec_x_dev,
+                    int32_t* rec_a_dev, int32_t* act_out_dev, float* q_out_dev, void* stream) {
+  if (!params_dev || !obs6_dev || !eps_dev || !seed_dev || !t_dev || !h_dev || !c_dev ||
+      !act_out_dev || (L > 0 && (!rec_x_dev || !rec_a_dev)))
+    return fail(MZ_EINVAL, "mz_drqn_pop_act: null pointer");
+  if (int rc = drqn_pop_args("mz_drqn_pop_act", hidden, P, b, "instances per learner")) return rc;
+  if (L < 0 || explore_actions < 1 || explore_actions > 4)
+    return fail(MZ_EINVAL, "mz_drqn_pop_act: L %d, explore_actions %d", L, explore_actions);
+  StreamGuard g(stream);
+  MzDrqnPopAct q{{mz_drqn_flat_net(params_dev), obs6_dev, P * b, L, 0.0f, explore_actions, 0,
+                  counter, t_dev, h_dev, c_dev, h_dev, c_dev, rec_x_dev, rec_a_dev, act_out_dev,
+                  q_out_dev},
+                 P, b, eps_dev, seed_dev};
+  MZ_HIP(mz_launch_drqn_pop_act(q, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_drqn_pop_store(const float* obs6_dev, const uint8_t* term_dev, int32_t P, int32_t b,
+                      int32_t L, const int32_t* fin_id_dev, const int32_t* fin_len_dev,
+                      const int32_t* fin_count_dev, float* rec_x_dev, const int32_t* rec_a_dev,
+                      const double* rec_r_dev, int64_t capacity, uint32_t* mem_dev,
+                      int32_t* mem_len_dev, int32_t* mem_term_dev, int64_t* ring_dev,
+                      void* stream) {
+  if (!obs6_dev || !term_dev || !fin_id_dev || !fin_len_dev || !fin_count_dev || !rec_x_dev ||
+      !rec_a_dev || !rec_r_dev || !mem_dev || !mem_len_dev || !mem_term_dev || !ring_dev)
+    return fail(MZ_EINVAL, "mz_drqn_pop_store: null pointer");
+  if (int rc = drqn_pop_args("mz_drqn_pop_store", MZ_DRQN_HIDDEN, P, b, "instances per learner"))
+    return rc;
+  if (L < 1 || capacity < 1)
+    return fail(MZ_EINVAL, "mz_drqn_pop_store: L %d, capacity %lld", L, (long long)capacity);
+  StreamGuard g(stream);
+  MzDrqnPopStore q{{obs6_dev, term_dev, P * b, L, fin_id_dev, fin_len_dev, fin_count_dev,
+                    rec_x_dev, rec_a_dev, rec_r_dev, capacity, mem_dev, mem_len_dev, mem_term_dev,
+                    ring_dev},
+                   P, b};
+  MZ_HIP(mz_launch_drqn_pop_store(q, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_drqn_pop_sample(const uint64_t* seed_dev, const uint64_t* counter_dev,
+                       const int32_t* due_dev, int32_t P, int32_t E, int32_t L, int64_t capacity,
+                       int64_t min_filled, const int64_t* ring_dev, const int32_t* mem_len_dev,
+                       int32_t* dir_slot_dev, int32_t* dir_len_dev, int64_t* dir_off_dev,
+                       int64_t* dir_tot_dev, void* stream) {
+  if (!seed_dev || !counter_dev || !ring_dev || !mem_len_dev || !dir_slot_dev || !dir_len_dev ||
+      !dir_off_dev || !dir_tot_dev)
+    return fail(MZ_EINVAL, "mz_drqn_pop_sample: null pointer");
+  if (int rc = drqn_pop_args("mz_drqn_pop_sample", MZ_DRQN_HIDDEN, P, E, "E")) return rc;
+  if (E > 8192 || L < 1 || capacity < E || min_filled > capacity || min_filled < E)
+    return fail(MZ_EINVAL, "mz_drqn_pop_sample: E %d (1..8192), L %d, capacity %lld, smallest "
+                "filled %lld", E, L, (long long)capacity, (long long)min_filled);
+  StreamGuard g(stream);
+  MzDrqnPopSample q{{0, 0, E, L, capacity, ring_dev, mem_len_dev, dir_slot_dev, dir_len_dev,
+                     dir_off_dev, dir_tot_dev},
+                    P, seed_dev, counter_dev, due_dev};
+  MZ_HIP(mz_launch_drqn_pop_sample(q, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_drqn_pop_seq_forward(const float* params_dev, int32_t hidden, int32_t target, int32_t P,
+                            int32_t E, int32_t L, int64_t capacity, const float* gamma_dev,
+                            const int32_t* due_dev, const uint32_t* mem_dev,
+                            const int32_t* mem_term_dev, const int32_t* dir_slot_dev,
+                            const int32_t* dir_len_dev, const int64_t* dir_off_dev,
+                            const int64_t* dir_tot_dev, float* qmax_dev, float* stash_dev,
+                            float* qa_dev, float* y_dev, float* d_dev, double* ep_loss_dev,
+                            void* stream) {
+  if (!params_dev || !mem_dev || !mem_term_dev || !dir_slot_dev || !dir_len_dev || !dir_off_dev ||
+      !dir_tot_dev || !qmax_dev ||
+      (!target && (!gamma_dev || !stash_dev || !qa_dev || !y_dev || !d_dev || !ep_loss_dev)))
+    return fail(MZ_EINVAL, "mz_drqn_pop_seq_forward: null pointer");
+  if (int rc = drqn_pop_args("mz_drqn_pop_seq_forward", hidden, P, E, "E")) return rc;
+  if (int rc = drqn_seq_args("mz_drqn_pop_seq_forward", hidden, E, L, capacity)) return rc;
+  StreamGuard g(stream);
+  MzDrqnPopSeq q{{mz_drqn_flat_net(params_dev), target ? 1 : 0, E, L, capacity, 0.0f, mem_dev,
+                  mem_term_dev, dir_slot_dev, dir_len_dev, dir_off_dev, dir_tot_dev, qmax_dev,
+                  stash_dev, qa_dev, y_dev, d_dev, ep_loss_dev, nullptr},
+                 P, gamma_dev, due_dev};
+  MZ_HIP(mz_launch_drqn_pop_seq_forward(q, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_drqn_pop_seq_backward(const float* params_dev, int32_t hidden, int32_t P, int32_t E,
+                             int32_t L, int64_t capacity, const int32_t* due_dev,
+                             const uint32_t* mem_dev, const int32_t* dir_slot_dev,
+                             const int32_t* dir_len_dev, const int64_t* dir_off_dev,
+                             const int64_t* dir_tot_dev, const float* stash_dev,
+                             const float* d_dev, const double* ep_loss_dev, float* gpart_dev,
+                             float* grads_dev, float* loss_dev, void* stream) {
+  if (!params_dev || !mem_dev || !dir_slot_dev || !dir_len_dev || !dir_off_dev || !dir_tot_dev ||
+      !stash_dev || !d_dev || !ep_loss_dev || !gpart_dev || !grads_dev || !loss_dev)
+    return fail(MZ_EINVAL, "mz_drqn_pop_seq_backward: null pointer");
+  if (int rc = drqn_pop_args("mz_drqn_pop_seq_backward", hidden, P, E, "E")) return rc;
+  if (int rc = drqn_seq_args("mz_drqn_pop_seq_backward", hidden, E, L, capacity)) return rc;
+  StreamGuard g(stream);
+  MzDrqnPopSeq q{{mz_drqn_flat_net(params_dev), 0, E, L, capacity, 0.0f, mem_dev, nullptr,
+                  dir_slot_dev, dir_len_dev, dir_off_dev, dir_tot_dev, nullptr,
+                  const_cast<float*>(stash_dev), nullptr, nullptr, const_cast<float*>(d_dev),
+                  nullptr, gpart_dev},
+                 P, nullptr, due_dev};
+  MZ_HIP(mz_launch_drqn_pop_seq_backward(q, static_cast<hipStream_t>(stream)));
+  MzDrqnPopReduce r{P, E, gpart_dev, ep_loss_dev, dir_len_dev, dir_tot_dev, grads_dev, loss_dev,
+                    due_dev};
+  MZ_HIP(mz_launch_drqn_pop_reduce(r, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_drqn_pop_sync(const float* src_dev, float* dst_dev, const int32_t* mask_dev, int32_t P,
+                     void* stream) {
+  if (!src_dev || !dst_dev || !mask_dev) return fail(MZ_EINVAL, "mz_drqn_pop_sync: null pointer");
+  if (P < 1 || P > 65535) return fail(MZ_EINVAL, "mz_drqn_pop_sync: learners %d (1..65535)", P);
+  StreamGuard g(stream);
+  MZ_HIP(mz_launch_drqn_pop_sync(src_dev, dst_dev, mask_dev, P, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_adamw_pop(float* param_dev, float* exp_avg_dev, float* exp_avg_sq_dev, float* grad_dev,
+                 int32_t P, int64_t n, const float* lr_dev, float* step_dev,
+                 const int32_t* due_dev, double beta1, double beta2, double eps,
+                 double weight_decay, float clamp, float grad_scale, int32_t write_grad,
+                 void* stream) {
+  if (!param_dev || !exp_avg_dev || !exp_avg_sq_dev || !grad_dev || !lr_dev || !step_dev)
+    return fail(MZ_EINVAL, "mz_adamw_pop: null pointer");
+  if (P < 1 || P > 65535 || n < 4 || (n & 3))
+    return fail(MZ_EINVAL, "mz_adamw_pop: learners %d (1..65535), row length %lld (a multiple of 4)",
+                P, (long long)n);
+  if (!(clamp > 0.0f)) return fail(MZ_EINVAL, "mz_adamw_pop: clamp %g", (double)clamp);
+  const uintptr_t al = reinterpret_cast<uintptr_t>(param_dev) | reinterpret_cast<uintptr_t>(exp_avg_dev) |
+                       reinterpret_cast<uintptr_t>(exp_avg_sq_dev) | reinterpret_cast<uintptr_t>(grad_dev);
+  if (al & 15) return fail(MZ_EALIGN, "mz_adamw_pop: buffers must be 16-byte aligned");
+  StreamGuard g(stream);
+  MZ_HIP(mz_launch_adamw_pop(param_dev, exp_avg_dev, exp_avg_sq_dev, grad_dev, P, n, lr_dev,
+                             step_dev, due_dev, beta1, beta2, eps, weight_decay, clamp, grad_scale,
+                             write_grad, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
 int mz_qact_prepare(const float* fc1_w_dev, const float* fc2_w_dev, uint16_t* w1_hi_dev,
                     uint16_t* w1_lo_dev, uint16_t* w2_hi_dev, uint16_t* w2_lo_dev, void* stream) {
   if (!fc1_w_dev || !fc2_w_dev || !w1_hi_dev || !w1_lo_dev || !w2_hi_dev || !w2_lo_dev)

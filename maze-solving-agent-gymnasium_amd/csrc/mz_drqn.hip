@@ -35,6 +35,15 @@
 //   k_drqn_reduce    per parameter the partials summed over the episodes in index order (float64,
 //                    rounded once) into the net's gradient segments; the loss (float64, episode
 //                    order). No float atomics anywhere: two runs give the same bits.
+// Populations (trainers/drqn_population.py VectorRecurrentDQNPopulation): P independent learners
+// over B = P b instances, learner p owning instances [p b, (p + 1) b), flat [P][5252] parameters.
+// Every kernel above is a thin wrapper of a __device__ body; its k_drqn_pop_* twin moves the
+// single-learner argument struct to learner p's rows (parameters, ring, directory, row buffers,
+// eps / seed / gamma / update count) and calls the same body, so a learner's results are the
+// single-learner kernels' bits by construction. Grids: act P x ceil(b / 16) workgroups (none
+// straddles two learners); store (<= 256, P) workgroups, learner p's run of the finished list
+// found by two binary searches; sample P waves; the sequence kernels P E waves; reduce and the
+// target sync (21, P). Waves of a learner that is not due exit at once.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -55,6 +64,9 @@ constexpr int STASH = MZ_DRQN_STASH;    // 192 floats per stashed step
 constexpr int P_WIH = 0, P_WHH = P_WIH + G4 * NX, P_BIH = P_WHH + G4 * H, P_BHH = P_BIH + G4,
               P_FCW = P_BHH + G4, P_FCB = P_FCW + 4 * H;
 static_assert(P_FCB + 4 == MZ_DRQN_PARAMS, "parameter count");
+// mz_drqn_flat_net (mz_learner.h) splits a population's flat row at these offsets
+static_assert(P_WHH == 768 && P_BIH == 768 + 4096 && P_BHH == P_BIH + 128 && P_FCW == P_BHH + 128 &&
+              P_FCB == P_FCW + 128, "flat row offsets");
 
 __device__ inline float sigmoidf_(float z) { return 1.0f / (1.0f + expf(-z)); }
 
@@ -75,7 +87,10 @@ static_assert(PARTS == 1 || PARTS == 2 || PARTS == 4, "threads per instance");
 // puts the (up to 4) distinct 16-B addresses of a wave's ds_read_b128 on different banks. Every
 // thread holds the instance's whole old h in registers. The new h goes round through LDS for the
 // head: part a computes q[a] (a + PARTS, ...) in the fixed order, part 0 draws and records.
-__global__ __launch_bounds__(ACT_T) void k_drqn_act(MzDrqnAct q) {
+// blk: the workgroup's index among the workgroups of q's B instances; ld: the pitch of h / c (the
+// launch's whole instance count: q may be one learner's block of a population's arrays). The Philox
+// draw is keyed by the instance's index within q.
+__device__ __forceinline__ void drqn_act_body(const MzDrqnAct& q, const int blk, const size_t B) {
   __shared__ __attribute__((aligned(16))) float w[A_TOT];
   __shared__ float hq[IPB][H + 1];
   __shared__ float qs[IPB][4];
@@ -90,10 +105,9 @@ __global__ __launch_bounds__(ACT_T) void k_drqn_act(MzDrqnAct q) {
   if (threadIdx.x < 4) w[A_FCB + threadIdx.x] = q.p.fc_b[threadIdx.x];
   __syncthreads();
   const int j = threadIdx.x % IPB, part = threadIdx.x / IPB;
-  const int i = blockIdx.x * IPB + j;
+  const int i = blk * IPB + j;
   const bool live = i < q.B;
   const int ii = live ? i : q.B - 1;  // a tail thread shadows the last instance and writes nothing
-  const size_t B = (size_t)q.B;
   const int t = q.t[ii];
   const bool eval = q.L == 0;
   const bool rec = live && t >= 0 && t < q.L;
@@ -170,14 +184,54 @@ __global__ __launch_bounds__(ACT_T) void k_drqn_act(MzDrqnAct q) {
   }
 }
 
+__global__ __launch_bounds__(ACT_T) void k_drqn_act(MzDrqnAct q) {
+  drqn_act_body(q, blockIdx.x, (size_t)q.B);
+}
+
+// learner p's view of a population's flat [P][5252] parameters
+__device__ __forceinline__ MzDrqnNet drqn_net_row(const MzDrqnNet& n, const int p) {
+  const size_t o = (size_t)p * MZ_DRQN_PARAMS;
+  return MzDrqnNet{n.w_ih + o, n.w_hh + o, n.b_ih + o, n.b_hh + o, n.fc_w + o, n.fc_b + o};
+}
+
+// The population's acting step: workgroup (p, blk) runs k_drqn_act's body on learner p's block of
+// b instances with its own parameters, eps and seed, so no workgroup straddles two learners (the
+// tail workgroup of a learner is partly idle).
+__global__ __launch_bounds__(ACT_T) void k_drqn_pop_act(MzDrqnPopAct q) {
+  const int bpl = (q.b + IPB - 1) / IPB;
+  const int p = blockIdx.x / bpl;
+  const size_t i0 = (size_t)p * q.b;
+  MzDrqnAct a = q.a;
+  a.p = drqn_net_row(q.a.p, p);
+  a.B = q.b;
+  a.eps = q.eps[p];
+  a.seed = q.seed[p];
+  a.obs6 += i0 * NX;
+  a.t += i0;
+  a.h += i0;
+  a.c += i0;
+  a.h_out += i0;
+  a.c_out += i0;
+  if (a.L > 0) {
+    a.rec_x += i0 * (a.L + 1) * NX;
+    a.rec_a += i0 * a.L;
+  }
+  a.act_out += i0;
+  if (a.q_out) a.q_out += i0 * 4;
+  drqn_act_body(a, blockIdx.x % bpl, (size_t)q.a.B);
+}
+
 // ---- replay memory ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_drqn_store(MzDrqnStore q) {
-  const int nfin = min(max(*q.fin_count, 0), q.B);
+// the listed episodes fin_id / fin_len [0, nfin) into q's ring, episode k into slot (head + k) mod
+// capacity; workgroup blk of nblk takes every nblk-th
+__device__ __forceinline__ void drqn_store_body(const MzDrqnStore& q, const int32_t* fin_id,
+                                                const int32_t* fin_len, const int nfin,
+                                                const int blk, const int nblk) {
   const int64_t head = q.ring[0];
   // more finished episodes than slots: the last `capacity` stay (a deque's maxlen)
   const int first = nfin > q.cap ? nfin - (int)q.cap : 0;
-  for (int k = first + blockIdx.x; k < nfin; k += gridDim.x) {
-    const int i = q.fin_id[k], n = q.fin_len[k];
+  for (int k = first + blk; k < nfin; k += nblk) {
+    const int i = fin_id[k], n = fin_len[k];
     if (i < 0 || i >= q.B || n < 1 || n > q.L || head < 0 || head >= q.cap) continue;
     const int64_t slot = (head + k) % q.cap;
     float* rx = q.rec_x + (size_t)i * (q.L + 1) * NX;
@@ -201,21 +255,69 @@ __global__ __launch_bounds__(256) void k_drqn_store(MzDrqnStore q) {
   }
 }
 
-// after k_drqn_store (same stream): head and count move on by the stored episodes
-__global__ void k_drqn_ring(const int32_t* fin_count, int B, int64_t cap, int64_t* ring) {
-  const int64_t nfin = min(max(*fin_count, 0), B);
+__global__ __launch_bounds__(256) void k_drqn_store(MzDrqnStore q) {
+  drqn_store_body(q, q.fin_id, q.fin_len, min(max(*q.fin_count, 0), q.B), blockIdx.x, gridDim.x);
+}
+
+__device__ __forceinline__ void drqn_ring_advance(int64_t* ring, const int64_t nfin,
+                                                  const int64_t cap) {
   const int64_t head = ring[0], count = ring[1];
   if (head < 0 || head >= cap) return;
   ring[0] = (head + nfin) % cap;
   ring[1] = count + nfin < cap ? count + nfin : cap;
 }
 
+// after k_drqn_store (same stream): head and count move on by the stored episodes
+__global__ void k_drqn_ring(const int32_t* fin_count, int B, int64_t cap, int64_t* ring) {
+  drqn_ring_advance(ring, min(max(*fin_count, 0), B), cap);
+}
+
+// The finished list is in instance order, so learner p's episodes are the run [lo, hi) of it whose
+// instances lie in [p b, (p + 1) b): two binary searches.
+__device__ __forceinline__ int drqn_first_at_least(const int32_t* a, const int n, const int64_t v) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if ((int64_t)a[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ void drqn_pop_run(const MzDrqnPopStore& q, const int p, int* lo,
+                                             int* hi) {
+  const int nfin = min(max(*q.s.fin_count, 0), q.s.B);
+  *lo = drqn_first_at_least(q.s.fin_id, nfin, (int64_t)p * q.b);
+  *hi = drqn_first_at_least(q.s.fin_id, nfin, (int64_t)(p + 1) * q.b);
+}
+
+// workgroups (., p): k_drqn_store's body on learner p's run and learner p's ring. A learner with
+// no finished episode writes nothing.
+__global__ __launch_bounds__(256) void k_drqn_pop_store(MzDrqnPopStore q) {
+  const int p = blockIdx.y;
+  int lo, hi;
+  drqn_pop_run(q, p, &lo, &hi);
+  if (hi <= lo) return;
+  MzDrqnStore s = q.s;
+  s.mem += (size_t)p * s.cap * (s.L + 1) * ROW;
+  s.mem_len += (size_t)p * s.cap;
+  s.mem_term += (size_t)p * s.cap;
+  s.ring += 2 * (size_t)p;
+  drqn_store_body(s, q.s.fin_id + lo, q.s.fin_len + lo, hi - lo, blockIdx.x, gridDim.x);
+}
+
+__global__ __launch_bounds__(WAVE) void k_drqn_pop_ring(MzDrqnPopStore q) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= q.P) return;
+  int lo, hi;
+  drqn_pop_run(q, p, &lo, &hi);
+  if (hi > lo) drqn_ring_advance(q.s.ring + 2 * (size_t)p, hi - lo, q.s.cap);
+}
+
 // E distinct slots, every E-subset of the filled slots equally likely (Floyd): for j = n - E .. n - 1
 // draw v uniform in [0, j]; take v unless already taken, else j. The draw is the high word of
 // u32 * (j + 1) (bias below 2^-32 (j + 1)). While count < capacity the filled slots are 0 ..
 // count - 1; afterwards all of them.
-__global__ __launch_bounds__(WAVE) void k_drqn_sample(MzDrqnSample q) {
-  extern __shared__ int32_t chosen[];  // [E]
+__device__ __forceinline__ void drqn_sample_body(const MzDrqnSample& q, int32_t* chosen) {
   const int lane = threadIdx.x;
   int64_t n64 = q.ring[1];
   if (n64 > q.cap) n64 = q.cap;
@@ -258,10 +360,31 @@ __global__ __launch_bounds__(WAVE) void k_drqn_sample(MzDrqnSample q) {
   }
 }
 
+__global__ __launch_bounds__(WAVE) void k_drqn_sample(MzDrqnSample q) {
+  extern __shared__ int32_t chosen[];  // [E]
+  drqn_sample_body(q, chosen);
+}
+
+// one wave per learner: k_drqn_sample's body on learner p's ring with its seed and update count
+__global__ __launch_bounds__(WAVE) void k_drqn_pop_sample(MzDrqnPopSample q) {
+  extern __shared__ int32_t chosen[];  // [E]
+  const int p = blockIdx.x;
+  if (q.due && q.due[p] == 0) return;
+  MzDrqnSample s = q.s;
+  s.seed = q.seed[p];
+  s.counter = q.counter[p];
+  s.ring += 2 * (size_t)p;
+  s.mem_len += (size_t)p * s.cap;
+  s.d_slot += (size_t)p * s.E;
+  s.d_len += (size_t)p * s.E;
+  s.d_off += (size_t)p * s.E;
+  s.d_tot += 2 * (size_t)p;
+  drqn_sample_body(s, chosen);
+}
+
 // ---- the sequence forward --------------------------------------------------------------------
-__global__ __launch_bounds__(WAVE) void k_drqn_seq_fwd(MzDrqnSeq q) {
+__device__ __forceinline__ void drqn_seq_fwd_body(const MzDrqnSeq& q, const int e) {
   __shared__ __attribute__((aligned(16))) float hs[H];
-  const int e = blockIdx.x;
   const int lane = threadIdx.x, u = lane & (H - 1), half = lane >> 5;
   const int n = q.d_len[e], slot = q.d_slot[e];
   const int64_t off = q.d_off[e];
@@ -354,10 +477,43 @@ __global__ __launch_bounds__(WAVE) void k_drqn_seq_fwd(MzDrqnSeq q) {
   if (!q.target && lane == 0) q.ep_loss[e] = sq;
 }
 
+__global__ __launch_bounds__(WAVE) void k_drqn_seq_fwd(MzDrqnSeq q) {
+  drqn_seq_fwd_body(q, blockIdx.x);
+}
+
+// learner p's view of a population's update: its parameters, ring, directory ([P][E]) and row
+// buffers ([P][E (L + 1)]), its discount factor
+__device__ __forceinline__ MzDrqnSeq drqn_seq_row(const MzDrqnPopSeq& q, const int p) {
+  MzDrqnSeq s = q.q;
+  const size_t E = (size_t)s.E, rows = E * (s.L + 1);
+  s.p = drqn_net_row(q.q.p, p);
+  if (q.gamma) s.gamma = q.gamma[p];
+  s.mem += (size_t)p * s.cap * (s.L + 1) * ROW;
+  if (s.mem_term) s.mem_term += (size_t)p * s.cap;
+  s.d_slot += p * E;
+  s.d_len += p * E;
+  s.d_off += p * E;
+  s.d_tot += 2 * (size_t)p;
+  if (s.qmax) s.qmax += p * rows;
+  if (s.stash) s.stash += p * rows * STASH;
+  if (s.qa) s.qa += p * rows;
+  if (s.y) s.y += p * rows;
+  if (s.d) s.d += p * rows;
+  if (s.ep_loss) s.ep_loss += p * E;
+  if (s.gpart) s.gpart += p * E * MZ_DRQN_PARAMS;
+  return s;
+}
+
+// one wave per (learner, episode); a learner that is not due exits at once
+__global__ __launch_bounds__(WAVE) void k_drqn_pop_seq_fwd(MzDrqnPopSeq q) {
+  const int p = blockIdx.x / q.q.E;
+  if (q.due && q.due[p] == 0) return;
+  drqn_seq_fwd_body(drqn_seq_row(q, p), blockIdx.x % q.q.E);
+}
+
 // ---- back-propagation through time -----------------------------------------------------------
-__global__ __launch_bounds__(WAVE) void k_drqn_seq_bwd(MzDrqnSeq q) {
+__device__ __forceinline__ void drqn_seq_bwd_body(const MzDrqnSeq& q, const int e) {
   __shared__ __attribute__((aligned(16))) float dzs[G4];
-  const int e = blockIdx.x;
   const int lane = threadIdx.x, u = lane & (H - 1), half = lane >> 5;
   const int n = q.d_len[e], slot = q.d_slot[e];
   const int64_t off = q.d_off[e];
@@ -479,11 +635,37 @@ __global__ __launch_bounds__(WAVE) void k_drqn_seq_bwd(MzDrqnSeq q) {
   }
 }
 
+__global__ __launch_bounds__(WAVE) void k_drqn_seq_bwd(MzDrqnSeq q) {
+  drqn_seq_bwd_body(q, blockIdx.x);
+}
+
+__global__ __launch_bounds__(WAVE) void k_drqn_pop_seq_bwd(MzDrqnPopSeq q) {
+  const int p = blockIdx.x / q.q.E;
+  if (q.due && q.due[p] == 0) return;
+  drqn_seq_bwd_body(drqn_seq_row(q, p), blockIdx.x % q.q.E);
+}
+
+// parameter k's partials summed over the episodes in index order (float64, rounded once)
+__device__ __forceinline__ float drqn_reduce_grad(const float* gpart, const int E, const int k) {
+  double s = 0.0;
+  for (int e = 0; e < E; ++e) s += (double)gpart[(size_t)e * MZ_DRQN_PARAMS + k];
+  return (float)s;
+}
+
+// the loss: the episodes' sums of squared residuals in episode order (float64) over the steps
+__device__ __forceinline__ float drqn_reduce_loss(const double* ep_loss, const int32_t* d_len,
+                                                  const int64_t* d_tot, const int E) {
+  double s = 0.0;
+  for (int e = 0; e < E; ++e)
+    if (d_len[e] > 0) s += ep_loss[e];
+  const int64_t steps = d_tot[1];
+  return steps > 0 ? (float)(s / (double)steps) : 0.0f;
+}
+
 __global__ __launch_bounds__(256) void k_drqn_reduce(MzDrqnReduce q) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k < MZ_DRQN_PARAMS) {
-    double s = 0.0;
-    for (int e = 0; e < q.E; ++e) s += (double)q.gpart[(size_t)e * MZ_DRQN_PARAMS + k];
+    const float s = drqn_reduce_grad(q.gpart, q.E, k);
     float* dst;
     int o;
     if (k < P_WHH) { dst = q.g[0]; o = k - P_WIH; }
@@ -492,15 +674,32 @@ __global__ __launch_bounds__(256) void k_drqn_reduce(MzDrqnReduce q) {
     else if (k < P_FCW) { dst = q.g[3]; o = k - P_BHH; }
     else if (k < P_FCB) { dst = q.g[4]; o = k - P_FCW; }
     else { dst = q.g[5]; o = k - P_FCB; }
-    dst[o] = (float)s;
+    dst[o] = s;
   }
-  if (k == 0) {
-    double s = 0.0;
-    for (int e = 0; e < q.E; ++e)
-      if (q.d_len[e] > 0) s += q.ep_loss[e];
-    const int64_t steps = q.d_tot[1];
-    *q.loss = steps > 0 ? (float)(s / (double)steps) : 0.0f;
-  }
+  if (k == 0) *q.loss = drqn_reduce_loss(q.ep_loss, q.d_len, q.d_tot, q.E);
+}
+
+// workgroups (., p): learner p's E partials into row p of the flat [P][5252] gradient (the flat
+// order is the partials' order), and its loss
+__global__ __launch_bounds__(256) void k_drqn_pop_reduce(MzDrqnPopReduce q) {
+  const int p = blockIdx.y;
+  if (q.due && q.due[p] == 0) return;
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t E = (size_t)q.E;
+  if (k < MZ_DRQN_PARAMS)
+    q.g[(size_t)p * MZ_DRQN_PARAMS + k] = drqn_reduce_grad(q.gpart + p * E * MZ_DRQN_PARAMS, q.E, k);
+  if (k == 0)
+    q.loss[p] = drqn_reduce_loss(q.ep_loss + p * E, q.d_len + p * E, q.d_tot + 2 * (size_t)p, q.E);
+}
+
+// the target sync of the learners flagged in mask: dst row <- src row
+__global__ __launch_bounds__(256) void k_drqn_pop_sync(const float* __restrict__ src,
+                                                       float* __restrict__ dst,
+                                                       const int32_t* __restrict__ mask) {
+  const int p = blockIdx.y;
+  if (mask[p] == 0) return;
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < MZ_DRQN_PARAMS) dst[(size_t)p * MZ_DRQN_PARAMS + k] = src[(size_t)p * MZ_DRQN_PARAMS + k];
 }
 
 }  // namespace
@@ -536,5 +735,50 @@ hipError_t mz_launch_drqn_seq_backward(const MzDrqnSeq& q, hipStream_t s) {
 
 hipError_t mz_launch_drqn_reduce(const MzDrqnReduce& q, hipStream_t s) {
   hipLaunchKernelGGL(k_drqn_reduce, dim3((MZ_DRQN_PARAMS + 255) / 256), dim3(256), 0, s, q);
+  return hipGetLastError();
+}
+
+// ---- populations ----------------------------------------------------------------------------
+hipError_t mz_launch_drqn_pop_act(const MzDrqnPopAct& q, hipStream_t s) {
+  const int bpl = (q.b + IPB - 1) / IPB;
+  hipLaunchKernelGGL(k_drqn_pop_act, dim3((unsigned)q.P * bpl), dim3(ACT_T), 0, s, q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_pop_store(const MzDrqnPopStore& q, hipStream_t s) {
+  const int blocks = q.b < 256 ? q.b : 256;
+  hipLaunchKernelGGL(k_drqn_pop_store, dim3(blocks, q.P), dim3(256), 0, s, q);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_drqn_pop_ring, dim3((q.P + WAVE - 1) / WAVE), dim3(WAVE), 0, s, q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_pop_sample(const MzDrqnPopSample& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_pop_sample, dim3(q.P), dim3(WAVE), (size_t)q.s.E * sizeof(int32_t), s,
+                     q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_pop_seq_forward(const MzDrqnPopSeq& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_pop_seq_fwd, dim3((unsigned)q.P * q.q.E), dim3(WAVE), 0, s, q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_pop_seq_backward(const MzDrqnPopSeq& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_pop_seq_bwd, dim3((unsigned)q.P * q.q.E), dim3(WAVE), 0, s, q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_pop_reduce(const MzDrqnPopReduce& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_pop_reduce, dim3((MZ_DRQN_PARAMS + 255) / 256, q.P), dim3(256), 0, s,
+                     q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_pop_sync(const float* src, float* dst, const int32_t* mask, int P,
+                                   hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_pop_sync, dim3((MZ_DRQN_PARAMS + 255) / 256, P), dim3(256), 0, s, src,
+                     dst, mask);
   return hipGetLastError();
 }

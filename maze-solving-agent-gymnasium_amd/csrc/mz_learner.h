@@ -203,6 +203,51 @@ hipError_t mz_launch_drqn_seq_forward(const MzDrqnSeq& q, hipStream_t s);
 hipError_t mz_launch_drqn_seq_backward(const MzDrqnSeq& q, hipStream_t s);
 hipError_t mz_launch_drqn_reduce(const MzDrqnReduce& q, hipStream_t s);
 
+// Populations: P independent learners over B = P b instances, learner p owning the block
+// [p b, (p + 1) b). Parameters, gradients and moments are flat [P][MZ_DRQN_PARAMS] f32, a row in
+// state_dict order. Each struct holds learner 0's single-learner view; the kernels move it to
+// learner p's rows. due: [P], 0 = the learner sits the update out (null: all due).
+inline MzDrqnNet mz_drqn_flat_net(const float* f) {  // the six tensors of one flat row
+  return MzDrqnNet{f, f + 768, f + 768 + 4096, f + 768 + 4096 + 128, f + 768 + 4096 + 256,
+                   f + 768 + 4096 + 256 + 128};
+}
+struct MzDrqnPopAct {
+  MzDrqnAct a;                               // a.B = P b (the pitch of h / c); a.eps, a.seed unused
+  int P, b;
+  const float* eps; const uint64_t* seed;    // [P]
+};
+struct MzDrqnPopStore {
+  MzDrqnStore s;                             // s.B = P b; mem [P][cap][L + 1][8], ring [P][2]
+  int P, b;
+};
+struct MzDrqnPopSample {
+  MzDrqnSample s;                            // directory [P][E], d_tot [P][2]; s.seed, s.counter unused
+  int P;
+  const uint64_t* seed; const uint64_t* counter; const int32_t* due;  // [P]
+};
+struct MzDrqnPopSeq {
+  MzDrqnSeq q;                               // row buffers [P][E (L + 1)], gpart [P][E][5252]
+  int P;
+  const float* gamma; const int32_t* due;    // [P]
+};
+struct MzDrqnPopReduce {
+  int P, E; const float* gpart; const double* ep_loss; const int32_t* d_len; const int64_t* d_tot;
+  float* g; float* loss; const int32_t* due; // flat gradient [P][5252], [P], [P]
+};
+hipError_t mz_launch_drqn_pop_act(const MzDrqnPopAct& q, hipStream_t s);
+hipError_t mz_launch_drqn_pop_store(const MzDrqnPopStore& q, hipStream_t s);
+hipError_t mz_launch_drqn_pop_sample(const MzDrqnPopSample& q, hipStream_t s);
+hipError_t mz_launch_drqn_pop_seq_forward(const MzDrqnPopSeq& q, hipStream_t s);
+hipError_t mz_launch_drqn_pop_seq_backward(const MzDrqnPopSeq& q, hipStream_t s);
+hipError_t mz_launch_drqn_pop_reduce(const MzDrqnPopReduce& q, hipStream_t s);
+hipError_t mz_launch_drqn_pop_sync(const float* src, float* dst, const int32_t* mask, int P,
+                                   hipStream_t s);
+// mz_optim.hip: k_adamw's element arithmetic over [P][n] rows with per-learner lr / step / due
+hipError_t mz_launch_adamw_pop(float* p, float* m, float* v, float* g, int P, int64_t n,
+                               const float* lr, float* step, const int32_t* due, double b1,
+                               double b2, double eps, double wd, float clamp, float gscale,
+                               int write_grad, hipStream_t s);
+
 // ---- f32-accurate acting forward on the bf16 MFMA (mz_qact.hip) ------------------------------
 struct MzQAct {
   const uint32_t* bits; const float* obs6;   // [B][22], [B][6] (instance rows)

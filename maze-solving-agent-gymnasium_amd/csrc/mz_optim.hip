@@ -52,21 +52,58 @@ struct Segs {
 
 __global__ void k_step_publish(float* step) { step[0] = step[0] + 1.0f; }
 
+// the per-step scalars as torch's eager AdamW forms them (Python doubles, then f32 operands)
+struct AdamStep {
+  float step_size, bc2_sqrt, decay, w1, b2f, w2, eps;
+};
+
+__device__ __forceinline__ AdamStep adam_step(const double lr, const float step0, const double b1,
+                                              const double b2, const double eps_d,
+                                              const double wd) {
+  const float t_next = step0 + 1.0f;
+  const double t = (double)t_next;
+  const double bc1 = 1.0 - pow(b1, t);
+  AdamStep a;
+  a.step_size = (float)(lr / bc1);
+  a.bc2_sqrt = (float)sqrt(1.0 - pow(b2, t));
+  a.decay = (float)(1.0 - lr * wd);
+  a.w1 = (float)(1.0 - b1);
+  a.b2f = (float)b2;
+  a.w2 = (float)(1.0 - b2);
+  a.eps = (float)eps_d;
+  return a;
+}
+
+// four elements' clamp + AdamW, shared by k_adamw and k_adamw_pop (g4 leaves clamped)
+__device__ __forceinline__ void adam_elem4(const AdamStep& a, const float clamp, const float gscale,
+                                           float4& g4, float4& p4, float4& m4, float4& v4) {
+  float* gs = &g4.x;
+  float* ps = &p4.x;
+  float* ms = &m4.x;
+  float* vs = &v4.x;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float g = gs[j] * gscale;
+    g = g < -clamp ? -clamp : (g > clamp ? clamp : g);
+    gs[j] = g;
+    float pj = ps[j] * a.decay;
+    float mj = ms[j] + a.w1 * (g - ms[j]);
+    float vj = vs[j] * a.b2f + a.w2 * (g * g);
+    const float denom = sqrtf(vj) / a.bc2_sqrt + a.eps;
+    pj = pj - a.step_size * (mj / denom);
+    ps[j] = pj;
+    ms[j] = mj;
+    vs[j] = vj;
+  }
+}
+
 __global__ __launch_bounds__(MZ_ADAMW_TPB) void k_adamw(float* __restrict__ p, float* __restrict__ m,
                                                float* __restrict__ v, Segs segs,
                                                const float* __restrict__ lr_dev,
                                                const float* step_dev, double b1,
                                                double b2, double eps_d, double wd, float clamp,
                                                float gscale, int write_grad) {
-  // the per-step scalars as torch's eager AdamW forms them (Python doubles, then f32 operands)
-  const double lr = (double)*lr_dev;
-  const float t_next = step_dev[0] + 1.0f;
-  const double t = (double)t_next;
-  const double bc1 = 1.0 - pow(b1, t);
-  const float step_size = (float)(lr / bc1);
-  const float bc2_sqrt = (float)sqrt(1.0 - pow(b2, t));
-  const float decay = (float)(1.0 - lr * wd);
-  const float w1 = (float)(1.0 - b1), b2f = (float)b2, w2 = (float)(1.0 - b2), eps = (float)eps_d;
+  const AdamStep a = adam_step((double)*lr_dev, step_dev[0], b1, b2, eps_d, wd);
   const int64_t n4 = segs.off[segs.n] >> 2;  // every segment length is a multiple of 4
   for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n4;
        q += (int64_t)gridDim.x * blockDim.x) {
@@ -78,29 +115,45 @@ __global__ __launch_bounds__(MZ_ADAMW_TPB) void k_adamw(float* __restrict__ p, f
     float4 p4 = reinterpret_cast<float4*>(p)[q];
     float4 m4 = reinterpret_cast<float4*>(m)[q];
     float4 v4 = reinterpret_cast<float4*>(v)[q];
-    float* gs = &g4.x;
-    float* ps = &p4.x;
-    float* ms = &m4.x;
-    float* vs = &v4.x;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float g = gs[j] * gscale;
-      g = g < -clamp ? -clamp : (g > clamp ? clamp : g);
-      gs[j] = g;
-      float pj = ps[j] * decay;
-      float mj = ms[j] + w1 * (g - ms[j]);
-      float vj = vs[j] * b2f + w2 * (g * g);
-      const float denom = sqrtf(vj) / bc2_sqrt + eps;
-      pj = pj - step_size * (mj / denom);
-      ps[j] = pj;
-      ms[j] = mj;
-      vs[j] = vj;
-    }
+    adam_elem4(a, clamp, gscale, g4, p4, m4, v4);
     reinterpret_cast<float4*>(p)[q] = p4;
     reinterpret_cast<float4*>(m)[q] = m4;
     reinterpret_cast<float4*>(v)[q] = v4;
     if (write_grad) *gp = g4;  // the clamped gradient stays visible, as with clamp_ in place
   }
+}
+
+// ---- a population's step: rows [P][n] (n a multiple of 4, 16-B aligned rows), learner p at its
+// own lr[p] and step count step[p]; a learner with due[p] == 0 has nothing written. Workgroups
+// (., p) cover row p; k_step_publish_pop advances the due learners' counts behind it.
+__global__ __launch_bounds__(256) void k_adamw_pop(float* __restrict__ p, float* __restrict__ m,
+                                                   float* __restrict__ v, float* __restrict__ g,
+                                                   int64_t n, const float* __restrict__ lr_dev,
+                                                   const float* step_dev,
+                                                   const int32_t* __restrict__ due, double b1,
+                                                   double b2, double eps_d, double wd, float clamp,
+                                                   float gscale, int write_grad) {
+  const int r = blockIdx.y;
+  if (due && due[r] == 0) return;
+  const AdamStep a = adam_step((double)lr_dev[r], step_dev[r], b1, b2, eps_d, wd);
+  const int64_t n4 = n >> 2, base = (int64_t)r * n4;
+  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n4;
+       q += (int64_t)gridDim.x * blockDim.x) {
+    float4 g4 = reinterpret_cast<float4*>(g)[base + q];
+    float4 p4 = reinterpret_cast<float4*>(p)[base + q];
+    float4 m4 = reinterpret_cast<float4*>(m)[base + q];
+    float4 v4 = reinterpret_cast<float4*>(v)[base + q];
+    adam_elem4(a, clamp, gscale, g4, p4, m4, v4);
+    reinterpret_cast<float4*>(p)[base + q] = p4;
+    reinterpret_cast<float4*>(m)[base + q] = m4;
+    reinterpret_cast<float4*>(v)[base + q] = v4;
+    if (write_grad) reinterpret_cast<float4*>(g)[base + q] = g4;
+  }
+}
+
+__global__ void k_step_publish_pop(float* step, const int32_t* due, int P) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < P && (!due || due[r] != 0)) step[r] = step[r] + 1.0f;
 }
 
 // ---- PPO's optimizer step (ppo_agent.py:232-236): clip_grad_norm_(params, 0.5), then AdamW
@@ -226,6 +279,20 @@ hipError_t mz_launch_adamw_groups(float* p, float* m, float* v, const float* con
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(k_adamw_groups, dim3(blocks), dim3(256), 0, s, p, m, v, sg, lr, step, coef, b1,
                      b2, eps, wd);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_adamw_pop(float* p, float* m, float* v, float* g, int P, int64_t n,
+                               const float* lr, float* step, const int32_t* due, double b1,
+                               double b2, double eps, double wd, float clamp, float gscale,
+                               int write_grad, hipStream_t s) {
+  const int64_t n4 = n >> 2;
+  int blocks = (int)((n4 + 255) / 256);
+  if (blocks > 64) blocks = 64;  // grid-stride beyond
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(k_adamw_pop, dim3(blocks, P), dim3(256), 0, s, p, m, v, g, n, lr, step, due,
+                     b1, b2, eps, wd, clamp, gscale, write_grad);
+  hipLaunchKernelGGL(k_step_publish_pop, dim3((P + 63) / 64), dim3(64), 0, s, step, due, P);
   return hipGetLastError();
 }
 

@@ -51,7 +51,9 @@ EXPORTS = ["mz_last_error", "mz_device_count", "mz_create", "mz_destroy", "mz_lo
            "mz_head_loss_backward_workspace_floats", "mz_adamw_groups",
            "mz_ppo_act", "mz_ppo_scan", "mz_ppo_finish", "mz_ppo_head_loss", "mz_rf_act", "mz_rf_finish",
            "mz_rf_head_loss", "mz_drqn_act", "mz_drqn_store", "mz_drqn_sample",
-           "mz_drqn_seq_forward", "mz_drqn_seq_backward", "mz_qact_prepare", "mz_qact",
+           "mz_drqn_seq_forward", "mz_drqn_seq_backward", "mz_drqn_pop_act", "mz_drqn_pop_store",
+           "mz_drqn_pop_sample", "mz_drqn_pop_seq_forward", "mz_drqn_pop_seq_backward",
+           "mz_drqn_pop_sync", "mz_adamw_pop", "mz_qact_prepare", "mz_qact",
            "mz_qact_workspace_floats", "mz_qtab_states", "mz_qtab_act", "mz_qtab_update",
            "mz_qtab_hash_act", "mz_qtab_hash_update", "mz_qtab_hash_rehash", "mz_qtab_hash_lookup",
            "mz_dqtab_act", "mz_dqtab_update", "mz_dqtab_hash_act", "mz_dqtab_hash_update",
@@ -192,6 +194,20 @@ def load(build_if_missing=True):
     L.mz_drqn_seq_forward.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
                                       C.c_float] + [vp] * 13
     L.mz_drqn_seq_backward.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64] + [vp] * 12
+    L.mz_drqn_pop_act.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, vp, C.c_int32,
+                                  vp, C.c_uint64] + [vp] * 8
+    L.mz_drqn_pop_store.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32] + [vp] * 6 + \
+        [C.c_int64] + [vp] * 5
+    L.mz_drqn_pop_sample.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                     C.c_int64] + [vp] * 7
+    L.mz_drqn_pop_seq_forward.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_int64] + [vp] * 15
+    L.mz_drqn_pop_seq_backward.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_int64] + [vp] * 13
+    L.mz_drqn_pop_sync.argtypes = [vp, vp, vp, C.c_int32, vp]
+    L.mz_adamw_pop.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int64, vp, vp, vp, C.c_double,
+                               C.c_double, C.c_double, C.c_double, C.c_float, C.c_float,
+                               C.c_int32, vp]
     L.mz_qact_prepare.argtypes = [vp] * 7
     L.mz_qact.argtypes = [vp, vp, vp, vp, C.c_int32] + [vp] * 10 + [C.c_int32, C.c_float,
                                                                    C.c_uint64, C.c_uint64] + [vp] * 4

@@ -7,6 +7,14 @@ The reference has no trainer for this agent; the semantics are VectorRecurrentDQ
 (trainers/drqn_trainer.py, six stated departures). Prints one JSON line with the training
 throughput and the greedy win-rate on fresh mazes before and after training, under the same
 evaluation seed.
+
+  python -m mazerl.train_lstm_dqn --envs 4096 --dim 9 --learners 8 --seeds 0,1,2,3,4,5,6,7
+  python -m mazerl.train_lstm_dqn --learners 4 --sweep lr=1e-3,3e-4,1e-4,3e-5 --sweep gamma=0.99
+
+--learners P trains P independent learners in one run (trainers/drqn_population.py), each on
+envs / P instances; --seeds and --sweep NAME=v1,v2,... (repeatable; NAME one of lr, gamma,
+eps-start, eps-final, eps-decay, target-update, seed; P values or one) set them apart. The final
+line then reports every learner's trained greedy win-rate on the same mazes, their mean and spread.
 """
 import argparse
 import json
@@ -17,7 +25,50 @@ from .trainers.drqn_trainer import VectorRecurrentDQNTrainer, evaluate_plain
 from .vector_env import VectorMazeEnv
 
 
-def main(argv=None):
+# --sweep names -> (the constructor's argument, the value type)
+SWEEPABLE = {"lr": ("lr", float), "gamma": ("discount_factor", float),
+             "eps-start": ("starting_epsilon", float), "eps-final": ("final_epsilon", float),
+             "eps-decay": ("epsilon_decay", float), "target-update": ("target_update_frequency", int),
+             "seed": ("seed", int)}
+
+
+def parse_sweeps(sweeps, seeds, P):
+    """--sweep NAME=v1,v2,... and --seeds s1,... -> {constructor argument: list of P values}.
+    Each list has P values or one (then every learner gets it)."""
+    out = {}
+    items = list(sweeps or [])
+    if seeds is not None:
+        items.append("seed=" + seeds)
+    for item in items:
+        name, eq, vals = item.partition("=")
+        name = name.strip().replace("_", "-")
+        if not eq or name not in SWEEPABLE:
+            raise ValueError(f"--sweep {item!r}: NAME=v1,v2,... with NAME one of "
+                             f"{', '.join(SWEEPABLE)}")
+        arg, kind = SWEEPABLE[name]
+        if arg in out:
+            raise ValueError(f"--sweep {name} given twice")
+        try:
+            vs = [kind(v) for v in vals.split(",")]
+        except ValueError:
+            raise ValueError(f"--sweep {item!r}: values must be {kind.__name__}s") from None
+        if len(vs) == 1:
+            vs = vs * P
+        if len(vs) != P:
+            raise ValueError(f"--sweep {name}: {len(vs)} values for {P} learners")
+        out[arg] = vs
+    return out
+
+
+def spread(rates):
+    """Mean, sample standard deviation (0 for one value), min and max of the learners' rates."""
+    n = len(rates)
+    mean = sum(rates) / n
+    sd = (sum((r - mean) ** 2 for r in rates) / (n - 1)) ** 0.5 if n > 1 else 0.0
+    return {"mean": mean, "std": sd, "min": min(rates), "max": max(rates)}
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--dim", type=int, default=9)
@@ -40,7 +91,67 @@ def main(argv=None):
     ap.add_argument("--no-bank", action="store_true")
     ap.add_argument("--resume", default=None, help="checkpoint to continue from")
     ap.add_argument("--save", default=None, help="checkpoint written after training")
+    ap.add_argument("--learners", type=int, default=None,
+                    help="P independent learners in one run, each on envs / P instances")
+    ap.add_argument("--sweep", action="append", default=None, metavar="NAME=v1,v2,...",
+                    help="per-learner values (P or one) of lr, gamma, eps-start, eps-final, "
+                         "eps-decay, target-update or seed; repeatable")
+    ap.add_argument("--seeds", default=None, metavar="s1,s2,...", help="--sweep seed=...")
     a = ap.parse_args(argv)
+    if a.learners is None:
+        if a.sweep or a.seeds:
+            ap.error("--sweep / --seeds need --learners")
+        a.per_learner = None
+        return a
+    if a.learners < 1 or a.envs % a.learners:
+        ap.error("--envs must be a multiple of --learners >= 1")
+    try:
+        a.per_learner = parse_sweeps(a.sweep, a.seeds, a.learners)
+    except ValueError as e:
+        ap.error(str(e))
+    return a
+
+
+def main_population(a):
+    from .trainers.drqn_population import VectorRecurrentDQNPopulation
+    dev = torch.device("cuda", torch.cuda.current_device())
+    env = VectorMazeEnv(a.envs, a.dim, toroidal=a.toroidal, enrich=False, device=dev,
+                        algorithm=a.algo, seed=0x5EED0000, pos=False, done_list=False)
+    kw = dict(lr=a.lr, starting_epsilon=a.eps_start, final_epsilon=a.eps_final,
+              epsilon_decay=a.eps_decay, discount_factor=a.gamma,
+              target_update_frequency=a.target_update, seed=a.seed)
+    kw.update(a.per_learner)
+    tr = VectorRecurrentDQNPopulation(
+        env, dev, learners=a.learners, batch_size=a.batch, memory_size=a.memory,
+        explore_actions=a.explore_actions, train_every=a.train_every, bank=not a.no_bank,
+        algorithm=a.algo, **kw)
+    if a.resume:
+        from .checkpoint import load_checkpoint
+        load_checkpoint(a.resume, tr)
+    ev = dict(algorithm=a.algo, seed=0x7E570000, toroidal=a.toroidal)
+    before = tr.evaluate_all(a.eval_mazes, a.dim, **ev)
+    secs = tr.train(a.steps, log_every=500, log=lambda r: print(json.dumps(r), flush=True))
+    if a.save:
+        from .checkpoint import save_checkpoint
+        save_checkpoint(a.save, tr)
+    after = tr.evaluate_all(a.eval_mazes, a.dim, **ev)
+    print(json.dumps({"config": "lstm-dqn population " + ("toroidal" if a.toroidal else "euclidean"),
+                      "envs": a.envs, "learners": a.learners, "dim": a.dim,
+                      "vector_steps": a.steps, "train_seconds": secs,
+                      "train_env_steps_per_s": a.envs * a.steps / secs, "episodes": tr.episodes,
+                      "wins": tr.wins, "updates": tr.updates, "batch_episodes": a.batch,
+                      "per_learner": {k: v for k, v in a.per_learner.items()},
+                      "replay_bytes": tr.memory_bytes()["replay"],
+                      "win_rate_greedy_untrained": before, "win_rate_greedy": after,
+                      "win_rate_greedy_spread": spread(after), "eval_mazes": a.eval_mazes}),
+          flush=True)
+    env.close()
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    if a.learners is not None:
+        return main_population(a)
     dev = torch.device("cuda", torch.cuda.current_device())
     env = VectorMazeEnv(a.envs, a.dim, toroidal=a.toroidal, enrich=False, device=dev,
                         algorithm=a.algo, seed=0x5EED0000, pos=False, done_list=False)

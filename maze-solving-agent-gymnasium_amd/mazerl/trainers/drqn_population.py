@@ -1,0 +1,404 @@
+"""Populations of recurrent DQN learners: P independent VectorRecurrentDQNTrainers advanced by the
+same launches (csrc/mz_drqn.hip k_drqn_pop_*, csrc/mz_optim.hip k_adamw_pop), so P seeds or P
+hyper-parameter settings of agents/lstm_dqn_agent.py cost about one run's launches.
+
+A population is P learners over B = P b instances; learner p owns the block [p b, (p + 1) b).
+Shared: the env, L = episode_bound, batch_size E, memory_size (capacity, in episodes),
+train_every, explore_actions. Per learner (a scalar or a length-P sequence): lr, discount_factor,
+starting_epsilon, final_epsilon, epsilon_decay, target_update_frequency, seed.
+
+Learner p is, by definition and bit for bit, what VectorRecurrentDQNTrainer (drqn_trainer.py: its
+six departures, its accumulation order, Philox streams and ring semantics) would be on its b
+instances with its hyper-parameters and seed: the population kernels run the single-learner
+device code on learner p's rows. The acting draw of instance i is keyed by (seed_p, counter,
+i - p b), the sample by (seed_p, updates_p); P = 1 is that trainer.
+
+Layout. Parameters, gradients and AdamW moments are flat [P][5252] f32, a row in state_dict order;
+h, c stay [32][B]; the replay memory is [P][capacity][L + 1][8] words with mem_len / mem_term
+[P][capacity] and an int64 ring [P][2] (head, count); an update's directory is [P][E] and its row
+buffers [P][E (L + 1)].
+
+The learners never couple on the device: each has its own ring, nets, moments and step count, its
+own eps clock steps_done[p] and its own update count updates[p] (its cosine schedule and target
+sync). A learner starts updating at the first vector step at which its own ring holds >= E
+episodes. The host reads the P ring counts once per vector step only until every learner has its
+first batch; from then on it knows every updates[p], uploads the per-update scalars (lr[p] from
+cosine_lr in float64 as the single trainer, the due mask, the sync mask, the sample counters) as
+one small array, and a vector step makes no device -> host read (beyond the single trainer's look
+at the overflow counter every 256 updates).
+
+curriculum="global" counts wins across all instances and would couple the learners: it is refused.
+With bank=False a learner's whole run is independent of the other learners, bit for bit. With the
+winner bank the maze a winner receives depends on how many instances of other learners won before
+it, so the learners then share the stream of replacement mazes.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from .. import _native as N
+from ..agents.lstm_dqn_agent import DQN, ETA_MIN, HIDDEN, T_MAX, epsilon_at
+from ..agents.rf_agent import cosine_lr
+from .drqn_trainer import EVAL_KEY, PARAMS, ROW, STASH, U64, _Evaluator
+from .episodic import EpisodicTrainer, episode_bound
+
+FORMAT = "mazerl.VectorRecurrentDQNPopulation/1"
+KEYS = ("lstm_cell.weight_ih", "lstm_cell.weight_hh", "lstm_cell.bias_ih", "lstm_cell.bias_hh",
+        "fc.weight", "fc.bias")
+SHAPES = ((128, 6), (128, 32), (128,), (128,), (4, 32), (4,))
+PER_LEARNER = ("lr", "discount_factor", "starting_epsilon", "final_epsilon", "epsilon_decay",
+               "target_update_frequency", "seed")
+BETAS, ADAM_EPS, WEIGHT_DECAY, CLAMP = (0.9, 0.999), 1e-8, 1e-2, 1.0
+
+
+def per_learner(value, P, name, kind=float):
+    """A scalar for all learners or one value per learner -> a list of P."""
+    if isinstance(value, (list, tuple, np.ndarray)):
+        vals = [kind(v) for v in value]
+        if len(vals) == 1:
+            vals = vals * P
+        if len(vals) != P:
+            raise ValueError(f"{name}: {len(vals)} values for {P} learners")
+        return vals
+    return [kind(value)] * P
+
+
+def _signed(u):
+    """A 64-bit key as the int64 torch stores."""
+    u &= U64
+    return u - (1 << 64) if u >> 63 else u
+
+
+def footprint(P, B, L, E, capacity):
+    """Bytes of the replay rings, the in-flight records, and an update's stash and row buffers."""
+    rows = E * (L + 1)
+    ring = P * capacity * ((L + 1) * ROW * 4 + 8)
+    records = B * ((L + 1) * 6 * 4 + L * 4 + L * 8)
+    update = P * (rows * (STASH + 4) * 4 + E * (PARAMS * 4 + 8 + 16))
+    return {"replay": ring, "records": records, "update": update,
+            "total": ring + records + update}
+
+
+class _LearnerView:
+    """What drqn_trainer._Evaluator reads of a trainer, for one learner of a population."""
+
+    def __init__(self, pop, p):
+        self.lib, self.explore_actions, self.seed = pop.lib, pop.explore_actions, pop.seed[p]
+        self._rows = pop.src  # keeps the buffer alive
+        base, off = pop.src[p].data_ptr(), 0
+        ptrs = []
+        for s in SHAPES:
+            ptrs.append(base + 4 * off)
+            off += int(np.prod(s))
+        self._ps = (C.c_void_p * 6)(*ptrs)
+
+
+class VectorRecurrentDQNPopulation(EpisodicTrainer):
+    _FORMAT = FORMAT
+    _SHAPE = ("L", "capacity", "P")
+    _REC = ("rec_x", "rec_a", "rec_r")
+    _COUNTERS = ("counter", "launches")
+
+    def __init__(self, env, device, learners=1, lr=1e-3, starting_epsilon=0.9, final_epsilon=0.05,
+                 epsilon_decay=1000.0, discount_factor=0.99, batch_size=32, memory_size=20000,
+                 target_update_frequency=10, explore_actions=4, train_every=1, seed=0, bank=True,
+                 curriculum=False, growth=None, algorithm="r-prim", bank_candidates=1):
+        P = int(learners)
+        if P < 1 or env.num_envs % P:
+            raise ValueError(f"env.num_envs {env.num_envs} must be a multiple of learners {P} >= 1")
+        if curriculum is True or curriculum == "global":
+            raise ValueError('curriculum="global" counts wins across all instances and would '
+                             'couple the learners; use False or "per-instance"')
+        self.tuf = per_learner(target_update_frequency, P, "target_update_frequency", int)
+        if batch_size < 1 or memory_size < batch_size or train_every < 1 or min(self.tuf) < 1 or \
+                explore_actions not in (1, 2, 3, 4):
+            raise ValueError("batch_size >= 1, memory_size >= batch_size, train_every >= 1, "
+                             "target_update_frequency >= 1, explore_actions in 1..4")
+        self.P, self.b = P, env.num_envs // P
+        self.lr = per_learner(lr, P, "lr")
+        self.gamma = per_learner(discount_factor, P, "discount_factor")
+        self.starting_epsilon = per_learner(starting_epsilon, P, "starting_epsilon")
+        self.final_epsilon = per_learner(final_epsilon, P, "final_epsilon")
+        self.epsilon_decay = per_learner(epsilon_decay, P, "epsilon_decay")
+        self.seed = per_learner(seed, P, "seed", int)
+        self.batch_size, self.capacity = int(batch_size), int(memory_size)
+        self.explore_actions, self.train_every = int(explore_actions), int(train_every)
+        B, E = env.num_envs, self.batch_size
+        L = episode_bound(env.max_dim, env.toroidal)
+        need = footprint(P, B, L, E, self.capacity)
+        dev = torch.device(device)
+        if dev.type == "cuda":
+            free, _ = torch.cuda.mem_get_info(dev)
+            if need["total"] > free:
+                raise MemoryError(
+                    f"{P} learners x {self.capacity} episodes of {L + 1} rows need "
+                    f"{need['replay'] / 2 ** 30:.2f} GiB of replay memory and "
+                    f"{need['total'] / 2 ** 30:.2f} GiB in all; {free / 2 ** 30:.2f} GiB are free. "
+                    "Lower memory_size or learners.")
+        super().__init__(env, device, bank=bank, curriculum=curriculum, growth=growth,
+                         algorithm=algorithm, bank_candidates=bank_candidates)
+        kw = dict(device=self.device)
+        i32, i64, f32 = torch.int32, torch.int64, torch.float32
+        self.src = torch.zeros(P, PARAMS, dtype=f32, **kw)
+        for p in range(P):  # learner p's initial net: the single trainer's under its seed
+            torch.manual_seed(self.seed[p])
+            net = DQN(6, 4, HIDDEN, self.device)
+            DQN(6, 4, HIDDEN, self.device)  # (the single trainer's target net: the same draws)
+            self.load_learner(p, net.state_dict())
+        self.tgt = self.src.clone()
+        self.grad = torch.zeros_like(self.src)
+        self.exp_avg = torch.zeros_like(self.src)
+        self.exp_avg_sq = torch.zeros_like(self.src)
+        self.step = torch.zeros(P, dtype=f32, **kw)  # the optimizer's step counts
+        self.steps_done = [0] * P  # the eps clocks
+        self.counter = 0           # vector steps (the exploration draws' counter)
+        self.launches = 0          # update launches (the overflow look's clock)
+        self.updates = [0] * P
+        self.filled = [0] * P      # the host's lower bounds of the rings' counts
+        self.gamma_dev = torch.tensor(self.gamma, dtype=f32, **kw)
+        self.seed_dev = torch.tensor([_signed(s) for s in self.seed], dtype=i64, **kw)
+        self.eps_dev = torch.zeros(P, dtype=f32, **kw)
+        # the per-update scalars, one upload: sample counters (int64), due, sync, lr (f32 bits)
+        self.upd = torch.zeros(5 * P, dtype=i32, **kw)
+        self.cnt_dev = self.upd[:2 * P].view(i64)
+        self.due_dev, self.sync_dev = self.upd[2 * P:3 * P], self.upd[3 * P:4 * P]
+        self.lr_dev = self.upd[4 * P:].view(f32)
+        self.h = torch.zeros(HIDDEN, B, dtype=f32, **kw)
+        self.c = torch.zeros(HIDDEN, B, dtype=f32, **kw)
+        self.rec_x = torch.zeros(B, L + 1, 6, dtype=f32, **kw)
+        self.rec_a = torch.zeros(B, L, dtype=i32, **kw)
+        self.rec_r = torch.zeros(B, L, dtype=torch.float64, **kw)
+        self.r64 = torch.zeros(B, dtype=torch.float64, **kw)
+        self.pool = torch.zeros(2, dtype=i64, **kw)  # mz_ppo_scan's row counters (unused here)
+        self.mem = torch.zeros(P, self.capacity, L + 1, ROW, dtype=i32, **kw)
+        self.mem_len = torch.zeros(P, self.capacity, dtype=i32, **kw)
+        self.mem_term = torch.zeros(P, self.capacity, dtype=i32, **kw)
+        self.ring = torch.zeros(P, 2, dtype=i64, **kw)  # head, count
+        rows = E * (L + 1)
+        self.d_slot = torch.zeros(P, E, dtype=i32, **kw)
+        self.d_len = torch.zeros(P, E, dtype=i32, **kw)
+        self.d_off = torch.zeros(P, E, dtype=i64, **kw)
+        self.d_tot = torch.zeros(P, 2, dtype=i64, **kw)
+        self.qmax = torch.zeros(P, rows, dtype=f32, **kw)
+        self.stash = torch.zeros(P, rows, STASH, dtype=f32, **kw)
+        self.qa = torch.zeros(P, rows, dtype=f32, **kw)
+        self.y = torch.zeros(P, rows, dtype=f32, **kw)
+        self.d = torch.zeros(P, rows, dtype=f32, **kw)
+        self.ep_loss = torch.zeros(P, E, dtype=torch.float64, **kw)
+        self.gpart = torch.zeros(P, E, PARAMS, dtype=f32, **kw)
+        self.loss = torch.zeros(P, dtype=f32, **kw)
+        self.last_lr = [None] * P
+        self.last_due = [False] * P  # the learners the last vector step updated
+
+    # ---- per-learner access -------------------------------------------------------------------
+    def memory_bytes(self):
+        """The replay, record, stash and row-buffer footprint in bytes (footprint())."""
+        return footprint(self.P, self.env.num_envs, self.L, self.batch_size, self.capacity)
+
+    def epsilon(self, p):
+        return epsilon_at(self.steps_done[p], self.starting_epsilon[p], self.final_epsilon[p],
+                          self.epsilon_decay[p])
+
+    def update_steps_done(self, p=None):
+        for k in range(self.P) if p is None else (int(p),):
+            self.steps_done[k] = self.steps_done[k] // 2
+
+    def learner_state_dict(self, p):
+        """Learner p's source net as the state_dict agents/lstm_dqn_agent.DQN and the reference's
+        DQN load."""
+        row, off, sd = self.src[int(p)], 0, {}
+        for k, s in zip(KEYS, SHAPES):
+            n = int(np.prod(s))
+            sd[k] = row[off:off + n].view(s).clone()
+            off += n
+        return sd
+
+    def load_learner(self, p, state_dict):
+        """Learner p's source net from a DQN state_dict (its target net follows at its next sync)."""
+        row = torch.cat([state_dict[k].detach().to(self.device, torch.float32).reshape(-1)
+                         for k in KEYS])
+        if row.numel() != PARAMS:
+            raise ValueError("not an LSTMCell(6, 32) + Linear(32, 4) state_dict")
+        self.src[int(p)].copy_(row)
+
+    def evaluator(self, p):
+        """Learner p as a learner for vector_trainer.evaluate / evaluate_plain (greedy actions
+        from a per-row (h, c) that starts at zero)."""
+        return _Evaluator(_LearnerView(self, int(p)))
+
+    def evaluate_all(self, num_mazes, dim, algorithm="r-prim", seed=0x7E57, toroidal=False):
+        """The P greedy win-rates from one rollout of P num_mazes rows on a plain env: every
+        learner plays the same num_mazes fresh mazes (those evaluate_plain plays under this seed)
+        through the population act in evaluation mode."""
+        from ..vector_env import VectorMazeEnv
+        P, n = self.P, int(num_mazes)
+        env = VectorMazeEnv(P * n, dim, toroidal=toroidal, enrich=False, device=self.device,
+                            algorithm=algorithm, seed=seed, pos=False, done_list=False,
+                            generate=False)
+        for p in range(P):  # an instance's maze is keyed by seed + its index
+            ids = torch.arange(p * n, (p + 1) * n, dtype=torch.int32, device=self.device)
+            env.generate(env_ids=ids, algorithm=algorithm, seed=(seed - p * n) & U64)
+        env.reset()
+        kw = dict(device=self.device)
+        h = torch.zeros(HIDDEN, P * n, dtype=torch.float32, **kw)
+        c = torch.zeros_like(h)
+        t = torch.zeros(P * n, dtype=torch.int32, **kw)
+        acts = torch.zeros(P * n, dtype=torch.int32, **kw)
+        eps = torch.zeros(P, dtype=torch.float32, **kw)
+        seeds = torch.tensor([_signed(s ^ EVAL_KEY) for s in self.seed], dtype=torch.int64, **kw)
+        finished = torch.zeros(P * n, dtype=torch.bool, **kw)
+        won = torch.zeros(P * n, dtype=torch.bool, **kw)
+        limit = episode_bound(dim, toroidal) + 1
+        k = 0
+        while k < limit:
+            N.check(self.lib.mz_drqn_pop_act(
+                self.src.data_ptr(), HIDDEN, P, n, env.obs6.data_ptr(), 0, eps.data_ptr(),
+                self.explore_actions, seeds.data_ptr(), k, t.data_ptr(), h.data_ptr(),
+                c.data_ptr(), None, None, acts.data_ptr(), None, self._stream()))
+            t.fill_(1)
+            env.step(torch.where(finished, torch.full_like(acts, -1), acts))
+            term = env.terminated.bool()
+            won |= term & ~finished
+            finished |= term | env.truncated.bool()
+            k += 1
+            if k % 32 == 0 and bool(finished.all()):
+                break
+        rates = won.view(P, n).float().mean(dim=1).tolist()
+        env.close()
+        return rates
+
+    # ---- a vector step --------------------------------------------------------------------------
+    def _act(self):
+        env = self.env
+        eps = [min(max(self.epsilon(p), 0.0), 1.0) for p in range(self.P)]
+        for p in range(self.P):
+            self.steps_done[p] += 1
+        self.eps_dev.copy_(torch.tensor(eps, dtype=torch.float32))
+        N.check(self.lib.mz_drqn_pop_act(
+            self.src.data_ptr(), HIDDEN, self.P, self.b, env.obs6.data_ptr(), self.L,
+            self.eps_dev.data_ptr(), self.explore_actions, self.seed_dev.data_ptr(),
+            self.counter & U64, self.t.data_ptr(), self.h.data_ptr(), self.c.data_ptr(),
+            self.rec_x.data_ptr(), self.rec_a.data_ptr(), self.act_out.data_ptr(), None,
+            self._stream()))
+        self.counter += 1
+
+    def _scan_store(self):
+        env, st = self.env, self._stream()
+        self.r64.copy_(env.reward)
+        self._scan(self.r64, env.terminated, env.truncated, self.rec_r,
+                   self.pool[0:].data_ptr(), self.pool[1:].data_ptr())
+        N.check(self.lib.mz_drqn_pop_store(
+            env.obs6.data_ptr(), env.terminated.data_ptr(), self.P, self.b, self.L,
+            self.fin_id.data_ptr(), self.fin_len.data_ptr(), self.fin_count.data_ptr(),
+            self.rec_x.data_ptr(), self.rec_a.data_ptr(), self.rec_r.data_ptr(), self.capacity,
+            self.mem.data_ptr(), self.mem_len.data_ptr(), self.mem_term.data_ptr(),
+            self.ring.data_ptr(), st))
+
+    def _upload(self, due, sync, lr):
+        P = self.P
+        buf = np.zeros(5 * P, np.int32)
+        buf[:2 * P].view(np.int64)[:] = self.updates
+        buf[2 * P:3 * P] = due
+        buf[3 * P:4 * P] = sync
+        buf[4 * P:].view(np.float32)[:] = lr
+        self.upd.copy_(torch.from_numpy(buf))
+
+    def sample(self, due):
+        """E distinct slots and the directory of every due learner, keyed by its update count."""
+        N.check(self.lib.mz_drqn_pop_sample(
+            self.seed_dev.data_ptr(), self.cnt_dev.data_ptr(), self.due_dev.data_ptr(), self.P,
+            self.batch_size, self.L, self.capacity,
+            min(f for f, d in zip(self.filled, due) if d), self.ring.data_ptr(),
+            self.mem_len.data_ptr(), self.d_slot.data_ptr(), self.d_len.data_ptr(),
+            self.d_off.data_ptr(), self.d_tot.data_ptr(), self._stream()))
+
+    def update(self):
+        """One optimizer step of every due learner on its directory's episodes at lr_dev[p]; the
+        losses stay on the device (self.loss)."""
+        P, E, L, st = self.P, self.batch_size, self.L, self._stream()
+        dirs = (self.d_slot.data_ptr(), self.d_len.data_ptr(), self.d_off.data_ptr(),
+                self.d_tot.data_ptr())
+        due, gam = self.due_dev.data_ptr(), self.gamma_dev.data_ptr()
+        N.check(self.lib.mz_drqn_pop_seq_forward(
+            self.tgt.data_ptr(), HIDDEN, 1, P, E, L, self.capacity, gam, due, self.mem.data_ptr(),
+            self.mem_term.data_ptr(), *dirs, self.qmax.data_ptr(), None, None, None, None, None,
+            st))
+        N.check(self.lib.mz_drqn_pop_seq_forward(
+            self.src.data_ptr(), HIDDEN, 0, P, E, L, self.capacity, gam, due, self.mem.data_ptr(),
+            self.mem_term.data_ptr(), *dirs, self.qmax.data_ptr(), self.stash.data_ptr(),
+            self.qa.data_ptr(), self.y.data_ptr(), self.d.data_ptr(), self.ep_loss.data_ptr(), st))
+        N.check(self.lib.mz_drqn_pop_seq_backward(
+            self.src.data_ptr(), HIDDEN, P, E, L, self.capacity, due, self.mem.data_ptr(), *dirs,
+            self.stash.data_ptr(), self.d.data_ptr(), self.ep_loss.data_ptr(),
+            self.gpart.data_ptr(), self.grad.data_ptr(), self.loss.data_ptr(), st))
+        N.check(self.lib.mz_adamw_pop(
+            self.src.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+            self.grad.data_ptr(), P, PARAMS, self.lr_dev.data_ptr(), self.step.data_ptr(), due,
+            BETAS[0], BETAS[1], ADAM_EPS, WEIGHT_DECAY, CLAMP, 1.0, 1, st))
+
+    def _update(self, due):
+        if self.launches % 256 == 0 and int(self.stats[3]):  # (one look every 256 updates)
+            raise RuntimeError(f"recurrent DQN episode records overflowed L = {self.L} steps "
+                               "(mz_ppo_scan stats[3])")
+        self.launches += 1
+        lr, sync = [0.0] * self.P, [0] * self.P
+        for p in range(self.P):
+            if due[p]:
+                lr[p] = self.last_lr[p] = cosine_lr(self.updates[p], self.lr[p], T_MAX, ETA_MIN)
+                sync[p] = int((self.updates[p] + 1) % self.tuf[p] == 0)
+        self._upload(due, sync, lr)
+        self.sample(due)
+        self.update()
+        if any(sync):
+            N.check(self.lib.mz_drqn_pop_sync(self.src.data_ptr(), self.tgt.data_ptr(),
+                                              self.sync_dev.data_ptr(), self.P, self._stream()))
+        for p in range(self.P):
+            self.updates[p] += int(due[p])
+
+    def vector_step(self):
+        self._act()
+        self.env.step(self.act_out)
+        self._scan_store()
+        self._reset_winners()
+        E = self.batch_size
+        if min(self.filled) < E:  # (only until every learner has its first batch: one sync a step)
+            counts = self.ring[:, 1].tolist()
+            self.filled = [f if f >= E else int(n) for f, n in zip(self.filled, counts)]
+        due = [False] * self.P
+        if self.counter % self.train_every == 0:
+            due = [f >= E for f in self.filled]
+        self.last_due = due
+        if any(due):
+            self._update(due)
+
+    def _log_fields(self):
+        return {"loss": [round(v, 6) for v in self.loss.tolist()],
+                "epsilon": [round(self.epsilon(p), 4) for p in range(self.P)]}
+
+    # ---- checkpoint / resume (mazerl/checkpoint.py) -------------------------------------------
+    _OWN = ("h", "c", "ring", "pool", "loss", "src", "tgt", "exp_avg", "exp_avg_sq", "step")
+    _LISTS = ("seed", "steps_done", "updates", "filled")
+
+    def state_dict(self):
+        """The run between two vector steps: every learner's nets, moments and step count, (h, c),
+        the in-flight records, each ring's filled slots with head and count, the per-learner
+        counters and the env (_save_common)."""
+        sd = self._save_common()
+        sd.update({k: getattr(self, k).clone() for k in self._OWN})
+        counts = [int(n) for n in self.ring[:, 1].tolist()]
+        for k in ("mem", "mem_len", "mem_term"):
+            sd[k] = [getattr(self, k)[p, :n].clone() for p, n in enumerate(counts)]
+        sd["learners"] = {k: [int(v) for v in getattr(self, k)] for k in self._LISTS}
+        return sd
+
+    def load_state_dict(self, sd):
+        self._load_common(sd)
+        for k in self._OWN:
+            getattr(self, k).copy_(sd[k])
+        for k in ("mem", "mem_len", "mem_term"):
+            for p, part in enumerate(sd[k]):
+                getattr(self, k)[p, :part.shape[0]].copy_(part)
+        for k in self._LISTS:
+            setattr(self, k, [int(v) for v in sd["learners"][k]])
+        self.seed_dev.copy_(torch.tensor([_signed(s) for s in self.seed], dtype=torch.int64))
