@@ -780,6 +780,70 @@ int mz_drqn_seq_backward(const float* const* params_dev, int32_t hidden, int32_t
                          const double* ep_loss_dev, float* gpart_dev, float* const* grads_dev,
                          float* loss_dev, void* stream);
 
+/* ---- Replay windows with stored state and burn-in (VectorRecurrentDQNTrainer(window=T)) -------
+ * An update trains on one window of T steps per sampled episode instead of the whole episode:
+ * window j of an episode of n steps covers steps s = j T .. s + m - 1, m = min(T, n - s),
+ * j = 0 .. ceil(n / T) - 1. Both nets start at step b = max(0, s - K) (K = the burn-in, a multiple
+ * of T) from the same state, snapshot b / T of the episode, or zero where b == 0 or no snapshots
+ * are kept, and unroll k = s - b burn-in steps that carry no loss term and no gradient. A
+ * snapshot is 64 f32 (h[32], c[32]): the state the instance held before it acted at step j T,
+ * j >= 1; an episode has ceil(L / T) snapshot entries, entry 0 is never written. The accumulation
+ * order of a step is the one stated above. Every entry point refuses a null pointer, T < 1, K < 0,
+ * K % T != 0, hidden != 32, E < 1, B < 1, L < 1 and capacity < E with MZ_EINVAL before any GPU
+ * call, as far as it has the argument. */
+
+/* Before mz_drqn_act of the same vector step: where 0 < t_dev[i] < L and t_dev[i] % T == 0, column
+ * i of h_dev / c_dev ([32][B]) goes to snap_rec_dev[i][t / T] ([B][ceil(L / T)][64]). */
+int mz_drqn_snapshot(int32_t hidden, int32_t B, int32_t L, int32_t T, const int32_t* t_dev,
+                     const float* h_dev, const float* c_dev, float* snap_rec_dev, void* stream);
+
+/* After mz_ppo_scan and BEFORE mz_drqn_store (which advances ring_dev): snapshots 1 ..
+ * ceil(n / T) - 1 of its k-th listed episode (instance i, n steps) from snap_rec_dev[i] into
+ * mem_state_dev[(head + k) mod capacity] ([capacity][ceil(L / T)][64]), the slot mz_drqn_store
+ * gives the episode; with more listed episodes than slots the last `capacity` stay. Nothing else
+ * of mem_state_dev is written. */
+int mz_drqn_snap_store(int32_t hidden, int32_t B, int32_t L, int32_t T, const int32_t* fin_id_dev,
+                       const int32_t* fin_len_dev, const int32_t* fin_count_dev,
+                       const float* snap_rec_dev, int64_t capacity, float* mem_state_dev,
+                       const int64_t* ring_dev, void* stream);
+
+/* mz_drqn_sample's E slots (the same draws for the same (seed, counter)), then for batch position
+ * e one window j = floor(u32 ceil(n / T) / 2^32) from a Philox stream of its own keyed by (seed,
+ * counter, e): windows are uniform within an episode, not over the memory. wdir_dev is int32
+ * [5][E]: slot, n, b, k, m. win_off_dev [E] int64 = the exclusive scan of (m + 2): window e owns
+ * rows win_off[e] (the entry state), + 1 .. + m (its training steps) and + m + 1 (the guard row)
+ * of the update's row buffers, which hold E (min(T, L) + 2) rows whatever L and K are.
+ * win_tot_dev int64 [2] = (rows, sum m). */
+int mz_drqn_window_sample(uint64_t seed, uint64_t counter, int32_t hidden, int32_t E, int32_t L,
+                          int32_t T, int32_t K, int64_t capacity, int64_t filled,
+                          const int64_t* ring_dev, const int32_t* mem_len_dev, int32_t* wdir_dev,
+                          int64_t* win_off_dev, int64_t* win_tot_dev, void* stream);
+
+/* mz_drqn_seq_forward over the directory's windows, one wave per window, from mem_state_dev's
+ * snapshots (NULL: zero state). target != 0: x_b .. x_{s+m}, qmax_dev[win_off + 1 + i] = max_a
+ * Q'_{s+i}, i = 0 .. m. target == 0: x_b .. x_{s+m-1}; stash_dev[win_off][128 .. 191] = (c, h)
+ * entering step s; per training step i at row win_off + 1 + i the stash, qa_dev, y_dev = r +
+ * gamma qmax[row + 1] (r alone where s + i == n - 1 and the episode terminated), d_dev =
+ * 2 (Q - y) / sum m; ep_loss_dev[e] = the window's sum of squared residuals. With T >= L and K == 0
+ * these are mz_drqn_seq_forward's bits, one row further down. */
+int mz_drqn_window_forward(const float* const* params_dev, int32_t hidden, int32_t target,
+                           int32_t E, int32_t L, int32_t T, int32_t K, int64_t capacity,
+                           float gamma, const uint32_t* mem_dev, const int32_t* mem_term_dev,
+                           const float* mem_state_dev, const int32_t* wdir_dev,
+                           const int64_t* win_off_dev, const int64_t* win_tot_dev, float* qmax_dev,
+                           float* stash_dev, float* qa_dev, float* y_dev, float* d_dev,
+                           double* ep_loss_dev, void* stream);
+
+/* mz_drqn_seq_backward over the m training steps of each window (nothing flows into the burn-in
+ * or the entry state): gpart_dev [E][5252], then grads_dev and loss_dev[0] = sum of ep_loss /
+ * sum m, reduced in index order as there. */
+int mz_drqn_window_backward(const float* const* params_dev, int32_t hidden, int32_t E, int32_t L,
+                            int32_t T, int32_t K, int64_t capacity, const uint32_t* mem_dev,
+                            const int32_t* wdir_dev, const int64_t* win_off_dev,
+                            const int64_t* win_tot_dev, const float* stash_dev,
+                            const float* d_dev, const double* ep_loss_dev, float* gpart_dev,
+                            float* const* grads_dev, float* loss_dev, void* stream);
+
 /* ---- Populations of recurrent DQN learners (VectorRecurrentDQNPopulation) ---------------------
  * P independent learners of agents/lstm_dqn_agent.py (nn.LSTMCell(6, 32) + nn.Linear(32, 4),
  * whole episodes from SequentialExperienceReplayMemory, lib/replay_memory.py:26-43) advanced by

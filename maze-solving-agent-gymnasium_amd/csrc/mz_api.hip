@@ -1633,6 +1633,110 @@ int mz_drqn_seq_backward(const float* const* params_dev, int32_t hidden, int32_t
   return MZ_OK;
 }
 
+// ---- recurrent DQN replay windows (mz_drqn.hip k_drqn_snapshot .. k_drqn_win_bwd) ----------------
+static int drqn_win_args(const char* who, int32_t hidden, int32_t T, int32_t K) {
+  if (hidden != MZ_DRQN_HIDDEN) return fail(MZ_EINVAL, "%s: hidden %d != 32", who, hidden);
+  if (T < 1 || K < 0 || K % T != 0)
+    return fail(MZ_EINVAL, "%s: window %d (>= 1), burn-in %d (>= 0, a multiple of the window)",
+                who, T, K);
+  return MZ_OK;
+}
+
+int mz_drqn_snapshot(int32_t hidden, int32_t B, int32_t L, int32_t T, const int32_t* t_dev,
+                     const float* h_dev, const float* c_dev, float* snap_rec_dev, void* stream) {
+  if (!t_dev || !h_dev || !c_dev || !snap_rec_dev)
+    return fail(MZ_EINVAL, "mz_drqn_snapshot: null pointer");
+  if (int rc = drqn_win_args("mz_drqn_snapshot", hidden, T, 0)) return rc;
+  if (B < 1 || L < 1) return fail(MZ_EINVAL, "mz_drqn_snapshot: B %d, L %d", B, L);
+  StreamGuard g(stream);
+  MzDrqnSnap q{B, L, T, t_dev, h_dev, c_dev, snap_rec_dev};
+  MZ_HIP(mz_launch_drqn_snapshot(q, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_drqn_snap_store(int32_t hidden, int32_t B, int32_t L, int32_t T, const int32_t* fin_id_dev,
+                       const int32_t* fin_len_dev, const int32_t* fin_count_dev,
+                       const float* snap_rec_dev, int64_t capacity, float* mem_state_dev,
+                       const int64_t* ring_dev, void* stream) {
+  if (!fin_id_dev || !fin_len_dev || !fin_count_dev || !snap_rec_dev || !mem_state_dev || !ring_dev)
+    return fail(MZ_EINVAL, "mz_drqn_snap_store: null pointer");
+  if (int rc = drqn_win_args("mz_drqn_snap_store", hidden, T, 0)) return rc;
+  if (B < 1 || L < 1 || capacity < 1)
+    return fail(MZ_EINVAL, "mz_drqn_snap_store: B %d, L %d, capacity %lld", B, L,
+                (long long)capacity);
+  StreamGuard g(stream);
+  MzDrqnSnapStore q{B, L, T, fin_id_dev, fin_len_dev, fin_count_dev, snap_rec_dev, capacity,
+                    mem_state_dev, ring_dev};
+  MZ_HIP(mz_launch_drqn_snap_store(q, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_drqn_window_sample(uint64_t seed, uint64_t counter, int32_t hidden, int32_t E, int32_t L,
+                          int32_t T, int32_t K, int64_t capacity, int64_t filled,
+                          const int64_t* ring_dev, const int32_t* mem_len_dev, int32_t* wdir_dev,
+                          int64_t* win_off_dev, int64_t* win_tot_dev, void* stream) {
+  if (!ring_dev || !mem_len_dev || !wdir_dev || !win_off_dev || !win_tot_dev)
+    return fail(MZ_EINVAL, "mz_drqn_window_sample: null pointer");
+  if (int rc = drqn_win_args("mz_drqn_window_sample", hidden, T, K)) return rc;
+  if (E < 1 || E > 8192 || L < 1 || capacity < E || filled > capacity || filled < E)
+    return fail(MZ_EINVAL, "mz_drqn_window_sample: E %d (1..8192), L %d, capacity %lld, filled "
+                "%lld", E, L, (long long)capacity, (long long)filled);
+  StreamGuard g(stream);
+  MzDrqnWinSample q{{seed, counter, E, L, capacity, ring_dev, mem_len_dev,
+                     wdir_dev + (size_t)MZ_DRQN_WDIR_SLOT * E, wdir_dev + (size_t)MZ_DRQN_WDIR_LEN * E,
+                     win_off_dev, win_tot_dev}, T, K, wdir_dev};
+  MZ_HIP(mz_launch_drqn_window_sample(q, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_drqn_window_forward(const float* const* params_dev, int32_t hidden, int32_t target,
+                           int32_t E, int32_t L, int32_t T, int32_t K, int64_t capacity,
+                           float gamma, const uint32_t* mem_dev, const int32_t* mem_term_dev,
+                           const float* mem_state_dev, const int32_t* wdir_dev,
+                           const int64_t* win_off_dev, const int64_t* win_tot_dev, float* qmax_dev,
+                           float* stash_dev, float* qa_dev, float* y_dev, float* d_dev,
+                           double* ep_loss_dev, void* stream) {
+  MzDrqnNet p;
+  if (!drqn_net(params_dev, &p) || !mem_dev || !mem_term_dev || !wdir_dev || !win_off_dev ||
+      !win_tot_dev || !qmax_dev ||
+      (!target && (!stash_dev || !qa_dev || !y_dev || !d_dev || !ep_loss_dev)))
+    return fail(MZ_EINVAL, "mz_drqn_window_forward: null pointer");
+  if (int rc = drqn_win_args("mz_drqn_window_forward", hidden, T, K)) return rc;
+  if (int rc = drqn_seq_args("mz_drqn_window_forward", hidden, E, L, capacity)) return rc;
+  StreamGuard g(stream);
+  MzDrqnWin q{p, target ? 1 : 0, E, L, T, K, capacity, gamma, mem_dev, mem_term_dev,
+              mem_state_dev, wdir_dev, win_off_dev, win_tot_dev, qmax_dev, stash_dev, qa_dev,
+              y_dev, d_dev, ep_loss_dev, nullptr};
+  MZ_HIP(mz_launch_drqn_window_forward(q, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_drqn_window_backward(const float* const* params_dev, int32_t hidden, int32_t E, int32_t L,
+                            int32_t T, int32_t K, int64_t capacity, const uint32_t* mem_dev,
+                            const int32_t* wdir_dev, const int64_t* win_off_dev,
+                            const int64_t* win_tot_dev, const float* stash_dev,
+                            const float* d_dev, const double* ep_loss_dev, float* gpart_dev,
+                            float* const* grads_dev, float* loss_dev, void* stream) {
+  MzDrqnNet p;
+  if (!drqn_net(params_dev, &p) || !mem_dev || !wdir_dev || !win_off_dev || !win_tot_dev ||
+      !stash_dev || !d_dev || !ep_loss_dev || !gpart_dev || !grads_dev || !loss_dev)
+    return fail(MZ_EINVAL, "mz_drqn_window_backward: null pointer");
+  for (int k = 0; k < 6; ++k)
+    if (!grads_dev[k]) return fail(MZ_EINVAL, "mz_drqn_window_backward: null gradient segment");
+  if (int rc = drqn_win_args("mz_drqn_window_backward", hidden, T, K)) return rc;
+  if (int rc = drqn_seq_args("mz_drqn_window_backward", hidden, E, L, capacity)) return rc;
+  StreamGuard g(stream);
+  MzDrqnWin q{p, 0, E, L, T, K, capacity, 0.0f, mem_dev, nullptr, nullptr, wdir_dev, win_off_dev,
+              win_tot_dev, nullptr, const_cast<float*>(stash_dev), nullptr, nullptr,
+              const_cast<float*>(d_dev), nullptr, gpart_dev};
+  MZ_HIP(mz_launch_drqn_window_backward(q, static_cast<hipStream_t>(stream)));
+  MzDrqnReduce r{E, gpart_dev, ep_loss_dev, wdir_dev + (size_t)MZ_DRQN_WDIR_M * E, win_tot_dev,
+                 {grads_dev[0], grads_dev[1], grads_dev[2], grads_dev[3], grads_dev[4],
+                  grads_dev[5]}, loss_dev};
+  MZ_HIP(mz_launch_drqn_reduce(r, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
 // ---- populations of recurrent DQN learners (mz_drqn.hip k_drqn_pop_*) ----------------------------
 static int drqn_pop_args(const char* who, int32_t hidden, int32_t P, int64_t per, const char* what) {
   if (hidden != MZ_DRQN_HIDDEN) return fail(MZ_EINVAL, "%s: hidden %d != 32", who, hidden);

@@ -35,6 +35,18 @@
 //   k_drqn_reduce    per parameter the partials summed over the episodes in index order (float64,
 //                    rounded once) into the net's gradient segments; the loss (float64, episode
 //                    order). No float atomics anywhere: two runs give the same bits.
+// Replay windows (window = T, burn_in = K; off by default, single learner only):
+//   k_drqn_snapshot    a launch of its own before k_drqn_act (whose code and bits stay as they
+//                      are): the state an instance acts from at t = j T, j >= 1, into its record.
+//   k_drqn_snap_store  before k_drqn_store: the finished episodes' snapshots into the ring slot
+//                      k_drqn_store is about to give them.
+//   k_drqn_win_sample  k_drqn_sample's body for the slots, then one window per episode and the
+//                      window directory; a window owns m + 2 rows (entry state, m steps, guard),
+//                      so the row buffers hold E (T + 2) rows whatever L and K are.
+//   k_drqn_win_fwd / k_drqn_win_bwd   the sequence kernels' lane layout and per-step arithmetic
+//                      over steps b .. of the episode from the stored state; the burn-in steps only
+//                      advance the state, BPTT covers the m training steps. k_drqn_reduce sums the
+//                      per-window partials.
 // Populations (trainers/drqn_population.py VectorRecurrentDQNPopulation): P independent learners
 // over B = P b instances, learner p owning instances [p b, (p + 1) b), flat [P][5252] parameters.
 // Every kernel above is a thin wrapper of a __device__ body; its k_drqn_pop_* twin moves the
@@ -383,6 +395,80 @@ __global__ __launch_bounds__(WAVE) void k_drqn_pop_sample(MzDrqnPopSample q) {
 }
 
 // ---- the sequence forward --------------------------------------------------------------------
+// A lane's share of the net in the sequence and window forwards: lane = (unit u, half) owns gate
+// rows r0 = half 64 + u and r1 = r0 + 32, i.e. (i_u, f_u) or (g_u, o_u), and row lane & 3 of the head.
+struct DrqnFwdLane {
+  float b0, b1, wx0[NX], wx1[NX], wh0[H], wh1[H], fw[H], fb;
+};
+__device__ __forceinline__ void drqn_fwd_lane(const MzDrqnNet& p, const int lane, DrqnFwdLane& w) {
+  const int r0 = (lane >> 5) * 2 * H + (lane & (H - 1)), r1 = r0 + H;
+  w.b0 = p.b_ih[r0] + p.b_hh[r0];
+  w.b1 = p.b_ih[r1] + p.b_hh[r1];
+#pragma unroll
+  for (int k = 0; k < NX; ++k) {
+    w.wx0[k] = p.w_ih[r0 * NX + k];
+    w.wx1[k] = p.w_ih[r1 * NX + k];
+  }
+#pragma unroll
+  for (int k = 0; k < H; ++k) {
+    w.wh0[k] = p.w_hh[r0 * H + k];
+    w.wh1[k] = p.w_hh[r1 * H + k];
+    w.fw[k] = p.fc_w[(lane & 3) * H + k];
+  }
+  w.fb = p.fc_b[lane & 3];
+}
+
+// One step of the cell from (hb = the old h, c) on the replay row (ra, rb): the lane's two gates
+// after their nonlinearity (v0, v1), the new c and h of unit u, and the new h of every unit in hb
+// (through hs, 128 B of LDS).
+__device__ __forceinline__ void drqn_fwd_step(const DrqnFwdLane& w, const uint4 ra, const uint4 rb,
+                                              float* hs, const int u, const int half,
+                                              float (&hb)[H], float& c, float& h, float& v0,
+                                              float& v1) {
+  const float x[NX] = {__uint_as_float(ra.x), __uint_as_float(ra.y), __uint_as_float(ra.z),
+                       __uint_as_float(ra.w), __uint_as_float(rb.x), __uint_as_float(rb.y)};
+  float z0 = w.b0, z1 = w.b1;
+#pragma unroll
+  for (int k = 0; k < NX; ++k) {
+    z0 = fmaf(w.wx0[k], x[k], z0);
+    z1 = fmaf(w.wx1[k], x[k], z1);
+  }
+#pragma unroll
+  for (int k = 0; k < H; ++k) {
+    z0 = fmaf(w.wh0[k], hb[k], z0);
+    z1 = fmaf(w.wh1[k], hb[k], z1);
+  }
+  v0 = half ? tanhf(z0) : sigmoidf_(z0);  // g or i
+  v1 = sigmoidf_(z1);                     // o or f
+  const float p0 = __shfl_xor(v0, 32), p1 = __shfl_xor(v1, 32);
+  const float gi = half ? p0 : v0, gf = half ? p1 : v1, gg = half ? v0 : p0, go = half ? v1 : p1;
+  c = gf * c + gi * gg;
+  h = go * tanhf(c);
+  __syncthreads();
+  if (!half) hs[u] = h;
+  __syncthreads();
+#pragma unroll
+  for (int k4 = 0; k4 < H / 4; ++k4) {
+    const float4 v = reinterpret_cast<const float4*>(hs)[k4];
+    hb[4 * k4 + 0] = v.x;
+    hb[4 * k4 + 1] = v.y;
+    hb[4 * k4 + 2] = v.z;
+    hb[4 * k4 + 3] = v.w;
+  }
+}
+
+// the four q values of the state in hb, in every lane
+__device__ __forceinline__ void drqn_fwd_head(const DrqnFwdLane& w, const float (&hb)[H], float& q0,
+                                              float& q1, float& q2, float& q3) {
+  float qa = w.fb;  // q[lane & 3]
+#pragma unroll
+  for (int k = 0; k < H; ++k) qa = fmaf(w.fw[k], hb[k], qa);
+  q0 = __shfl(qa, 0);
+  q1 = __shfl(qa, 1);
+  q2 = __shfl(qa, 2);
+  q3 = __shfl(qa, 3);
+}
+
 __device__ __forceinline__ void drqn_seq_fwd_body(const MzDrqnSeq& q, const int e) {
   __shared__ __attribute__((aligned(16))) float hs[H];
   const int lane = threadIdx.x, u = lane & (H - 1), half = lane >> 5;
@@ -393,20 +479,8 @@ __device__ __forceinline__ void drqn_seq_fwd_body(const MzDrqnSeq& q, const int 
     return;
   const uint32_t* ep = q.mem + (size_t)slot * (q.L + 1) * ROW;
   const int r0 = half * 2 * H + u, r1 = r0 + H;  // (i_u, f_u) or (g_u, o_u)
-  float b0 = q.p.b_ih[r0] + q.p.b_hh[r0], b1 = q.p.b_ih[r1] + q.p.b_hh[r1];
-  float wx0[NX], wx1[NX], wh0[H], wh1[H], fw[H];
-#pragma unroll
-  for (int k = 0; k < NX; ++k) {
-    wx0[k] = q.p.w_ih[r0 * NX + k];
-    wx1[k] = q.p.w_ih[r1 * NX + k];
-  }
-#pragma unroll
-  for (int k = 0; k < H; ++k) {
-    wh0[k] = q.p.w_hh[r0 * H + k];
-    wh1[k] = q.p.w_hh[r1 * H + k];
-    fw[k] = q.p.fc_w[(lane & 3) * H + k];
-  }
-  const float fb = q.p.fc_b[lane & 3];
+  DrqnFwdLane w;
+  drqn_fwd_lane(q.p, lane, w);
   float hb[H];
 #pragma unroll
   for (int k = 0; k < H; ++k) hb[k] = 0.0f;
@@ -418,40 +492,9 @@ __device__ __forceinline__ void drqn_seq_fwd_body(const MzDrqnSeq& q, const int 
   for (int t = 0; t < steps; ++t) {
     const uint4 ra = *reinterpret_cast<const uint4*>(ep + (size_t)t * ROW);
     const uint4 rb = *reinterpret_cast<const uint4*>(ep + (size_t)t * ROW + 4);
-    const float x[NX] = {__uint_as_float(ra.x), __uint_as_float(ra.y), __uint_as_float(ra.z),
-                         __uint_as_float(ra.w), __uint_as_float(rb.x), __uint_as_float(rb.y)};
-    float z0 = b0, z1 = b1;
-#pragma unroll
-    for (int k = 0; k < NX; ++k) {
-      z0 = fmaf(wx0[k], x[k], z0);
-      z1 = fmaf(wx1[k], x[k], z1);
-    }
-#pragma unroll
-    for (int k = 0; k < H; ++k) {
-      z0 = fmaf(wh0[k], hb[k], z0);
-      z1 = fmaf(wh1[k], hb[k], z1);
-    }
-    const float v0 = half ? tanhf(z0) : sigmoidf_(z0);  // g or i
-    const float v1 = sigmoidf_(z1);                     // o or f
-    const float p0 = __shfl_xor(v0, 32), p1 = __shfl_xor(v1, 32);
-    const float gi = half ? p0 : v0, gf = half ? p1 : v1, gg = half ? v0 : p0, go = half ? v1 : p1;
-    c = gf * c + gi * gg;
-    const float h = go * tanhf(c);
-    __syncthreads();
-    if (!half) hs[u] = h;
-    __syncthreads();
-#pragma unroll
-    for (int k4 = 0; k4 < H / 4; ++k4) {
-      const float4 v = reinterpret_cast<const float4*>(hs)[k4];
-      hb[4 * k4 + 0] = v.x;
-      hb[4 * k4 + 1] = v.y;
-      hb[4 * k4 + 2] = v.z;
-      hb[4 * k4 + 3] = v.w;
-    }
-    float qa = fb;  // q[lane & 3]
-#pragma unroll
-    for (int k = 0; k < H; ++k) qa = fmaf(fw[k], hb[k], qa);
-    const float q0 = __shfl(qa, 0), q1 = __shfl(qa, 1), q2 = __shfl(qa, 2), q3 = __shfl(qa, 3);
+    float h, v0, v1, q0, q1, q2, q3;
+    drqn_fwd_step(w, ra, rb, hs, u, half, hb, c, h, v0, v1);
+    drqn_fwd_head(w, hb, q0, q1, q2, q3);
     const int64_t R = off + t;
     if (q.target) {
       if (lane == 0) q.qmax[R] = fmaxf(fmaxf(q0, q1), fmaxf(q2, q3));
@@ -512,6 +555,129 @@ __global__ __launch_bounds__(WAVE) void k_drqn_pop_seq_fwd(MzDrqnPopSeq q) {
 }
 
 // ---- back-propagation through time -----------------------------------------------------------
+// A lane's state in the sequence and window backwards (the forward's lane layout): the weights it
+// reads, the gradient accumulators of its two gate rows and of the head, and what flows back in time.
+struct DrqnBwdLane {
+  float wt[2 * H], fcu[4];  // W_hh^T: unit u's column over the half's 64 gate rows; fc_w[:, u]
+  float gx0[NX], gx1[NX], gh0[H], gh1[H], gfc[4], gfb[4], gb0, gb1;
+  float dh_next, dc_next;
+};
+__device__ __forceinline__ void drqn_bwd_lane(const MzDrqnNet& p, const int u, const int half,
+                                              DrqnBwdLane& g) {
+#pragma unroll
+  for (int j = 0; j < 2 * H; ++j) g.wt[j] = p.w_hh[(half * 2 * H + j) * H + u];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) g.fcu[a] = p.fc_w[a * H + u];
+#pragma unroll
+  for (int k = 0; k < NX; ++k) g.gx0[k] = g.gx1[k] = 0.0f;
+#pragma unroll
+  for (int k = 0; k < H; ++k) g.gh0[k] = g.gh1[k] = 0.0f;
+#pragma unroll
+  for (int a = 0; a < 4; ++a) g.gfc[a] = g.gfb[a] = 0.0f;
+  g.gb0 = g.gb1 = g.dh_next = g.dc_next = 0.0f;
+}
+
+// the (c, h) of the step one stash row above st: c of unit u, h of every unit
+__device__ __forceinline__ void drqn_bwd_prev(const float* st, const int u, float& cp,
+                                              float (&hp)[H]) {
+  cp = st[G4 + u - STASH];
+  const float4* hv = reinterpret_cast<const float4*>(st - STASH + G4 + H);
+#pragma unroll
+  for (int k4 = 0; k4 < H / 4; ++k4) {
+    const float4 v = hv[k4];
+    hp[4 * k4 + 0] = v.x;
+    hp[4 * k4 + 1] = v.y;
+    hp[4 * k4 + 2] = v.z;
+    hp[4 * k4 + 3] = v.w;
+  }
+}
+
+// One step back: from the step's stash row st, the state before it (cp, hp), its replay row and
+// d = d loss / d Q_t[a_t] (the 1 / steps folded in) the lane's gradient terms, dc_{t-1} and dh_{t-1}
+// (through dzs, 512 B of LDS).
+__device__ __forceinline__ void drqn_bwd_step(DrqnBwdLane& g, const float* st, const float cp,
+                                              const float (&hp)[H], const uint4 ra, const uint4 rb,
+                                              const float d, float* dzs, const int u,
+                                              const int half) {
+  const int r0 = half * 2 * H + u, r1 = r0 + H;
+  const float gi = st[u], gf = st[H + u], gg = st[2 * H + u], go = st[3 * H + u];
+  const float ct = st[G4 + u], ht = st[G4 + H + u];
+  const float x[NX] = {__uint_as_float(ra.x), __uint_as_float(ra.y), __uint_as_float(ra.z),
+                       __uint_as_float(ra.w), __uint_as_float(rb.x), __uint_as_float(rb.y)};
+  const int a = (int)rb.z & 3;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    g.gfc[k] += k == a ? d * ht : 0.0f;
+    g.gfb[k] += k == a ? d : 0.0f;
+  }
+  const float fsel = a == 0 ? g.fcu[0] : (a == 1 ? g.fcu[1] : (a == 2 ? g.fcu[2] : g.fcu[3]));
+  const float dh = fmaf(d, fsel, g.dh_next);
+  const float tc = tanhf(ct);
+  const float dc = fmaf(dh * go, 1.0f - tc * tc, g.dc_next);
+  const float dzi = dc * gg * gi * (1.0f - gi);
+  const float dzf = dc * cp * gf * (1.0f - gf);
+  const float dzg = dc * gi * (1.0f - gg * gg);
+  const float dzo = dh * tc * go * (1.0f - go);
+  g.dc_next = dc * gf;
+  const float dz0 = half ? dzg : dzi, dz1 = half ? dzo : dzf;
+  g.gb0 += dz0;
+  g.gb1 += dz1;
+#pragma unroll
+  for (int k = 0; k < NX; ++k) {
+    g.gx0[k] = fmaf(dz0, x[k], g.gx0[k]);
+    g.gx1[k] = fmaf(dz1, x[k], g.gx1[k]);
+  }
+#pragma unroll
+  for (int k = 0; k < H; ++k) {
+    g.gh0[k] = fmaf(dz0, hp[k], g.gh0[k]);
+    g.gh1[k] = fmaf(dz1, hp[k], g.gh1[k]);
+  }
+  // dh_{t-1}[u] = sum over the 128 gate rows of W_hh[row][u] dz[row]: each half its 64 rows in
+  // row order, then the two halves added
+  __syncthreads();
+  dzs[r0] = dz0;
+  dzs[r1] = dz1;
+  __syncthreads();
+  float part = 0.0f;
+#pragma unroll
+  for (int j4 = 0; j4 < 2 * H / 4; ++j4) {
+    const float4 v = reinterpret_cast<const float4*>(dzs + half * 2 * H)[j4];
+    part = fmaf(g.wt[4 * j4 + 0], v.x, part);
+    part = fmaf(g.wt[4 * j4 + 1], v.y, part);
+    part = fmaf(g.wt[4 * j4 + 2], v.z, part);
+    part = fmaf(g.wt[4 * j4 + 3], v.w, part);
+  }
+  g.dh_next = part + __shfl_xor(part, 32);
+}
+
+// the lane's accumulators into the partial gp [5252], flat parameter order
+__device__ __forceinline__ void drqn_bwd_write(const DrqnBwdLane& g, float* gp, const int lane) {
+  const int u = lane & (H - 1), half = lane >> 5;
+  const int r0 = half * 2 * H + u, r1 = r0 + H;
+#pragma unroll
+  for (int k = 0; k < NX; ++k) {
+    gp[P_WIH + r0 * NX + k] = g.gx0[k];
+    gp[P_WIH + r1 * NX + k] = g.gx1[k];
+  }
+#pragma unroll
+  for (int k = 0; k < H; ++k) {
+    gp[P_WHH + r0 * H + k] = g.gh0[k];
+    gp[P_WHH + r1 * H + k] = g.gh1[k];
+  }
+  gp[P_BIH + r0] = g.gb0;
+  gp[P_BIH + r1] = g.gb1;
+  gp[P_BHH + r0] = g.gb0;
+  gp[P_BHH + r1] = g.gb1;
+  if (!half) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a) gp[P_FCW + a * H + u] = g.gfc[a];
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a) gp[P_FCB + a] = g.gfb[a];
+  }
+}
+
 __device__ __forceinline__ void drqn_seq_bwd_body(const MzDrqnSeq& q, const int e) {
   __shared__ __attribute__((aligned(16))) float dzs[G4];
   const int lane = threadIdx.x, u = lane & (H - 1), half = lane >> 5;
@@ -524,115 +690,23 @@ __device__ __forceinline__ void drqn_seq_bwd_body(const MzDrqnSeq& q, const int 
     return;
   }
   const uint32_t* ep = q.mem + (size_t)slot * (q.L + 1) * ROW;
-  const int r0 = half * 2 * H + u, r1 = r0 + H;
-  // W_hh^T: this lane's unit column over its half's 64 gate rows
-  float wt[2 * H];
-#pragma unroll
-  for (int j = 0; j < 2 * H; ++j) wt[j] = q.p.w_hh[(half * 2 * H + j) * H + u];
-  float fcu[4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a) fcu[a] = q.p.fc_w[a * H + u];
-  float gx0[NX], gx1[NX], gh0[H], gh1[H], gfc[4], gfb[4];
-#pragma unroll
-  for (int k = 0; k < NX; ++k) gx0[k] = gx1[k] = 0.0f;
-#pragma unroll
-  for (int k = 0; k < H; ++k) gh0[k] = gh1[k] = 0.0f;
-#pragma unroll
-  for (int a = 0; a < 4; ++a) gfc[a] = gfb[a] = 0.0f;
-  float gb0 = 0.0f, gb1 = 0.0f, dh_next = 0.0f, dc_next = 0.0f;
+  DrqnBwdLane g;
+  drqn_bwd_lane(q.p, u, half, g);
   for (int t = n - 1; t >= 0; --t) {
     const int64_t R = off + t;
     const float* st = q.stash + (size_t)R * STASH;
-    const float gi = st[u], gf = st[H + u], gg = st[2 * H + u], go = st[3 * H + u];
-    const float ct = st[G4 + u], ht = st[G4 + H + u];
-    const float cp = t ? st[G4 + u - STASH] : 0.0f;
-    float hp[H];
+    float cp = 0.0f, hp[H];
     if (t) {
-      const float4* hv = reinterpret_cast<const float4*>(st - STASH + G4 + H);
-#pragma unroll
-      for (int k4 = 0; k4 < H / 4; ++k4) {
-        const float4 v = hv[k4];
-        hp[4 * k4 + 0] = v.x;
-        hp[4 * k4 + 1] = v.y;
-        hp[4 * k4 + 2] = v.z;
-        hp[4 * k4 + 3] = v.w;
-      }
+      drqn_bwd_prev(st, u, cp, hp);
     } else {
 #pragma unroll
       for (int k = 0; k < H; ++k) hp[k] = 0.0f;
     }
     const uint4 ra = *reinterpret_cast<const uint4*>(ep + (size_t)t * ROW);
     const uint4 rb = *reinterpret_cast<const uint4*>(ep + (size_t)t * ROW + 4);
-    const float x[NX] = {__uint_as_float(ra.x), __uint_as_float(ra.y), __uint_as_float(ra.z),
-                         __uint_as_float(ra.w), __uint_as_float(rb.x), __uint_as_float(rb.y)};
-    const int a = (int)rb.z & 3;
-    const float d = q.d[R];  // d loss / d Q_t[a_t], the 1 / sum n folded in
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      gfc[k] += k == a ? d * ht : 0.0f;
-      gfb[k] += k == a ? d : 0.0f;
-    }
-    const float fsel = a == 0 ? fcu[0] : (a == 1 ? fcu[1] : (a == 2 ? fcu[2] : fcu[3]));
-    const float dh = fmaf(d, fsel, dh_next);
-    const float tc = tanhf(ct);
-    const float dc = fmaf(dh * go, 1.0f - tc * tc, dc_next);
-    const float dzi = dc * gg * gi * (1.0f - gi);
-    const float dzf = dc * cp * gf * (1.0f - gf);
-    const float dzg = dc * gi * (1.0f - gg * gg);
-    const float dzo = dh * tc * go * (1.0f - go);
-    dc_next = dc * gf;
-    const float dz0 = half ? dzg : dzi, dz1 = half ? dzo : dzf;
-    gb0 += dz0;
-    gb1 += dz1;
-#pragma unroll
-    for (int k = 0; k < NX; ++k) {
-      gx0[k] = fmaf(dz0, x[k], gx0[k]);
-      gx1[k] = fmaf(dz1, x[k], gx1[k]);
-    }
-#pragma unroll
-    for (int k = 0; k < H; ++k) {
-      gh0[k] = fmaf(dz0, hp[k], gh0[k]);
-      gh1[k] = fmaf(dz1, hp[k], gh1[k]);
-    }
-    // dh_{t-1}[u] = sum over the 128 gate rows of W_hh[row][u] dz[row]: each half its 64 rows in
-    // row order, then the two halves added
-    __syncthreads();
-    dzs[r0] = dz0;
-    dzs[r1] = dz1;
-    __syncthreads();
-    float part = 0.0f;
-#pragma unroll
-    for (int j4 = 0; j4 < 2 * H / 4; ++j4) {
-      const float4 v = reinterpret_cast<const float4*>(dzs + half * 2 * H)[j4];
-      part = fmaf(wt[4 * j4 + 0], v.x, part);
-      part = fmaf(wt[4 * j4 + 1], v.y, part);
-      part = fmaf(wt[4 * j4 + 2], v.z, part);
-      part = fmaf(wt[4 * j4 + 3], v.w, part);
-    }
-    dh_next = part + __shfl_xor(part, 32);
+    drqn_bwd_step(g, st, cp, hp, ra, rb, q.d[R], dzs, u, half);
   }
-#pragma unroll
-  for (int k = 0; k < NX; ++k) {
-    gp[P_WIH + r0 * NX + k] = gx0[k];
-    gp[P_WIH + r1 * NX + k] = gx1[k];
-  }
-#pragma unroll
-  for (int k = 0; k < H; ++k) {
-    gp[P_WHH + r0 * H + k] = gh0[k];
-    gp[P_WHH + r1 * H + k] = gh1[k];
-  }
-  gp[P_BIH + r0] = gb0;
-  gp[P_BIH + r1] = gb1;
-  gp[P_BHH + r0] = gb0;
-  gp[P_BHH + r1] = gb1;
-  if (!half) {
-#pragma unroll
-    for (int a = 0; a < 4; ++a) gp[P_FCW + a * H + u] = gfc[a];
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int a = 0; a < 4; ++a) gp[P_FCB + a] = gfb[a];
-  }
+  drqn_bwd_write(g, gp, lane);
 }
 
 __global__ __launch_bounds__(WAVE) void k_drqn_seq_bwd(MzDrqnSeq q) {
@@ -702,6 +776,196 @@ __global__ __launch_bounds__(256) void k_drqn_pop_sync(const float* __restrict__
   if (k < MZ_DRQN_PARAMS) dst[(size_t)p * MZ_DRQN_PARAMS + k] = src[(size_t)p * MZ_DRQN_PARAMS + k];
 }
 
+// ---- replay windows: stored state, burn-in -------------------------------------------------
+constexpr int SNAP = MZ_DRQN_SNAP;  // h[32], c[32]
+__device__ __forceinline__ int drqn_windows(const int n, const int T) { return (n - 1) / T + 1; }
+
+// Before the acting step: where 0 < t[i] < L and t[i] % T == 0 the state instance i is about to
+// act from goes to its in-flight record as snapshot t[i] / T. Workgroups (., w): word w of 256
+// instances, so the reads of h / c ([32][B]) coalesce; one instance in T writes.
+__global__ __launch_bounds__(256) void k_drqn_snapshot(MzDrqnSnap q) {
+  const int i = blockIdx.x * 256 + threadIdx.x, w = blockIdx.y;
+  if (i >= q.B) return;
+  const int t = q.t[i];
+  if (t <= 0 || t >= q.L || t % q.T != 0) return;
+  const float v = w < H ? q.h[(size_t)w * q.B + i] : q.c[(size_t)(w - H) * q.B + i];
+  q.snap_rec[((size_t)i * drqn_windows(q.L, q.T) + t / q.T) * SNAP + w] = v;
+}
+
+// Before k_drqn_store (which advances the ring): the listed episodes' snapshots 1 ..
+// ceil(n / T) - 1 into the slot k_drqn_store gives the episode, by the same rule.
+__global__ __launch_bounds__(256) void k_drqn_snap_store(MzDrqnSnapStore q) {
+  const int nfin = min(max(*q.fin_count, 0), q.B);
+  const int64_t head = q.ring[0];
+  const size_t per = (size_t)drqn_windows(q.L, q.T) * SNAP;
+  const int first = nfin > q.cap ? nfin - (int)q.cap : 0;
+  for (int k = first + blockIdx.x; k < nfin; k += gridDim.x) {
+    const int i = q.fin_id[k], n = q.fin_len[k];
+    if (i < 0 || i >= q.B || n < 1 || n > q.L || head < 0 || head >= q.cap) continue;
+    const int64_t slot = (head + k) % q.cap;
+    const float* src = q.snap_rec + (size_t)i * per;
+    float* dst = q.mem_state + (size_t)slot * per;
+    for (int e = SNAP + threadIdx.x; e < drqn_windows(n, q.T) * SNAP; e += blockDim.x)
+      dst[e] = src[e];
+  }
+}
+
+// k_drqn_sample's slots (the same draws), then per chosen episode one window j uniform over its
+// ceil(n / T) windows (a Philox stream of its own, keyed by the position in the batch), the window
+// directory and the row offsets: window e owns rows w_off[e] .. w_off[e] + m + 1.
+__global__ __launch_bounds__(WAVE) void k_drqn_win_sample(MzDrqnWinSample q) {
+  extern __shared__ int32_t chosen[];  // [E]
+  drqn_sample_body(q.s, chosen);
+  __syncthreads();
+  const int lane = threadIdx.x, E = q.s.E;
+  int32_t* w = q.wdir;
+  for (int e = lane; e < E; e += WAVE) {
+    const int n = w[MZ_DRQN_WDIR_LEN * E + e];
+    int b = 0, kb = 0, m = 0;
+    if (n >= 1) {
+      uint32_t r[4];
+      mz_philox(q.s.seed, MZ_DRQN_WINDOW_STREAM ^ ((uint64_t)(uint32_t)e << 32), q.s.counter, r);
+      const int j = (int)(((uint64_t)r[0] * (uint64_t)drqn_windows(n, q.T)) >> 32);
+      const int s = j * q.T;
+      b = s > q.K ? s - q.K : 0;
+      kb = s - b;
+      m = min(q.T, n - s);
+    }
+    w[MZ_DRQN_WDIR_B * E + e] = b;
+    w[MZ_DRQN_WDIR_K * E + e] = kb;
+    w[MZ_DRQN_WDIR_M * E + e] = m;
+  }
+  __syncthreads();
+  if (lane == 0) {
+    int64_t rows = 0, steps = 0;
+    for (int e = 0; e < E; ++e) {
+      const int m = w[MZ_DRQN_WDIR_M * E + e];
+      q.s.d_off[e] = rows;
+      rows += m > 0 ? m + MZ_DRQN_WIN_PAD : 0;
+      steps += m;
+    }
+    q.s.d_tot[0] = rows;
+    q.s.d_tot[1] = steps;
+  }
+}
+
+// window e of the directory; false where it is not one the sampler writes
+struct DrqnWindow {
+  int n, slot, b, kb, m;
+  int64_t off;
+};
+__device__ __forceinline__ bool drqn_window(const MzDrqnWin& q, const int e, DrqnWindow* w) {
+  w->slot = q.wdir[MZ_DRQN_WDIR_SLOT * q.E + e];
+  w->n = q.wdir[MZ_DRQN_WDIR_LEN * q.E + e];
+  w->b = q.wdir[MZ_DRQN_WDIR_B * q.E + e];
+  w->kb = q.wdir[MZ_DRQN_WDIR_K * q.E + e];
+  w->m = q.wdir[MZ_DRQN_WDIR_M * q.E + e];
+  w->off = q.w_off[e];
+  const int64_t rows = (int64_t)q.E * (min(q.T, q.L) + MZ_DRQN_WIN_PAD);
+  return w->n >= 1 && w->n <= q.L && w->slot >= 0 && w->slot < q.cap && w->m >= 1 && w->m <= q.T &&
+         w->b >= 0 && w->b % q.T == 0 && w->kb >= 0 && w->kb <= q.K &&
+         (int64_t)w->b + w->kb + w->m <= w->n && w->off >= 0 &&
+         w->off + w->m + MZ_DRQN_WIN_PAD <= rows;
+}
+
+// drqn_seq_fwd_body over steps b .. b + kb + m - 1 (the target: one more) of the window's episode
+// from the stored state (snapshot b / T; zero where b == 0 or there is no state memory), the same
+// lane layout and per-step arithmetic. The kb burn-in steps only advance the state. Rows: the
+// window's first row holds (c, h) entering the first training step, where the backward finds them;
+// training step i is row off + 1 + i; the target's q of step b + kb + m is in the guard row.
+__device__ __forceinline__ void drqn_win_fwd_body(const MzDrqnWin& q, const int e) {
+  __shared__ __attribute__((aligned(16))) float hs[H];
+  const int lane = threadIdx.x, u = lane & (H - 1), half = lane >> 5;
+  DrqnWindow w;
+  if (!drqn_window(q, e, &w)) return;
+  const int n = w.n, kb = w.kb;
+  const int64_t off = w.off;
+  const uint32_t* ep = q.mem + ((size_t)w.slot * (q.L + 1) + w.b) * ROW;
+  const int r0 = half * 2 * H + u, r1 = r0 + H;  // (i_u, f_u) or (g_u, o_u)
+  DrqnFwdLane lw;
+  drqn_fwd_lane(q.p, lane, lw);
+  const float* snap = (q.mem_state && w.b > 0)
+      ? q.mem_state + ((size_t)w.slot * drqn_windows(q.L, q.T) + w.b / q.T) * SNAP : nullptr;
+  float hb[H];
+#pragma unroll
+  for (int k = 0; k < H; ++k) hb[k] = snap ? snap[k] : 0.0f;
+  float c = snap ? snap[H + u] : 0.0f;
+  float h = snap ? snap[u] : 0.0f;
+  const int steps = kb + w.m + (q.target ? 1 : 0);
+  const float inv = q.target ? 0.0f : (float)(1.0 / (double)q.w_tot[1]);
+  const bool term = q.mem_term[w.slot] != 0;
+  double sq = 0.0;
+  for (int i = 0;; ++i) {
+    if (!q.target && i == kb) {  // the state entering the first training step
+      float* st = q.stash + (size_t)off * STASH;
+      if (!half) st[G4 + u] = c; else st[G4 + H + u] = h;
+    }
+    if (i >= steps) break;
+    const uint4 ra = *reinterpret_cast<const uint4*>(ep + (size_t)i * ROW);
+    const uint4 rb = *reinterpret_cast<const uint4*>(ep + (size_t)i * ROW + 4);
+    float v0, v1, q0, q1, q2, q3;
+    drqn_fwd_step(lw, ra, rb, hs, u, half, hb, c, h, v0, v1);
+    if (i < kb) continue;  // burn-in: no q, no loss term
+    drqn_fwd_head(lw, hb, q0, q1, q2, q3);
+    const int64_t R = off + 1 + (i - kb);
+    if (q.target) {
+      if (lane == 0) q.qmax[R] = fmaxf(fmaxf(q0, q1), fmaxf(q2, q3));
+      continue;
+    }
+    float* st = q.stash + (size_t)R * STASH;
+    st[r0] = v0;
+    st[r1] = v1;
+    if (!half) st[G4 + u] = c; else st[G4 + H + u] = h;
+    const int a = (int)rb.z & 3;
+    const float rew = __uint_as_float(rb.w);
+    const float qsel = a == 0 ? q0 : (a == 1 ? q1 : (a == 2 ? q2 : q3));
+    const bool last = w.b + i == n - 1;
+    const float y = (last && term) ? rew : fmaf(q.gamma, q.qmax[R + 1], rew);
+    const float d = qsel - y;
+    sq += (double)d * (double)d;
+    if (lane == 0) {
+      q.qa[R] = qsel;
+      q.y[R] = y;
+      q.d[R] = 2.0f * d * inv;
+    }
+  }
+  if (!q.target && lane == 0) q.ep_loss[e] = sq;
+}
+
+__global__ __launch_bounds__(WAVE) void k_drqn_win_fwd(MzDrqnWin q) {
+  drqn_win_fwd_body(q, blockIdx.x);
+}
+
+// drqn_seq_bwd_body over the window's m training steps: the step before the first is the entry
+// row, so every step finds (c, h) of its predecessor one row up; nothing flows into the burn-in.
+__device__ __forceinline__ void drqn_win_bwd_body(const MzDrqnWin& q, const int e) {
+  __shared__ __attribute__((aligned(16))) float dzs[G4];
+  const int lane = threadIdx.x, u = lane & (H - 1), half = lane >> 5;
+  float* gp = q.gpart + (size_t)e * MZ_DRQN_PARAMS;
+  DrqnWindow w;
+  if (!drqn_window(q, e, &w)) {
+    for (int k = lane; k < MZ_DRQN_PARAMS; k += WAVE) gp[k] = 0.0f;
+    return;
+  }
+  const uint32_t* ep = q.mem + ((size_t)w.slot * (q.L + 1) + w.b + w.kb) * ROW;
+  DrqnBwdLane g;
+  drqn_bwd_lane(q.p, u, half, g);
+  for (int t = w.m - 1; t >= 0; --t) {
+    const int64_t R = w.off + 1 + t;
+    const float* st = q.stash + (size_t)R * STASH;
+    float cp, hp[H];
+    drqn_bwd_prev(st, u, cp, hp);
+    const uint4 ra = *reinterpret_cast<const uint4*>(ep + (size_t)t * ROW);
+    const uint4 rb = *reinterpret_cast<const uint4*>(ep + (size_t)t * ROW + 4);
+    drqn_bwd_step(g, st, cp, hp, ra, rb, q.d[R], dzs, u, half);
+  }
+  drqn_bwd_write(g, gp, lane);
+}
+
+__global__ __launch_bounds__(WAVE) void k_drqn_win_bwd(MzDrqnWin q) {
+  drqn_win_bwd_body(q, blockIdx.x);
+}
+
 }  // namespace
 
 hipError_t mz_launch_drqn_act(const MzDrqnAct& q, hipStream_t s) {
@@ -735,6 +999,33 @@ hipError_t mz_launch_drqn_seq_backward(const MzDrqnSeq& q, hipStream_t s) {
 
 hipError_t mz_launch_drqn_reduce(const MzDrqnReduce& q, hipStream_t s) {
   hipLaunchKernelGGL(k_drqn_reduce, dim3((MZ_DRQN_PARAMS + 255) / 256), dim3(256), 0, s, q);
+  return hipGetLastError();
+}
+
+// ---- replay windows -------------------------------------------------------------------------
+hipError_t mz_launch_drqn_snapshot(const MzDrqnSnap& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_snapshot, dim3((q.B + 255) / 256, SNAP), dim3(256), 0, s, q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_snap_store(const MzDrqnSnapStore& q, hipStream_t s) {
+  const int blocks = q.B < 2048 ? q.B : 2048;
+  hipLaunchKernelGGL(k_drqn_snap_store, dim3(blocks), dim3(256), 0, s, q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_window_sample(const MzDrqnWinSample& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_win_sample, dim3(1), dim3(WAVE), (size_t)q.s.E * sizeof(int32_t), s, q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_window_forward(const MzDrqnWin& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_win_fwd, dim3(q.E), dim3(WAVE), 0, s, q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_window_backward(const MzDrqnWin& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_win_bwd, dim3(q.E), dim3(WAVE), 0, s, q);
   return hipGetLastError();
 }
 

@@ -203,6 +203,48 @@ hipError_t mz_launch_drqn_seq_forward(const MzDrqnSeq& q, hipStream_t s);
 hipError_t mz_launch_drqn_seq_backward(const MzDrqnSeq& q, hipStream_t s);
 hipError_t mz_launch_drqn_reduce(const MzDrqnReduce& q, hipStream_t s);
 
+// Replay windows of T steps with stored state and K burn-in steps. A state snapshot is 64 f32
+// (h[32], c[32]); an episode's snapshot j is the state before it acted at step j T (entry 0 is
+// never written: zero by definition). The window directory wdir is int32 [5][E]:
+#define MZ_DRQN_SNAP 64
+#define MZ_DRQN_WDIR_SLOT 0     // ring slot
+#define MZ_DRQN_WDIR_LEN 1      // the episode's length n
+#define MZ_DRQN_WDIR_B 2        // first unrolled step b = max(0, j T - K)
+#define MZ_DRQN_WDIR_K 3        // burn-in steps k = j T - b
+#define MZ_DRQN_WDIR_M 4        // training steps m = min(T, n - j T)
+#define MZ_DRQN_WIN_PAD 2       // a window's rows: the entry-state row, m step rows, the guard row
+struct MzDrqnSnap {
+  int B, L, T;
+  const int32_t* t; const float *h, *c;      // [B]; [32][B]
+  float* snap_rec;                           // [B][ceil(L / T)][64]
+};
+struct MzDrqnSnapStore {
+  int B, L, T;
+  const int32_t* fin_id; const int32_t* fin_len; const int32_t* fin_count;
+  const float* snap_rec; int64_t cap; float* mem_state;  // [cap][ceil(L / T)][64]
+  const int64_t* ring;
+};
+struct MzDrqnWinSample {
+  MzDrqnSample s;                            // s.d_slot / s.d_len: wdir's first two rows
+  int T, K;
+  int32_t* wdir;
+};
+struct MzDrqnWin {
+  MzDrqnNet p;
+  int target, E, L, T, K; int64_t cap; float gamma;
+  const uint32_t* mem; const int32_t* mem_term;
+  const float* mem_state;                    // null: every window starts from zero state
+  const int32_t* wdir; const int64_t* w_off; const int64_t* w_tot;  // rows, training steps
+  float* qmax;                               // [E (T + 2)] rows, as MzDrqnSeq's
+  float* stash; float* qa; float* y; float* d; double* ep_loss;
+  float* gpart;
+};
+hipError_t mz_launch_drqn_snapshot(const MzDrqnSnap& q, hipStream_t s);
+hipError_t mz_launch_drqn_snap_store(const MzDrqnSnapStore& q, hipStream_t s);
+hipError_t mz_launch_drqn_window_sample(const MzDrqnWinSample& q, hipStream_t s);
+hipError_t mz_launch_drqn_window_forward(const MzDrqnWin& q, hipStream_t s);
+hipError_t mz_launch_drqn_window_backward(const MzDrqnWin& q, hipStream_t s);
+
 // Populations: P independent learners over B = P b instances, learner p owning the block
 // [p b, (p + 1) b). Parameters, gradients and moments are flat [P][MZ_DRQN_PARAMS] f32, a row in
 // state_dict order. Each struct holds learner 0's single-learner view; the kernels move it to

@@ -51,7 +51,9 @@ EXPORTS = ["mz_last_error", "mz_device_count", "mz_create", "mz_destroy", "mz_lo
            "mz_head_loss_backward_workspace_floats", "mz_adamw_groups",
            "mz_ppo_act", "mz_ppo_scan", "mz_ppo_finish", "mz_ppo_head_loss", "mz_rf_act", "mz_rf_finish",
            "mz_rf_head_loss", "mz_drqn_act", "mz_drqn_store", "mz_drqn_sample",
-           "mz_drqn_seq_forward", "mz_drqn_seq_backward", "mz_drqn_pop_act", "mz_drqn_pop_store",
+           "mz_drqn_seq_forward", "mz_drqn_seq_backward", "mz_drqn_snapshot", "mz_drqn_snap_store",
+           "mz_drqn_window_sample", "mz_drqn_window_forward", "mz_drqn_window_backward",
+           "mz_drqn_pop_act", "mz_drqn_pop_store",
            "mz_drqn_pop_sample", "mz_drqn_pop_seq_forward", "mz_drqn_pop_seq_backward",
            "mz_drqn_pop_sync", "mz_adamw_pop", "mz_qact_prepare", "mz_qact",
            "mz_qact_workspace_floats", "mz_qtab_states", "mz_qtab_act", "mz_qtab_update",
@@ -194,6 +196,12 @@ def load(build_if_missing=True):
     L.mz_drqn_seq_forward.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
                                       C.c_float] + [vp] * 13
     L.mz_drqn_seq_backward.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64] + [vp] * 12
+    L.mz_drqn_snapshot.argtypes = [C.c_int32] * 4 + [vp] * 5
+    L.mz_drqn_snap_store.argtypes = [C.c_int32] * 4 + [vp] * 4 + [C.c_int64] + [vp] * 3
+    L.mz_drqn_window_sample.argtypes = [C.c_uint64, C.c_uint64] + [C.c_int32] * 5 + \
+        [C.c_int64, C.c_int64] + [vp] * 6
+    L.mz_drqn_window_forward.argtypes = [vp] + [C.c_int32] * 6 + [C.c_int64, C.c_float] + [vp] * 13
+    L.mz_drqn_window_backward.argtypes = [vp] + [C.c_int32] * 5 + [C.c_int64] + [vp] * 11
     L.mz_drqn_pop_act.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, vp, C.c_int32,
                                   vp, C.c_uint64] + [vp] * 8
     L.mz_drqn_pop_store.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32] + [vp] * 6 + \

@@ -24,7 +24,9 @@ DQNAgent   the reference's constructor and method names. The reference leaves th
      x_n); loss = mean over all steps of (Q_t[a_t] - y_t)^2, no gradient through y; the
      reference's clamp_(-1, 1) per element and AdamW;
   6. nothing happens until the memory holds `batch_size` episodes.
-Truncated windows, burn-in and stored recurrent state are out of scope.
+window_td_loss is the loss of the vectorised trainer's replay windows (its departures 7-9: fixed
+windows of T steps, stored recurrent state, burn-in) for one env's code; DQNAgent itself keeps
+training on whole episodes.
 """
 import math
 import random
@@ -77,6 +79,14 @@ class DQN(nn.Module):
             out.append(self.fc(h))
         return torch.stack(out, dim=1)
 
+    def unroll_from(self, x, h, c):
+        """unroll() from the state (h, c) [batch, hidden] -> (q [batch, seq, actions], h, c)."""
+        out = []
+        for i in range(x.size(1)):
+            h, c = self.lstm_cell(x[:, i, :], (h, c))
+            out.append(self.fc(h))
+        return torch.stack(out, dim=1), h, c
+
 
 def td_loss(source, target, episodes, gamma):
     """The episode-batch loss (semantics 5). episodes: (x [n + 1, 6], a [n] long, r [n], term)."""
@@ -90,6 +100,30 @@ def td_loss(source, target, episodes, gamma):
                 y[n - 1] = r[n - 1]
         total = total + ((q.gather(1, a[:, None]).squeeze(1) - y) ** 2).sum()
         steps += n
+    return total / steps
+
+
+def window_td_loss(source, target, windows, gamma):
+    """The loss of a batch of replay windows (trainers/drqn_trainer.py, departure 9). A window is
+    (x [k + m + 1, 6], a [m] long, r [m], h0 [32], c0 [32], k, term): the observations of steps
+    b .. s + m, the actions and rewards of the m training steps s .. s + m - 1, the state both nets
+    start from at step b, the k = s - b burn-in steps, and term = the last training step is the
+    last step of a terminated episode (its y is r alone). Burn-in steps carry no loss term and no
+    gradient flows into them or through the state that enters step s. loss = sum (Q_t[a_t] -
+    y_t)^2 / sum m."""
+    total, steps = 0.0, 0
+    for x, a, r, h0, c0, k, term in windows:
+        m = a.shape[0]
+        h, c = h0[None], c0[None]
+        with torch.no_grad():
+            if k:
+                _, h, c = source.unroll_from(x[None, :k], h, c)
+            y = r + gamma * target.unroll_from(x[None], h0[None], c0[None])[0][0, k + 1:].max(dim=1)[0]
+            if term:
+                y[m - 1] = r[m - 1]
+        q = source.unroll_from(x[None, k:k + m], h, c)[0][0]
+        total = total + ((q.gather(1, a[:, None]).squeeze(1) - y) ** 2).sum()
+        steps += m
     return total / steps
 
 

@@ -4,12 +4,17 @@ over obs6, whole episodes as the unit of replay) over a population of plain maze
   python -m mazerl.train_lstm_dqn --envs 4096 --dim 9 --steps 2000
 
 The reference has no trainer for this agent; the semantics are VectorRecurrentDQNTrainer's
-(trainers/drqn_trainer.py, six stated departures). Prints one JSON line with the training
+(trainers/drqn_trainer.py, its stated departures). Prints one JSON line with the training
 throughput and the greedy win-rate on fresh mazes before and after training, under the same
 evaluation seed.
 
   python -m mazerl.train_lstm_dqn --envs 4096 --dim 9 --learners 8 --seeds 0,1,2,3,4,5,6,7
   python -m mazerl.train_lstm_dqn --learners 4 --sweep lr=1e-3,3e-4,1e-4,3e-5 --sweep gamma=0.99
+
+--window T trains on one window of T steps per sampled episode instead of the whole episode,
+--burn-in K (a multiple of T) unrolls K steps before it without loss or gradient, --initial-state
+stored | zero starts from the recurrent state recorded while acting or from zero (departures 7-9;
+single learner only).
 
 --learners P trains P independent learners in one run (trainers/drqn_population.py), each on
 envs / P instances; --seeds and --sweep NAME=v1,v2,... (repeatable; NAME one of lr, gamma,
@@ -21,7 +26,7 @@ import json
 
 import torch
 
-from .trainers.drqn_trainer import VectorRecurrentDQNTrainer, evaluate_plain
+from .trainers.drqn_trainer import VectorRecurrentDQNTrainer, check_window, evaluate_plain
 from .vector_env import VectorMazeEnv
 
 
@@ -91,6 +96,12 @@ def parse_args(argv=None):
     ap.add_argument("--no-bank", action="store_true")
     ap.add_argument("--resume", default=None, help="checkpoint to continue from")
     ap.add_argument("--save", default=None, help="checkpoint written after training")
+    ap.add_argument("--window", type=int, default=None, metavar="T",
+                    help="train on replay windows of T steps (default: whole episodes)")
+    ap.add_argument("--burn-in", type=int, default=0, metavar="K",
+                    help="burn-in steps before a window, a multiple of --window")
+    ap.add_argument("--initial-state", choices=("stored", "zero"), default="stored",
+                    help="a window's starting state: the snapshot recorded while acting, or zero")
     ap.add_argument("--learners", type=int, default=None,
                     help="P independent learners in one run, each on envs / P instances")
     ap.add_argument("--sweep", action="append", default=None, metavar="NAME=v1,v2,...",
@@ -98,6 +109,12 @@ def parse_args(argv=None):
                          "eps-decay, target-update or seed; repeatable")
     ap.add_argument("--seeds", default=None, metavar="s1,s2,...", help="--sweep seed=...")
     a = ap.parse_args(argv)
+    try:
+        check_window(a.window, a.burn_in, a.initial_state)
+    except ValueError as e:
+        ap.error(str(e))
+    if a.learners is not None and a.window is not None:
+        ap.error("--window is not available with --learners (populations train on whole episodes)")
     if a.learners is None:
         if a.sweep or a.seeds:
             ap.error("--sweep / --seeds need --learners")
@@ -160,7 +177,8 @@ def main(argv=None):
         epsilon_decay=a.eps_decay, discount_factor=a.gamma, batch_size=a.batch,
         memory_size=a.memory, target_update_frequency=a.target_update,
         explore_actions=a.explore_actions, train_every=a.train_every, seed=a.seed,
-        bank=not a.no_bank, algorithm=a.algo)
+        bank=not a.no_bank, algorithm=a.algo, window=a.window, burn_in=a.burn_in,
+        initial_state=a.initial_state)
     if a.resume:
         from .checkpoint import load_checkpoint
         load_checkpoint(a.resume, tr)
@@ -175,7 +193,9 @@ def main(argv=None):
                       "envs": a.envs, "dim": a.dim, "vector_steps": a.steps, "train_seconds": secs,
                       "train_env_steps_per_s": a.envs * a.steps / secs, "episodes": tr.episodes,
                       "wins": tr.wins, "updates": tr.updates, "batch_episodes": a.batch,
-                      "seed": a.seed, "win_rate_greedy_untrained": before,
+                      "seed": a.seed, "window": a.window, "burn_in": a.burn_in,
+                      "initial_state": a.initial_state if a.window else None,
+                      "win_rate_greedy_untrained": before,
                       "win_rate_greedy": after, "eval_mazes": a.eval_mazes, "eval_steps": k}),
           flush=True)
     env.close()

@@ -16,6 +16,10 @@ Per vector step, with no host round trip once the memory holds a batch (csrc/mz_
            sequence forward (max_a Q'_t), the source net's (Q_t[a_t], y_t, residuals, the stash),
            mz_drqn_seq_backward (BPTT, gradients reduced in a fixed order into the flat gradient
            segments), then FlatAdamW (the reference's clamp_(-1, 1) + AdamW in one launch).
+With window=T the update trains on one window of T steps per sampled episode (departures 7-9):
+mz_drqn_snapshot runs before act, mz_drqn_snap_store before store, and the update is
+mz_drqn_window_sample / _forward / _backward; its row buffers hold E (T + 2) rows whatever the maze
+size and the burn-in are. With window=None (the default) none of these is launched.
 
 The reference defines the net, the gate order, eps = final + (start - final) exp(-steps / decay),
 episodes as the unit of replay sampled without replacement, the MSE loss, the clamp, AdamW at
@@ -39,7 +43,27 @@ state is resized to the batch and never restored). Six departures fix the semant
   6. cadence: one update per `train_every` vector steps once the memory holds >= batch_size
      episodes; target sync every `target_update_frequency` updates; the cosine schedule advances
      once per update.
-Training on truncated windows, burn-in and stored recurrent state (R2D2) are out of scope.
+Replay windows, stored recurrent state and burn-in (R2D2's way to train from replay) are the
+option window=T, burn_in=K, initial_state="stored" | "zero"; window=None is the trainer above:
+  7. state snapshots: the (h, c) an instance holds before it acts at episode step t = j T, j >= 1,
+     is kept with the episode as snapshot j (64 f32); snapshot 0 is zero by definition. An episode
+     of n steps has windows j = 0 .. ceil(n / T) - 1. The snapshots are the acting kernel's own
+     values, computed with the parameters of that moment: they go stale as the net trains, which
+     is what the burn-in is for. With initial_state="zero" none is recorded or stored;
+  8. the unit of a batch: the memory stays the ring of whole episodes. A batch is E distinct
+     episodes chosen with exactly mz_drqn_sample's draws for the same (seed, update count), then
+     one window j per chosen episode, uniform over its ceil(n / T) windows, from a Philox stream of
+     its own keyed by (seed, update count, position in the batch). Windows are therefore uniform
+     within an episode, not over the memory: a step of a short episode is trained on more often;
+  9. the loss of a window: s = j T, m = min(T, n - s) training steps, b = max(0, s - K), k = s - b
+     burn-in steps. Both nets start at step b from the same state (snapshot b / T when "stored",
+     zero when "zero" or b = 0); the source unrolls x_b .. x_{s+m-1}, the target x_b .. x_{s+m},
+     each with its own parameters. The burn-in steps carry no loss term and no gradient flows into
+     them or through the state that enters step s. y_t = r_t + gamma max_a Q'_{t+1}[a] for the
+     training steps, r_t alone only at t = n - 1 of a terminated episode (a window that ends
+     before the episode does bootstraps from x_{s+m}); loss = sum (Q_t[a_t] - y_t)^2 / sum m.
+K must be a multiple of T. Overlapping windows (a stride other than T) are out of scope, and so
+are windows in VectorRecurrentDQNPopulation, which takes no such argument.
 """
 import ctypes as C
 
@@ -64,6 +88,18 @@ def param_ptrs(net):
     return (C.c_void_p * 6)(*[p.data_ptr() for p in ps])
 
 
+def check_window(window, burn_in, initial_state):
+    """The replay-window arguments' rules (departures 7-9); ValueError otherwise."""
+    ints = all(isinstance(v, int) and not isinstance(v, bool) for v in (burn_in,) +
+               (() if window is None else (window,)))
+    if not ints or initial_state not in ("stored", "zero") or burn_in < 0 or \
+            (window is None and burn_in != 0) or \
+            (window is not None and (window < 1 or burn_in % window != 0)):
+        raise ValueError("window: None or an int >= 1; burn_in: an int >= 0, a multiple of the "
+                         "window, 0 without one; initial_state: 'stored' or 'zero' "
+                         f"(got {window!r}, {burn_in!r}, {initial_state!r})")
+
+
 class VectorRecurrentDQNTrainer(EpisodicTrainer):
     _FORMAT = FORMAT
     _SHAPE = ("L", "capacity")
@@ -73,7 +109,9 @@ class VectorRecurrentDQNTrainer(EpisodicTrainer):
     def __init__(self, env, device, lr=1e-3, starting_epsilon=0.9, final_epsilon=0.05,
                  epsilon_decay=1000.0, discount_factor=0.99, batch_size=32, memory_size=20000,
                  target_update_frequency=10, explore_actions=4, train_every=1, seed=0, bank=True,
-                 curriculum=False, growth=None, algorithm="r-prim", bank_candidates=1):
+                 curriculum=False, growth=None, algorithm="r-prim", bank_candidates=1, window=None,
+                 burn_in=0, initial_state="stored"):
+        check_window(window, burn_in, initial_state)
         if batch_size < 1 or memory_size < batch_size or train_every < 1 or \
                 target_update_frequency < 1 or explore_actions not in (1, 2, 3, 4):
             raise ValueError("batch_size >= 1, memory_size >= batch_size, train_every >= 1, "
@@ -98,6 +136,8 @@ class VectorRecurrentDQNTrainer(EpisodicTrainer):
         self.target_update_frequency = int(target_update_frequency)
         self.explore_actions, self.train_every = int(explore_actions), int(train_every)
         self.seed = int(seed)
+        self.window = None if window is None else int(window)
+        self.burn_in, self.initial_state = int(burn_in), initial_state
         self.steps_done = 0   # the eps clock
         self.counter = 0      # vector steps (the exploration draws' counter)
         self.updates = 0
@@ -117,8 +157,16 @@ class VectorRecurrentDQNTrainer(EpisodicTrainer):
         self.mem_len = torch.zeros(self.capacity, dtype=i32, **kw)
         self.mem_term = torch.zeros(self.capacity, dtype=i32, **kw)
         self.ring = torch.zeros(2, dtype=i64, **kw)  # head, count
-        # an update's directory and row buffers
-        rows = E * (L + 1)
+        # an update's directory and row buffers: whole episodes, or windows of m <= T steps
+        # (+ the entry-state row and the guard row), which the burn-in does not lengthen
+        rows = E * (L + 1) if self.window is None else E * (min(self.window, L) + 2)
+        if self.window is not None:
+            self.wdir = torch.zeros(5, E, dtype=i32, **kw)  # slot, n, b, k, m
+            self.snaps = (L - 1) // self.window + 1
+        self.stored = self.window is not None and initial_state == "stored"
+        if self.stored:
+            self.snap_rec = torch.zeros(B, self.snaps, 2 * HIDDEN, dtype=f32, **kw)
+            self.mem_state = torch.zeros(self.capacity, self.snaps, 2 * HIDDEN, dtype=f32, **kw)
         self.d_slot = torch.zeros(E, dtype=i32, **kw)
         self.d_len = torch.zeros(E, dtype=i32, **kw)
         self.d_off = torch.zeros(E, dtype=i64, **kw)
@@ -144,6 +192,10 @@ class VectorRecurrentDQNTrainer(EpisodicTrainer):
         env = self.env
         eps = min(max(self.epsilon(), 0.0), 1.0)
         self.steps_done += 1
+        if self.stored:
+            N.check(self.lib.mz_drqn_snapshot(
+                HIDDEN, env.num_envs, self.L, self.window, self.t.data_ptr(), self.h.data_ptr(),
+                self.c.data_ptr(), self.snap_rec.data_ptr(), self._stream()))
         N.check(self.lib.mz_drqn_act(
             self._ps, HIDDEN, env.obs6.data_ptr(), env.num_envs, self.L, eps, self.explore_actions,
             self.seed & U64, self.counter & U64, self.t.data_ptr(), self.h.data_ptr(),
@@ -156,6 +208,11 @@ class VectorRecurrentDQNTrainer(EpisodicTrainer):
         self.r64.copy_(env.reward)
         self._scan(self.r64, env.terminated, env.truncated, self.rec_r,
                    self.pool[0:].data_ptr(), self.pool[1:].data_ptr())
+        if self.stored:  # (reads the ring's head, which mz_drqn_store advances)
+            N.check(self.lib.mz_drqn_snap_store(
+                HIDDEN, B, L, self.window, self.fin_id.data_ptr(), self.fin_len.data_ptr(),
+                self.fin_count.data_ptr(), self.snap_rec.data_ptr(), self.capacity,
+                self.mem_state.data_ptr(), self.ring.data_ptr(), st))
         N.check(self.lib.mz_drqn_store(
             env.obs6.data_ptr(), env.terminated.data_ptr(), B, L, self.fin_id.data_ptr(),
             self.fin_len.data_ptr(), self.fin_count.data_ptr(), self.rec_x.data_ptr(),
@@ -164,7 +221,15 @@ class VectorRecurrentDQNTrainer(EpisodicTrainer):
 
     def sample(self):
         """E distinct slots and the directory (d_slot, d_len, d_off, d_tot), keyed by the update
-        count."""
+        count; windowed: the same slots, one window each and the window directory (wdir, d_off,
+        d_tot)."""
+        if self.window is not None:
+            N.check(self.lib.mz_drqn_window_sample(
+                self.seed & U64, self.updates & U64, HIDDEN, self.batch_size, self.L, self.window,
+                self.burn_in, self.capacity, self.filled, self.ring.data_ptr(),
+                self.mem_len.data_ptr(), self.wdir.data_ptr(), self.d_off.data_ptr(),
+                self.d_tot.data_ptr(), self._stream()))
+            return
         N.check(self.lib.mz_drqn_sample(
             self.seed & U64, self.updates & U64, self.batch_size, self.L, self.capacity,
             self.filled, self.ring.data_ptr(), self.mem_len.data_ptr(), self.d_slot.data_ptr(),
@@ -177,6 +242,10 @@ class VectorRecurrentDQNTrainer(EpisodicTrainer):
         dirs = (self.d_slot.data_ptr(), self.d_len.data_ptr(), self.d_off.data_ptr(),
                 self.d_tot.data_ptr())
         self.opt.param_groups[0]["lr"].fill_(float(lr))
+        if self.window is not None:
+            self._window_update(st)
+            self.opt.step()
+            return
         N.check(self.lib.mz_drqn_seq_forward(
             self._pt, HIDDEN, 1, E, L, self.capacity, self.gamma, self.mem.data_ptr(),
             self.mem_term.data_ptr(), *dirs, self.qmax.data_ptr(), None, None, None, None, None,
@@ -190,6 +259,23 @@ class VectorRecurrentDQNTrainer(EpisodicTrainer):
             self.stash.data_ptr(), self.d.data_ptr(), self.ep_loss.data_ptr(),
             self.gpart.data_ptr(), self._pg, self.loss.data_ptr(), st))
         self.opt.step()
+
+    def _window_update(self, st):
+        E, L, T, K = self.batch_size, self.L, self.window, self.burn_in
+        state = self.mem_state.data_ptr() if self.stored else None
+        dirs = (self.wdir.data_ptr(), self.d_off.data_ptr(), self.d_tot.data_ptr())
+        N.check(self.lib.mz_drqn_window_forward(
+            self._pt, HIDDEN, 1, E, L, T, K, self.capacity, self.gamma, self.mem.data_ptr(),
+            self.mem_term.data_ptr(), state, *dirs, self.qmax.data_ptr(), None, None, None, None,
+            None, st))
+        N.check(self.lib.mz_drqn_window_forward(
+            self._ps, HIDDEN, 0, E, L, T, K, self.capacity, self.gamma, self.mem.data_ptr(),
+            self.mem_term.data_ptr(), state, *dirs, self.qmax.data_ptr(), self.stash.data_ptr(),
+            self.qa.data_ptr(), self.y.data_ptr(), self.d.data_ptr(), self.ep_loss.data_ptr(), st))
+        N.check(self.lib.mz_drqn_window_backward(
+            self._ps, HIDDEN, E, L, T, K, self.capacity, self.mem.data_ptr(), *dirs,
+            self.stash.data_ptr(), self.d.data_ptr(), self.ep_loss.data_ptr(),
+            self.gpart.data_ptr(), self._pg, self.loss.data_ptr(), st))
 
     def _update(self):
         if self.updates % 256 == 0 and int(self.stats[3]):  # (one look every 256 updates)
@@ -240,9 +326,15 @@ class VectorRecurrentDQNTrainer(EpisodicTrainer):
     def state_dict(self):
         """The run between two vector steps: both nets, the optimizer, (h, c), the in-flight
         records, the filled replay slots with head and count, the counters and the env
-        (_save_common)."""
+        (_save_common); a windowed trainer adds its settings and, when it stores state, the
+        in-flight and the filled slots' snapshots."""
         sd, o = self._save_common(), self.opt
         n = int(self.ring[1])
+        if self.window is not None:
+            sd["window"] = self._window_settings()
+        if self.stored:
+            sd["snap_rec"] = self.snap_rec.clone()
+            sd["mem_state"] = self.mem_state[:n].clone()
         sd.update({k: getattr(self, k).clone() for k in self._OWN})
         sd.update({k: getattr(self, k)[:n].clone() for k in ("mem", "mem_len", "mem_term")})
         sd["source"] = {k: v.clone() for k, v in self.source_net.state_dict().items()}
@@ -251,7 +343,17 @@ class VectorRecurrentDQNTrainer(EpisodicTrainer):
                      "step": o._step_buf.clone(), "lr": o.param_groups[0]["lr"].clone()}
         return sd
 
+    def _window_settings(self):
+        if self.window is None:
+            return None
+        return {"window": self.window, "burn_in": self.burn_in,
+                "initial_state": self.initial_state}
+
     def load_state_dict(self, sd):
+        # (a checkpoint from before the window option has no "window" key: window=None)
+        if sd.get("window") != self._window_settings():
+            raise ValueError(f"the checkpoint's replay windows {sd.get('window')} differ from this "
+                             f"trainer's {self._window_settings()}")
         self._load_common(sd)
         with torch.no_grad():
             self.source_net.load_state_dict(sd["source"])
@@ -266,6 +368,9 @@ class VectorRecurrentDQNTrainer(EpisodicTrainer):
         n = sd["mem"].shape[0]
         for k in ("mem", "mem_len", "mem_term"):
             getattr(self, k)[:n].copy_(sd[k])
+        if self.stored:
+            self.snap_rec.copy_(sd["snap_rec"])
+            self.mem_state[:n].copy_(sd["mem_state"])
 
 
 def evaluate_plain(learner, num_mazes, dim, algorithm="r-prim", seed=0x7E57, toroidal=False,
