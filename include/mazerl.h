@@ -912,6 +912,68 @@ int mz_drqn_pop_seq_backward(const float* params_dev, int32_t hidden, int32_t P,
                              const float* d_dev, const double* ep_loss_dev, float* gpart_dev,
                              float* grads_dev, float* loss_dev, void* stream);
 
+/* ---- Replay windows in a population ------------------------------------------------------------
+ * Learner p is mz_drqn_window_* on its rows with (T, K_p, stored or zero state), bit for bit. T is
+ * shared by the population and fixes the layouts; burn_in_dev (int32 [P]) holds the K_p, K_max is
+ * their largest, stored_dev (int32 [P]) says which learners read the state memory. mz_drqn_snapshot
+ * is called as it is with B = P b. Every entry point refuses a null pointer, P < 1, b < 1, E < 1,
+ * T < 1, K_max < 0, K_max % T != 0, hidden != 32, L < 1 and capacity < E with MZ_EINVAL before any
+ * GPU call, as far as it has the argument. A burn_in_dev[p] that is negative, not a multiple of T or
+ * above K_max cannot be refused by the host, which never reads the array: the caller validates the
+ * values before it uploads them. On the device such a learner gets no window (its directory has
+ * b = k = m = 0 and win_tot 0), none of its row buffers is written, its partials, its gradient row
+ * and its loss are zero, and every access stays within the buffers. */
+
+/* mz_drqn_snap_store for every learner, BEFORE mz_drqn_pop_store of the same vector step (whose
+ * ring launch advances the heads read here): learner p's run of the finished list by
+ * mz_drqn_pop_store's rule and validity tests, the snapshots of its k-th episode into slot
+ * (head_p + k) mod capacity of mem_state_dev [P][capacity][ceil(L / T)][64]. snap_rec_dev is
+ * [P b][ceil(L / T)][64], indexed by the global instance. A learner with no finished episode has
+ * nothing written; snapshot 0 and the entries past an episode's windows are never written. */
+int mz_drqn_pop_snap_store(int32_t hidden, int32_t P, int32_t b, int32_t L, int32_t T,
+                           const int32_t* fin_id_dev, const int32_t* fin_len_dev,
+                           const int32_t* fin_count_dev, const float* snap_rec_dev,
+                           int64_t capacity, float* mem_state_dev, const int64_t* ring_dev,
+                           void* stream);
+
+/* mz_drqn_window_sample per due learner, one wave each, keyed by (seed_dev[p], counter_dev[p])
+ * with K = burn_in_dev[p]. wdir_dev is int32 [P][5][E], one single-learner directory per learner;
+ * win_off_dev [P][E] counts rows within the learner's own buffers; win_tot_dev [P][2]. min_filled
+ * as in mz_drqn_pop_sample. */
+int mz_drqn_pop_window_sample(const uint64_t* seed_dev, const uint64_t* counter_dev,
+                              const int32_t* burn_in_dev, const int32_t* due_dev, int32_t hidden,
+                              int32_t P, int32_t E, int32_t L, int32_t T, int32_t K_max,
+                              int64_t capacity, int64_t min_filled, const int64_t* ring_dev,
+                              const int32_t* mem_len_dev, int32_t* wdir_dev, int64_t* win_off_dev,
+                              int64_t* win_tot_dev, void* stream);
+
+/* mz_drqn_window_forward per due learner: one wave per (learner, window). Learner p starts from
+ * mem_state_dev's snapshots where stored_dev[p] != 0 and from zero state otherwise; a NULL
+ * mem_state_dev is zero state for all (stored_dev may then be NULL). The row buffers are
+ * [P][E (min(T, L) + 2)] (stash_dev [...][192]), ep_loss_dev [P][E]. gamma_dev: f32 [P] (source
+ * mode; may be NULL with target != 0). */
+int mz_drqn_pop_window_forward(const float* params_dev, int32_t hidden, int32_t target, int32_t P,
+                               int32_t E, int32_t L, int32_t T, int32_t K_max, int64_t capacity,
+                               const float* gamma_dev, const int32_t* burn_in_dev,
+                               const int32_t* stored_dev, const int32_t* due_dev,
+                               const uint32_t* mem_dev, const int32_t* mem_term_dev,
+                               const float* mem_state_dev, const int32_t* wdir_dev,
+                               const int64_t* win_off_dev, const int64_t* win_tot_dev,
+                               float* qmax_dev, float* stash_dev, float* qa_dev, float* y_dev,
+                               float* d_dev, double* ep_loss_dev, void* stream);
+
+/* mz_drqn_window_backward per due learner: gpart_dev [P][E][5252]; each learner's E partials are
+ * summed in window order (float64, rounded once) into row p of grads_dev (flat [P][5252],
+ * overwritten) and loss_dev[p] = its sum of ep_loss / sum m. No atomics. */
+int mz_drqn_pop_window_backward(const float* params_dev, int32_t hidden, int32_t P, int32_t E,
+                                int32_t L, int32_t T, int32_t K_max, int64_t capacity,
+                                const int32_t* burn_in_dev, const int32_t* due_dev,
+                                const uint32_t* mem_dev, const int32_t* wdir_dev,
+                                const int64_t* win_off_dev, const int64_t* win_tot_dev,
+                                const float* stash_dev, const float* d_dev,
+                                const double* ep_loss_dev, float* gpart_dev, float* grads_dev,
+                                float* loss_dev, void* stream);
+
 /* The target sync (lstm_dqn_agent.py update_target: target.load_state_dict(source.state_dict()))
  * of the learners with mask_dev[p] != 0: row p of dst_dev <- row p of src_dev ([P][5252]). */
 int mz_drqn_pop_sync(const float* src_dev, float* dst_dev, const int32_t* mask_dev, int32_t P,

@@ -1849,8 +1849,103 @@ int mz_drqn_pop_seq_backward(const float* params_dev, int32_t hidden, int32_t P,
                   nullptr, gpart_dev},
                  P, nullptr, due_dev};
   MZ_HIP(mz_launch_drqn_pop_seq_backward(q, static_cast<hipStream_t>(stream)));
-  MzDrqnPopReduce r{P, E, gpart_dev, ep_loss_dev, dir_len_dev, dir_tot_dev, grads_dev, loss_dev,
+  MzDrqnPopReduce r{P, E, E, gpart_dev, ep_loss_dev, dir_len_dev, dir_tot_dev, grads_dev, loss_dev,
                     due_dev};
+  MZ_HIP(mz_launch_drqn_pop_reduce(r, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+// ---- replay windows in populations (mz_drqn.hip k_drqn_pop_snap_store .. k_drqn_pop_win_bwd) ------
+int mz_drqn_pop_snap_store(int32_t hidden, int32_t P, int32_t b, int32_t L, int32_t T,
+                           const int32_t* fin_id_dev, const int32_t* fin_len_dev,
+                           const int32_t* fin_count_dev, const float* snap_rec_dev,
+                           int64_t capacity, float* mem_state_dev, const int64_t* ring_dev,
+                           void* stream) {
+  if (!fin_id_dev || !fin_len_dev || !fin_count_dev || !snap_rec_dev || !mem_state_dev || !ring_dev)
+    return fail(MZ_EINVAL, "mz_drqn_pop_snap_store: null pointer");
+  if (int rc = drqn_pop_args("mz_drqn_pop_snap_store", hidden, P, b, "instances per learner"))
+    return rc;
+  if (int rc = drqn_win_args("mz_drqn_pop_snap_store", hidden, T, 0)) return rc;
+  if (L < 1 || capacity < 1)
+    return fail(MZ_EINVAL, "mz_drqn_pop_snap_store: L %d, capacity %lld", L, (long long)capacity);
+  StreamGuard g(stream);
+  MzDrqnPopSnapStore q{{P * b, L, T, fin_id_dev, fin_len_dev, fin_count_dev, snap_rec_dev,
+                        capacity, mem_state_dev, ring_dev},
+                       P, b};
+  MZ_HIP(mz_launch_drqn_pop_snap_store(q, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_drqn_pop_window_sample(const uint64_t* seed_dev, const uint64_t* counter_dev,
+                              const int32_t* burn_in_dev, const int32_t* due_dev, int32_t hidden,
+                              int32_t P, int32_t E, int32_t L, int32_t T, int32_t K_max,
+                              int64_t capacity, int64_t min_filled, const int64_t* ring_dev,
+                              const int32_t* mem_len_dev, int32_t* wdir_dev, int64_t* win_off_dev,
+                              int64_t* win_tot_dev, void* stream) {
+  if (!seed_dev || !counter_dev || !burn_in_dev || !ring_dev || !mem_len_dev || !wdir_dev ||
+      !win_off_dev || !win_tot_dev)
+    return fail(MZ_EINVAL, "mz_drqn_pop_window_sample: null pointer");
+  if (int rc = drqn_pop_args("mz_drqn_pop_window_sample", hidden, P, E, "E")) return rc;
+  if (int rc = drqn_win_args("mz_drqn_pop_window_sample", hidden, T, K_max)) return rc;
+  if (E > 8192 || L < 1 || capacity < E || min_filled > capacity || min_filled < E)
+    return fail(MZ_EINVAL, "mz_drqn_pop_window_sample: E %d (1..8192), L %d, capacity %lld, "
+                "smallest filled %lld", E, L, (long long)capacity, (long long)min_filled);
+  StreamGuard g(stream);
+  MzDrqnPopWinSample q{{{0, 0, E, L, capacity, ring_dev, mem_len_dev, wdir_dev, wdir_dev,
+                         win_off_dev, win_tot_dev}, T, K_max, wdir_dev},
+                       P, seed_dev, counter_dev, burn_in_dev, due_dev};
+  MZ_HIP(mz_launch_drqn_pop_window_sample(q, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_drqn_pop_window_forward(const float* params_dev, int32_t hidden, int32_t target, int32_t P,
+                               int32_t E, int32_t L, int32_t T, int32_t K_max, int64_t capacity,
+                               const float* gamma_dev, const int32_t* burn_in_dev,
+                               const int32_t* stored_dev, const int32_t* due_dev,
+                               const uint32_t* mem_dev, const int32_t* mem_term_dev,
+                               const float* mem_state_dev, const int32_t* wdir_dev,
+                               const int64_t* win_off_dev, const int64_t* win_tot_dev,
+                               float* qmax_dev, float* stash_dev, float* qa_dev, float* y_dev,
+                               float* d_dev, double* ep_loss_dev, void* stream) {
+  if (!params_dev || !burn_in_dev || !mem_dev || !mem_term_dev || !wdir_dev || !win_off_dev ||
+      !win_tot_dev || !qmax_dev || (mem_state_dev && !stored_dev) ||
+      (!target && (!gamma_dev || !stash_dev || !qa_dev || !y_dev || !d_dev || !ep_loss_dev)))
+    return fail(MZ_EINVAL, "mz_drqn_pop_window_forward: null pointer");
+  if (int rc = drqn_pop_args("mz_drqn_pop_window_forward", hidden, P, E, "E")) return rc;
+  if (int rc = drqn_win_args("mz_drqn_pop_window_forward", hidden, T, K_max)) return rc;
+  if (int rc = drqn_seq_args("mz_drqn_pop_window_forward", hidden, E, L, capacity)) return rc;
+  StreamGuard g(stream);
+  MzDrqnPopWin q{{mz_drqn_flat_net(params_dev), target ? 1 : 0, E, L, T, K_max, capacity, 0.0f,
+                  mem_dev, mem_term_dev, mem_state_dev, wdir_dev, win_off_dev, win_tot_dev,
+                  qmax_dev, stash_dev, qa_dev, y_dev, d_dev, ep_loss_dev, nullptr},
+                 P, gamma_dev, burn_in_dev, stored_dev, due_dev};
+  MZ_HIP(mz_launch_drqn_pop_window_forward(q, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_drqn_pop_window_backward(const float* params_dev, int32_t hidden, int32_t P, int32_t E,
+                                int32_t L, int32_t T, int32_t K_max, int64_t capacity,
+                                const int32_t* burn_in_dev, const int32_t* due_dev,
+                                const uint32_t* mem_dev, const int32_t* wdir_dev,
+                                const int64_t* win_off_dev, const int64_t* win_tot_dev,
+                                const float* stash_dev, const float* d_dev,
+                                const double* ep_loss_dev, float* gpart_dev, float* grads_dev,
+                                float* loss_dev, void* stream) {
+  if (!params_dev || !burn_in_dev || !mem_dev || !wdir_dev || !win_off_dev || !win_tot_dev ||
+      !stash_dev || !d_dev || !ep_loss_dev || !gpart_dev || !grads_dev || !loss_dev)
+    return fail(MZ_EINVAL, "mz_drqn_pop_window_backward: null pointer");
+  if (int rc = drqn_pop_args("mz_drqn_pop_window_backward", hidden, P, E, "E")) return rc;
+  if (int rc = drqn_win_args("mz_drqn_pop_window_backward", hidden, T, K_max)) return rc;
+  if (int rc = drqn_seq_args("mz_drqn_pop_window_backward", hidden, E, L, capacity)) return rc;
+  StreamGuard g(stream);
+  MzDrqnPopWin q{{mz_drqn_flat_net(params_dev), 0, E, L, T, K_max, capacity, 0.0f, mem_dev,
+                  nullptr, nullptr, wdir_dev, win_off_dev, win_tot_dev, nullptr,
+                  const_cast<float*>(stash_dev), nullptr, nullptr, const_cast<float*>(d_dev),
+                  nullptr, gpart_dev},
+                 P, nullptr, burn_in_dev, nullptr, due_dev};
+  MZ_HIP(mz_launch_drqn_pop_window_backward(q, static_cast<hipStream_t>(stream)));
+  MzDrqnPopReduce r{P, E, 5 * E, gpart_dev, ep_loss_dev, wdir_dev + (size_t)MZ_DRQN_WDIR_M * E,
+                    win_tot_dev, grads_dev, loss_dev, due_dev};
   MZ_HIP(mz_launch_drqn_pop_reduce(r, static_cast<hipStream_t>(stream)));
   return MZ_OK;
 }

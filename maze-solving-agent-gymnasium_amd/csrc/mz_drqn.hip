@@ -35,7 +35,7 @@
 //   k_drqn_reduce    per parameter the partials summed over the episodes in index order (float64,
 //                    rounded once) into the net's gradient segments; the loss (float64, episode
 //                    order). No float atomics anywhere: two runs give the same bits.
-// Replay windows (window = T, burn_in = K; off by default, single learner only):
+// Replay windows (window = T, burn_in = K; off by default):
 //   k_drqn_snapshot    a launch of its own before k_drqn_act (whose code and bits stay as they
 //                      are): the state an instance acts from at t = j T, j >= 1, into its record.
 //   k_drqn_snap_store  before k_drqn_store: the finished episodes' snapshots into the ring slot
@@ -56,6 +56,13 @@
 // straddles two learners); store (<= 256, P) workgroups, learner p's run of the finished list
 // found by two binary searches; sample P waves; the sequence kernels P E waves; reduce and the
 // target sync (21, P). Waves of a learner that is not due exit at once.
+// Replay windows in a population (T shared, burn-in K_p and stored / zero state per learner): the
+// same rule. k_drqn_snapshot serves B = P b as it is; k_drqn_pop_snap_store (grid as the store's,
+// launched before it), k_drqn_pop_win_sample (P waves), k_drqn_pop_win_fwd / _bwd (P E waves) move
+// the window structs to learner p's rows; k_drqn_pop_reduce reads the m row of learner p's
+// directory block. A K_p that breaks the rule (negative, no multiple of T, above K_max) lives on
+// the device and cannot be refused: that learner's view gets K = -1, which no window passes, so
+// its batch has no window, nothing of its row buffers is written and its partials are zero.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -295,11 +302,16 @@ __device__ __forceinline__ int drqn_first_at_least(const int32_t* a, const int n
   return lo;
 }
 
+__device__ __forceinline__ void drqn_pop_run(const int32_t* fin_id, const int32_t* fin_count,
+                                             const int B, const int b, const int p, int* lo,
+                                             int* hi) {
+  const int nfin = min(max(*fin_count, 0), B);
+  *lo = drqn_first_at_least(fin_id, nfin, (int64_t)p * b);
+  *hi = drqn_first_at_least(fin_id, nfin, (int64_t)(p + 1) * b);
+}
 __device__ __forceinline__ void drqn_pop_run(const MzDrqnPopStore& q, const int p, int* lo,
                                              int* hi) {
-  const int nfin = min(max(*q.s.fin_count, 0), q.s.B);
-  *lo = drqn_first_at_least(q.s.fin_id, nfin, (int64_t)p * q.b);
-  *hi = drqn_first_at_least(q.s.fin_id, nfin, (int64_t)(p + 1) * q.b);
+  drqn_pop_run(q.s.fin_id, q.s.fin_count, q.s.B, q.b, p, lo, hi);
 }
 
 // workgroups (., p): k_drqn_store's body on learner p's run and learner p's ring. A learner with
@@ -754,7 +766,8 @@ __global__ __launch_bounds__(256) void k_drqn_reduce(MzDrqnReduce q) {
 }
 
 // workgroups (., p): learner p's E partials into row p of the flat [P][5252] gradient (the flat
-// order is the partials' order), and its loss
+// order is the partials' order), and its loss. Learner p's lengths are d_len + p ld: ld = E for the
+// [P][E] episode directory, 5 E for the m row of the [P][5][E] window directory.
 __global__ __launch_bounds__(256) void k_drqn_pop_reduce(MzDrqnPopReduce q) {
   const int p = blockIdx.y;
   if (q.due && q.due[p] == 0) return;
@@ -763,7 +776,8 @@ __global__ __launch_bounds__(256) void k_drqn_pop_reduce(MzDrqnPopReduce q) {
   if (k < MZ_DRQN_PARAMS)
     q.g[(size_t)p * MZ_DRQN_PARAMS + k] = drqn_reduce_grad(q.gpart + p * E * MZ_DRQN_PARAMS, q.E, k);
   if (k == 0)
-    q.loss[p] = drqn_reduce_loss(q.ep_loss + p * E, q.d_len + p * E, q.d_tot + 2 * (size_t)p, q.E);
+    q.loss[p] = drqn_reduce_loss(q.ep_loss + p * E, q.d_len + (size_t)p * q.ld,
+                                 q.d_tot + 2 * (size_t)p, q.E);
 }
 
 // the target sync of the learners flagged in mask: dst row <- src row
@@ -794,13 +808,17 @@ __global__ __launch_bounds__(256) void k_drqn_snapshot(MzDrqnSnap q) {
 
 // Before k_drqn_store (which advances the ring): the listed episodes' snapshots 1 ..
 // ceil(n / T) - 1 into the slot k_drqn_store gives the episode, by the same rule.
-__global__ __launch_bounds__(256) void k_drqn_snap_store(MzDrqnSnapStore q) {
-  const int nfin = min(max(*q.fin_count, 0), q.B);
+// The listed episodes fin_id / fin_len [0, nfin) as drqn_store_body takes them; workgroup blk of
+// nblk takes every nblk-th.
+__device__ __forceinline__ void drqn_snap_store_body(const MzDrqnSnapStore& q,
+                                                     const int32_t* fin_id, const int32_t* fin_len,
+                                                     const int nfin, const int blk,
+                                                     const int nblk) {
   const int64_t head = q.ring[0];
   const size_t per = (size_t)drqn_windows(q.L, q.T) * SNAP;
   const int first = nfin > q.cap ? nfin - (int)q.cap : 0;
-  for (int k = first + blockIdx.x; k < nfin; k += gridDim.x) {
-    const int i = q.fin_id[k], n = q.fin_len[k];
+  for (int k = first + blk; k < nfin; k += nblk) {
+    const int i = fin_id[k], n = fin_len[k];
     if (i < 0 || i >= q.B || n < 1 || n > q.L || head < 0 || head >= q.cap) continue;
     const int64_t slot = (head + k) % q.cap;
     const float* src = q.snap_rec + (size_t)i * per;
@@ -810,11 +828,31 @@ __global__ __launch_bounds__(256) void k_drqn_snap_store(MzDrqnSnapStore q) {
   }
 }
 
+__global__ __launch_bounds__(256) void k_drqn_snap_store(MzDrqnSnapStore q) {
+  drqn_snap_store_body(q, q.fin_id, q.fin_len, min(max(*q.fin_count, 0), q.B), blockIdx.x,
+                       gridDim.x);
+}
+
+// workgroups (., p), before k_drqn_pop_store: k_drqn_snap_store's body on learner p's run of the
+// finished list (k_drqn_pop_store's run), its ring and its state memory; snap_rec stays indexed by
+// the global instance. A learner with no finished episode writes nothing.
+__global__ __launch_bounds__(256) void k_drqn_pop_snap_store(MzDrqnPopSnapStore q) {
+  const int p = blockIdx.y;
+  int lo, hi;
+  drqn_pop_run(q.s.fin_id, q.s.fin_count, q.s.B, q.b, p, &lo, &hi);
+  if (hi <= lo) return;
+  MzDrqnSnapStore s = q.s;
+  s.mem_state += (size_t)p * s.cap * drqn_windows(s.L, s.T) * SNAP;
+  s.ring += 2 * (size_t)p;
+  drqn_snap_store_body(s, q.s.fin_id + lo, q.s.fin_len + lo, hi - lo, blockIdx.x, gridDim.x);
+}
+
 // k_drqn_sample's slots (the same draws), then per chosen episode one window j uniform over its
 // ceil(n / T) windows (a Philox stream of its own, keyed by the position in the batch), the window
-// directory and the row offsets: window e owns rows w_off[e] .. w_off[e] + m + 1.
-__global__ __launch_bounds__(WAVE) void k_drqn_win_sample(MzDrqnWinSample q) {
-  extern __shared__ int32_t chosen[];  // [E]
+// directory and the row offsets: window e owns rows w_off[e] .. w_off[e] + m + 1. K < 0 (never
+// from the host, which refuses it: a population learner whose device-side burn-in breaks the rule)
+// gives the batch no window: b = k = m = 0 throughout.
+__device__ __forceinline__ void drqn_win_sample_body(const MzDrqnWinSample& q, int32_t* chosen) {
   drqn_sample_body(q.s, chosen);
   __syncthreads();
   const int lane = threadIdx.x, E = q.s.E;
@@ -822,7 +860,7 @@ __global__ __launch_bounds__(WAVE) void k_drqn_win_sample(MzDrqnWinSample q) {
   for (int e = lane; e < E; e += WAVE) {
     const int n = w[MZ_DRQN_WDIR_LEN * E + e];
     int b = 0, kb = 0, m = 0;
-    if (n >= 1) {
+    if (n >= 1 && q.K >= 0) {
       uint32_t r[4];
       mz_philox(q.s.seed, MZ_DRQN_WINDOW_STREAM ^ ((uint64_t)(uint32_t)e << 32), q.s.counter, r);
       const int j = (int)(((uint64_t)r[0] * (uint64_t)drqn_windows(n, q.T)) >> 32);
@@ -847,6 +885,40 @@ __global__ __launch_bounds__(WAVE) void k_drqn_win_sample(MzDrqnWinSample q) {
     q.s.d_tot[0] = rows;
     q.s.d_tot[1] = steps;
   }
+}
+
+__global__ __launch_bounds__(WAVE) void k_drqn_win_sample(MzDrqnWinSample q) {
+  extern __shared__ int32_t chosen[];  // [E]
+  drqn_win_sample_body(q, chosen);
+}
+
+// learner p's burn-in where it keeps the rule (0 <= K_p <= K_max, a multiple of T), else -1, which
+// no window passes: the sampler then writes none and drqn_window refuses every one
+__device__ __forceinline__ int drqn_pop_burn_in(const int32_t* burn_in, const int p, const int T,
+                                                const int Kmax) {
+  const int K = burn_in[p];
+  return (K >= 0 && K <= Kmax && K % T == 0) ? K : -1;
+}
+
+// one wave per learner: k_drqn_win_sample's body on learner p's ring with its seed, update count
+// and burn-in; its directory block [5][E] is the single layout
+__global__ __launch_bounds__(WAVE) void k_drqn_pop_win_sample(MzDrqnPopWinSample q) {
+  extern __shared__ int32_t chosen[];  // [E]
+  const int p = blockIdx.x;
+  if (q.due && q.due[p] == 0) return;
+  MzDrqnWinSample w = q.w;
+  const size_t E = (size_t)w.s.E;
+  w.K = drqn_pop_burn_in(q.burn_in, p, w.T, q.w.K);
+  w.wdir += (size_t)p * 5 * E;
+  w.s.seed = q.seed[p];
+  w.s.counter = q.counter[p];
+  w.s.ring += 2 * (size_t)p;
+  w.s.mem_len += (size_t)p * w.s.cap;
+  w.s.d_slot = w.wdir + MZ_DRQN_WDIR_SLOT * E;
+  w.s.d_len = w.wdir + MZ_DRQN_WDIR_LEN * E;
+  w.s.d_off += p * E;
+  w.s.d_tot += 2 * (size_t)p;
+  drqn_win_sample_body(w, chosen);
 }
 
 // window e of the directory; false where it is not one the sampler writes
@@ -966,6 +1038,45 @@ __global__ __launch_bounds__(WAVE) void k_drqn_win_bwd(MzDrqnWin q) {
   drqn_win_bwd_body(q, blockIdx.x);
 }
 
+// learner p's view of a population's windowed update: its parameters, ring, state memory (only
+// where stored[p] != 0: otherwise zero state), directory block ([P][5][E]), row buffers
+// ([P][E (min(T, L) + 2)]), discount factor and burn-in
+__device__ __forceinline__ MzDrqnWin drqn_win_row(const MzDrqnPopWin& q, const int p) {
+  MzDrqnWin s = q.q;
+  const size_t E = (size_t)s.E, rows = E * (min(s.T, s.L) + MZ_DRQN_WIN_PAD);
+  s.p = drqn_net_row(q.q.p, p);
+  if (q.gamma) s.gamma = q.gamma[p];
+  s.K = drqn_pop_burn_in(q.burn_in, p, s.T, q.q.K);
+  s.mem += (size_t)p * s.cap * (s.L + 1) * ROW;
+  if (s.mem_term) s.mem_term += (size_t)p * s.cap;
+  s.mem_state = (s.mem_state && q.stored && q.stored[p] != 0)
+      ? s.mem_state + (size_t)p * s.cap * drqn_windows(s.L, s.T) * SNAP : nullptr;
+  s.wdir += p * 5 * E;
+  s.w_off += p * E;
+  s.w_tot += 2 * (size_t)p;
+  if (s.qmax) s.qmax += p * rows;
+  if (s.stash) s.stash += p * rows * STASH;
+  if (s.qa) s.qa += p * rows;
+  if (s.y) s.y += p * rows;
+  if (s.d) s.d += p * rows;
+  if (s.ep_loss) s.ep_loss += p * E;
+  if (s.gpart) s.gpart += p * E * MZ_DRQN_PARAMS;
+  return s;
+}
+
+// one wave per (learner, window); a learner that is not due exits at once
+__global__ __launch_bounds__(WAVE) void k_drqn_pop_win_fwd(MzDrqnPopWin q) {
+  const int p = blockIdx.x / q.q.E;
+  if (q.due && q.due[p] == 0) return;
+  drqn_win_fwd_body(drqn_win_row(q, p), blockIdx.x % q.q.E);
+}
+
+__global__ __launch_bounds__(WAVE) void k_drqn_pop_win_bwd(MzDrqnPopWin q) {
+  const int p = blockIdx.x / q.q.E;
+  if (q.due && q.due[p] == 0) return;
+  drqn_win_bwd_body(drqn_win_row(q, p), blockIdx.x % q.q.E);
+}
+
 }  // namespace
 
 hipError_t mz_launch_drqn_act(const MzDrqnAct& q, hipStream_t s) {
@@ -1064,6 +1175,28 @@ hipError_t mz_launch_drqn_pop_seq_backward(const MzDrqnPopSeq& q, hipStream_t s)
 hipError_t mz_launch_drqn_pop_reduce(const MzDrqnPopReduce& q, hipStream_t s) {
   hipLaunchKernelGGL(k_drqn_pop_reduce, dim3((MZ_DRQN_PARAMS + 255) / 256, q.P), dim3(256), 0, s,
                      q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_pop_snap_store(const MzDrqnPopSnapStore& q, hipStream_t s) {
+  const int blocks = q.b < 256 ? q.b : 256;
+  hipLaunchKernelGGL(k_drqn_pop_snap_store, dim3(blocks, q.P), dim3(256), 0, s, q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_pop_window_sample(const MzDrqnPopWinSample& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_pop_win_sample, dim3(q.P), dim3(WAVE),
+                     (size_t)q.w.s.E * sizeof(int32_t), s, q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_pop_window_forward(const MzDrqnPopWin& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_pop_win_fwd, dim3((unsigned)q.P * q.q.E), dim3(WAVE), 0, s, q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_pop_window_backward(const MzDrqnPopWin& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_pop_win_bwd, dim3((unsigned)q.P * q.q.E), dim3(WAVE), 0, s, q);
   return hipGetLastError();
 }
 

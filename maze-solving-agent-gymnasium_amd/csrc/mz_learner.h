@@ -273,8 +273,25 @@ struct MzDrqnPopSeq {
   const float* gamma; const int32_t* due;    // [P]
 };
 struct MzDrqnPopReduce {
-  int P, E; const float* gpart; const double* ep_loss; const int32_t* d_len; const int64_t* d_tot;
+  int P, E, ld;                              // ld: int32 words between two learners' d_len rows
+  const float* gpart; const double* ep_loss; const int32_t* d_len; const int64_t* d_tot;
   float* g; float* loss; const int32_t* due; // flat gradient [P][5252], [P], [P]
+};
+// Replay windows in a population: T is shared (it fixes the layouts), the burn-in K_p and whether
+// the state memory is read are per learner. The window directory is one [5][E] block per learner.
+struct MzDrqnPopSnapStore {
+  MzDrqnSnapStore s;                         // s.B = P b; mem_state [P][cap][ceil(L / T)][64], ring [P][2]
+  int P, b;
+};
+struct MzDrqnPopWinSample {
+  MzDrqnWinSample w;                         // wdir [P][5][E], d_off [P][E], d_tot [P][2]; w.K = K_max
+  int P;
+  const uint64_t* seed; const uint64_t* counter; const int32_t* burn_in; const int32_t* due;  // [P]
+};
+struct MzDrqnPopWin {
+  MzDrqnWin q;                               // row buffers [P][E (min(T, L) + 2)]; q.K = K_max
+  int P;
+  const float* gamma; const int32_t* burn_in; const int32_t* stored; const int32_t* due;  // [P]
 };
 hipError_t mz_launch_drqn_pop_act(const MzDrqnPopAct& q, hipStream_t s);
 hipError_t mz_launch_drqn_pop_store(const MzDrqnPopStore& q, hipStream_t s);
@@ -284,6 +301,10 @@ hipError_t mz_launch_drqn_pop_seq_backward(const MzDrqnPopSeq& q, hipStream_t s)
 hipError_t mz_launch_drqn_pop_reduce(const MzDrqnPopReduce& q, hipStream_t s);
 hipError_t mz_launch_drqn_pop_sync(const float* src, float* dst, const int32_t* mask, int P,
                                    hipStream_t s);
+hipError_t mz_launch_drqn_pop_snap_store(const MzDrqnPopSnapStore& q, hipStream_t s);
+hipError_t mz_launch_drqn_pop_window_sample(const MzDrqnPopWinSample& q, hipStream_t s);
+hipError_t mz_launch_drqn_pop_window_forward(const MzDrqnPopWin& q, hipStream_t s);
+hipError_t mz_launch_drqn_pop_window_backward(const MzDrqnPopWin& q, hipStream_t s);
 // mz_optim.hip: k_adamw's element arithmetic over [P][n] rows with per-learner lr / step / due
 hipError_t mz_launch_adamw_pop(float* p, float* m, float* v, float* g, int P, int64_t n,
                                const float* lr, float* step, const int32_t* due, double b1,

@@ -13,13 +13,19 @@ evaluation seed.
 
 --window T trains on one window of T steps per sampled episode instead of the whole episode,
 --burn-in K (a multiple of T) unrolls K steps before it without loss or gradient, --initial-state
-stored | zero starts from the recurrent state recorded while acting or from zero (departures 7-9;
-single learner only).
+stored | zero starts from the recurrent state recorded while acting or from zero (departures 7-9).
 
 --learners P trains P independent learners in one run (trainers/drqn_population.py), each on
 envs / P instances; --seeds and --sweep NAME=v1,v2,... (repeatable; NAME one of lr, gamma,
-eps-start, eps-final, eps-decay, target-update, seed; P values or one) set them apart. The final
-line then reports every learner's trained greedy win-rate on the same mazes, their mean and spread.
+eps-start, eps-final, eps-decay, target-update, seed, burn-in, initial-state; P values or one) set
+them apart. The final line then reports every learner's trained greedy win-rate on the same mazes,
+their mean and spread, and every learner's window settings.
+
+  python -m mazerl.train_lstm_dqn --dim 41 --learners 16 --window 40 --burn-in 40 \\
+      --sweep initial-state=stored,stored,...,zero,zero --seeds 0,1,...
+
+With --learners, --window T is shared by the population (it fixes the layouts and cannot be
+swept); --burn-in and --initial-state are per learner.
 """
 import argparse
 import json
@@ -30,11 +36,19 @@ from .trainers.drqn_trainer import VectorRecurrentDQNTrainer, check_window, eval
 from .vector_env import VectorMazeEnv
 
 
-# --sweep names -> (the constructor's argument, the value type)
+def state(v):
+    """An --initial-state value."""
+    if v not in ("stored", "zero"):
+        raise ValueError(v)
+    return v
+
+
+# --sweep names -> (the constructor's argument, the value type). --window is shared by the
+# population (it fixes the layouts) and stays out.
 SWEEPABLE = {"lr": ("lr", float), "gamma": ("discount_factor", float),
              "eps-start": ("starting_epsilon", float), "eps-final": ("final_epsilon", float),
              "eps-decay": ("epsilon_decay", float), "target-update": ("target_update_frequency", int),
-             "seed": ("seed", int)}
+             "seed": ("seed", int), "burn-in": ("burn_in", int), "initial-state": ("initial_state", state)}
 
 
 def parse_sweeps(sweeps, seeds, P):
@@ -113,8 +127,6 @@ def parse_args(argv=None):
         check_window(a.window, a.burn_in, a.initial_state)
     except ValueError as e:
         ap.error(str(e))
-    if a.learners is not None and a.window is not None:
-        ap.error("--window is not available with --learners (populations train on whole episodes)")
     if a.learners is None:
         if a.sweep or a.seeds:
             ap.error("--sweep / --seeds need --learners")
@@ -124,6 +136,8 @@ def parse_args(argv=None):
         ap.error("--envs must be a multiple of --learners >= 1")
     try:
         a.per_learner = parse_sweeps(a.sweep, a.seeds, a.learners)
+        for K in a.per_learner.get("burn_in", ()):  # every learner's K_p against the shared T
+            check_window(a.window, K, a.initial_state)
     except ValueError as e:
         ap.error(str(e))
     return a
@@ -136,12 +150,13 @@ def main_population(a):
                         algorithm=a.algo, seed=0x5EED0000, pos=False, done_list=False)
     kw = dict(lr=a.lr, starting_epsilon=a.eps_start, final_epsilon=a.eps_final,
               epsilon_decay=a.eps_decay, discount_factor=a.gamma,
-              target_update_frequency=a.target_update, seed=a.seed)
+              target_update_frequency=a.target_update, seed=a.seed, burn_in=a.burn_in,
+              initial_state=a.initial_state)
     kw.update(a.per_learner)
     tr = VectorRecurrentDQNPopulation(
         env, dev, learners=a.learners, batch_size=a.batch, memory_size=a.memory,
         explore_actions=a.explore_actions, train_every=a.train_every, bank=not a.no_bank,
-        algorithm=a.algo, **kw)
+        algorithm=a.algo, window=a.window, **kw)
     if a.resume:
         from .checkpoint import load_checkpoint
         load_checkpoint(a.resume, tr)
@@ -158,6 +173,7 @@ def main_population(a):
                       "train_env_steps_per_s": a.envs * a.steps / secs, "episodes": tr.episodes,
                       "wins": tr.wins, "updates": tr.updates, "batch_episodes": a.batch,
                       "per_learner": {k: v for k, v in a.per_learner.items()},
+                      "window": tr._window_settings(),  # T and every learner's K_p, S_p
                       "replay_bytes": tr.memory_bytes()["replay"],
                       "win_rate_greedy_untrained": before, "win_rate_greedy": after,
                       "win_rate_greedy_spread": spread(after), "eval_mazes": a.eval_mazes}),

@@ -27,6 +27,19 @@ cosine_lr in float64 as the single trainer, the due mask, the sync mask, the sam
 one small array, and a vector step makes no device -> host read (beyond the single trainer's look
 at the overflow counter every 256 updates).
 
+Replay windows (window=T, burn_in, initial_state; window=None, the default, is the population
+above: no new launch, the same bits, the same checkpoint keys). T is shared by the population: it
+fixes the layouts (ceil(L / T) snapshots per episode, row buffers [P][E (min(T, L) + 2)], a window
+directory [P][5][E]). burn_in and initial_state are per learner (a scalar or a length-P sequence),
+each K_p a multiple of T, checked before anything touches the GPU and uploaded once. Learner p is
+VectorRecurrentDQNTrainer(window=T, burn_in=K_p, initial_state=S_p) on its block, bit for bit
+(its departures 7-9): its episode draw is keyed by (seed_p, updates_p), its window draw by
+(seed_p, updates_p, position in the batch). mz_drqn_snapshot runs over all P b instances and the
+state memory [P][capacity][ceil(L / T)][64] exists when at least one learner is "stored"; a "zero"
+learner never reads it. A checkpoint then also holds T and the two per-learner lists and, when
+stored, snap_rec and each ring's filled slots of mem_state; it loads only into a population with
+the same window settings.
+
 curriculum="global" counts wins across all instances and would couple the learners: it is refused.
 With bank=False a learner's whole run is independent of the other learners, bit for bit. With the
 winner bank the maze a winner receives depends on how many instances of other learners won before
@@ -40,7 +53,7 @@ import torch
 from .. import _native as N
 from ..agents.lstm_dqn_agent import DQN, ETA_MIN, HIDDEN, T_MAX, epsilon_at
 from ..agents.rf_agent import cosine_lr
-from .drqn_trainer import EVAL_KEY, PARAMS, ROW, STASH, U64, _Evaluator
+from .drqn_trainer import EVAL_KEY, PARAMS, ROW, STASH, U64, _Evaluator, check_window
 from .episodic import EpisodicTrainer, episode_bound
 
 FORMAT = "mazerl.VectorRecurrentDQNPopulation/1"
@@ -70,14 +83,22 @@ def _signed(u):
     return u - (1 << 64) if u >> 63 else u
 
 
-def footprint(P, B, L, E, capacity):
-    """Bytes of the replay rings, the in-flight records, and an update's stash and row buffers."""
-    rows = E * (L + 1)
+def footprint(P, B, L, E, capacity, window=None, stored=False):
+    """Bytes of the replay rings, the in-flight records, and an update's stash and row buffers;
+    windowed: the row buffers hold E (min(T, L) + 2) rows, and with stored state the state memory
+    (P capacity ceil(L / T) snapshots of 256 B) and the in-flight snapshots are added."""
+    rows = E * (L + 1) if window is None else E * (min(window, L) + 2)
     ring = P * capacity * ((L + 1) * ROW * 4 + 8)
     records = B * ((L + 1) * 6 * 4 + L * 4 + L * 8)
     update = P * (rows * (STASH + 4) * 4 + E * (PARAMS * 4 + 8 + 16))
-    return {"replay": ring, "records": records, "update": update,
-            "total": ring + records + update}
+    out = {"replay": ring, "records": records, "update": update,
+           "total": ring + records + update}
+    if window is not None:
+        snaps = ((L - 1) // window + 1) * 2 * HIDDEN * 4 if stored else 0
+        out["state"], out["snap_rec"] = P * capacity * snaps, B * snaps
+        out["update"] += P * 5 * E * 4
+        out["total"] = ring + records + out["update"] + out["state"] + out["snap_rec"]
+    return out
 
 
 class _LearnerView:
@@ -103,13 +124,21 @@ class VectorRecurrentDQNPopulation(EpisodicTrainer):
     def __init__(self, env, device, learners=1, lr=1e-3, starting_epsilon=0.9, final_epsilon=0.05,
                  epsilon_decay=1000.0, discount_factor=0.99, batch_size=32, memory_size=20000,
                  target_update_frequency=10, explore_actions=4, train_every=1, seed=0, bank=True,
-                 curriculum=False, growth=None, algorithm="r-prim", bank_candidates=1):
+                 curriculum=False, growth=None, algorithm="r-prim", bank_candidates=1, window=None,
+                 burn_in=0, initial_state="stored"):
         P = int(learners)
         if P < 1 or env.num_envs % P:
             raise ValueError(f"env.num_envs {env.num_envs} must be a multiple of learners {P} >= 1")
         if curriculum is True or curriculum == "global":
             raise ValueError('curriculum="global" counts wins across all instances and would '
                              'couple the learners; use False or "per-instance"')
+        same = lambda v: v  # noqa: E731 (check_window wants the values as they were given)
+        self.burn_in = per_learner(burn_in, P, "burn_in", same)
+        self.initial_state = per_learner(initial_state, P, "initial_state", same)
+        for K, S in zip(self.burn_in, self.initial_state):
+            check_window(window, K, S)
+        self.window = None if window is None else int(window)
+        self.stored = [self.window is not None and S == "stored" for S in self.initial_state]
         self.tuf = per_learner(target_update_frequency, P, "target_update_frequency", int)
         if batch_size < 1 or memory_size < batch_size or train_every < 1 or min(self.tuf) < 1 or \
                 explore_actions not in (1, 2, 3, 4):
@@ -126,7 +155,7 @@ class VectorRecurrentDQNPopulation(EpisodicTrainer):
         self.explore_actions, self.train_every = int(explore_actions), int(train_every)
         B, E = env.num_envs, self.batch_size
         L = episode_bound(env.max_dim, env.toroidal)
-        need = footprint(P, B, L, E, self.capacity)
+        need = footprint(P, B, L, E, self.capacity, self.window, any(self.stored))
         dev = torch.device(device)
         if dev.type == "cuda":
             free, _ = torch.cuda.mem_get_info(dev)
@@ -134,6 +163,9 @@ class VectorRecurrentDQNPopulation(EpisodicTrainer):
                 raise MemoryError(
                     f"{P} learners x {self.capacity} episodes of {L + 1} rows need "
                     f"{need['replay'] / 2 ** 30:.2f} GiB of replay memory and "
+                    + (f"{need['state'] / 2 ** 30:.2f} GiB of state memory (mem_state) with "
+                       f"{need['snap_rec'] / 2 ** 30:.2f} GiB of in-flight snapshots (snap_rec) and "
+                       if any(self.stored) else "") +
                     f"{need['total'] / 2 ** 30:.2f} GiB in all; {free / 2 ** 30:.2f} GiB are free. "
                     "Lower memory_size or learners.")
         super().__init__(env, device, bank=bank, curriculum=curriculum, growth=growth,
@@ -175,7 +207,17 @@ class VectorRecurrentDQNPopulation(EpisodicTrainer):
         self.mem_len = torch.zeros(P, self.capacity, dtype=i32, **kw)
         self.mem_term = torch.zeros(P, self.capacity, dtype=i32, **kw)
         self.ring = torch.zeros(P, 2, dtype=i64, **kw)  # head, count
-        rows = E * (L + 1)
+        # an update's directory and row buffers: whole episodes, or windows of m <= T steps (+ the
+        # entry-state row and the guard row) whatever the burn-in is
+        rows = E * (L + 1) if self.window is None else E * (min(self.window, L) + 2)
+        if self.window is not None:
+            self.wdir = torch.zeros(P, 5, E, dtype=i32, **kw)  # per learner: slot, n, b, k, m
+            self.snaps = (L - 1) // self.window + 1
+            self.burn_in_dev = torch.tensor(self.burn_in, dtype=i32, **kw)
+            self.stored_dev = torch.tensor([int(s) for s in self.stored], dtype=i32, **kw)
+        if any(self.stored):
+            self.snap_rec = torch.zeros(B, self.snaps, 2 * HIDDEN, dtype=f32, **kw)
+            self.mem_state = torch.zeros(P, self.capacity, self.snaps, 2 * HIDDEN, dtype=f32, **kw)
         self.d_slot = torch.zeros(P, E, dtype=i32, **kw)
         self.d_len = torch.zeros(P, E, dtype=i32, **kw)
         self.d_off = torch.zeros(P, E, dtype=i64, **kw)
@@ -194,7 +236,8 @@ class VectorRecurrentDQNPopulation(EpisodicTrainer):
     # ---- per-learner access -------------------------------------------------------------------
     def memory_bytes(self):
         """The replay, record, stash and row-buffer footprint in bytes (footprint())."""
-        return footprint(self.P, self.env.num_envs, self.L, self.batch_size, self.capacity)
+        return footprint(self.P, self.env.num_envs, self.L, self.batch_size, self.capacity,
+                         self.window, any(self.stored))
 
     def epsilon(self, p):
         return epsilon_at(self.steps_done[p], self.starting_epsilon[p], self.final_epsilon[p],
@@ -275,6 +318,10 @@ class VectorRecurrentDQNPopulation(EpisodicTrainer):
         for p in range(self.P):
             self.steps_done[p] += 1
         self.eps_dev.copy_(torch.tensor(eps, dtype=torch.float32))
+        if any(self.stored):  # (all P b instances: a zero-state learner's snapshots are never read)
+            N.check(self.lib.mz_drqn_snapshot(
+                HIDDEN, env.num_envs, self.L, self.window, self.t.data_ptr(), self.h.data_ptr(),
+                self.c.data_ptr(), self.snap_rec.data_ptr(), self._stream()))
         N.check(self.lib.mz_drqn_pop_act(
             self.src.data_ptr(), HIDDEN, self.P, self.b, env.obs6.data_ptr(), self.L,
             self.eps_dev.data_ptr(), self.explore_actions, self.seed_dev.data_ptr(),
@@ -288,6 +335,11 @@ class VectorRecurrentDQNPopulation(EpisodicTrainer):
         self.r64.copy_(env.reward)
         self._scan(self.r64, env.terminated, env.truncated, self.rec_r,
                    self.pool[0:].data_ptr(), self.pool[1:].data_ptr())
+        if any(self.stored):  # (reads the rings' heads, which mz_drqn_pop_store advances)
+            N.check(self.lib.mz_drqn_pop_snap_store(
+                HIDDEN, self.P, self.b, self.L, self.window, self.fin_id.data_ptr(),
+                self.fin_len.data_ptr(), self.fin_count.data_ptr(), self.snap_rec.data_ptr(),
+                self.capacity, self.mem_state.data_ptr(), self.ring.data_ptr(), st))
         N.check(self.lib.mz_drqn_pop_store(
             env.obs6.data_ptr(), env.terminated.data_ptr(), self.P, self.b, self.L,
             self.fin_id.data_ptr(), self.fin_len.data_ptr(), self.fin_count.data_ptr(),
@@ -305,11 +357,20 @@ class VectorRecurrentDQNPopulation(EpisodicTrainer):
         self.upd.copy_(torch.from_numpy(buf))
 
     def sample(self, due):
-        """E distinct slots and the directory of every due learner, keyed by its update count."""
+        """E distinct slots and the directory of every due learner, keyed by its update count;
+        windowed: the same slots, one window each and the learner's window directory."""
+        filled = min(f for f, d in zip(self.filled, due) if d)
+        if self.window is not None:
+            N.check(self.lib.mz_drqn_pop_window_sample(
+                self.seed_dev.data_ptr(), self.cnt_dev.data_ptr(), self.burn_in_dev.data_ptr(),
+                self.due_dev.data_ptr(), HIDDEN, self.P, self.batch_size, self.L, self.window,
+                max(self.burn_in), self.capacity, filled, self.ring.data_ptr(),
+                self.mem_len.data_ptr(), self.wdir.data_ptr(), self.d_off.data_ptr(),
+                self.d_tot.data_ptr(), self._stream()))
+            return
         N.check(self.lib.mz_drqn_pop_sample(
             self.seed_dev.data_ptr(), self.cnt_dev.data_ptr(), self.due_dev.data_ptr(), self.P,
-            self.batch_size, self.L, self.capacity,
-            min(f for f, d in zip(self.filled, due) if d), self.ring.data_ptr(),
+            self.batch_size, self.L, self.capacity, filled, self.ring.data_ptr(),
             self.mem_len.data_ptr(), self.d_slot.data_ptr(), self.d_len.data_ptr(),
             self.d_off.data_ptr(), self.d_tot.data_ptr(), self._stream()))
 
@@ -320,6 +381,10 @@ class VectorRecurrentDQNPopulation(EpisodicTrainer):
         dirs = (self.d_slot.data_ptr(), self.d_len.data_ptr(), self.d_off.data_ptr(),
                 self.d_tot.data_ptr())
         due, gam = self.due_dev.data_ptr(), self.gamma_dev.data_ptr()
+        if self.window is not None:
+            self._window_update(due, gam, st)
+            self._adamw(due, st)
+            return
         N.check(self.lib.mz_drqn_pop_seq_forward(
             self.tgt.data_ptr(), HIDDEN, 1, P, E, L, self.capacity, gam, due, self.mem.data_ptr(),
             self.mem_term.data_ptr(), *dirs, self.qmax.data_ptr(), None, None, None, None, None,
@@ -332,10 +397,33 @@ class VectorRecurrentDQNPopulation(EpisodicTrainer):
             self.src.data_ptr(), HIDDEN, P, E, L, self.capacity, due, self.mem.data_ptr(), *dirs,
             self.stash.data_ptr(), self.d.data_ptr(), self.ep_loss.data_ptr(),
             self.gpart.data_ptr(), self.grad.data_ptr(), self.loss.data_ptr(), st))
+        self._adamw(due, st)
+
+    def _adamw(self, due, st):
         N.check(self.lib.mz_adamw_pop(
             self.src.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-            self.grad.data_ptr(), P, PARAMS, self.lr_dev.data_ptr(), self.step.data_ptr(), due,
-            BETAS[0], BETAS[1], ADAM_EPS, WEIGHT_DECAY, CLAMP, 1.0, 1, st))
+            self.grad.data_ptr(), self.P, PARAMS, self.lr_dev.data_ptr(), self.step.data_ptr(),
+            due, BETAS[0], BETAS[1], ADAM_EPS, WEIGHT_DECAY, CLAMP, 1.0, 1, st))
+
+    def _window_update(self, due, gam, st):
+        P, E, L, T, K = self.P, self.batch_size, self.L, self.window, max(self.burn_in)
+        state = self.mem_state.data_ptr() if any(self.stored) else None
+        burn, stored = self.burn_in_dev.data_ptr(), self.stored_dev.data_ptr()
+        dirs = (self.wdir.data_ptr(), self.d_off.data_ptr(), self.d_tot.data_ptr())
+        N.check(self.lib.mz_drqn_pop_window_forward(
+            self.tgt.data_ptr(), HIDDEN, 1, P, E, L, T, K, self.capacity, gam, burn, stored, due,
+            self.mem.data_ptr(), self.mem_term.data_ptr(), state, *dirs, self.qmax.data_ptr(),
+            None, None, None, None, None, st))
+        N.check(self.lib.mz_drqn_pop_window_forward(
+            self.src.data_ptr(), HIDDEN, 0, P, E, L, T, K, self.capacity, gam, burn, stored, due,
+            self.mem.data_ptr(), self.mem_term.data_ptr(), state, *dirs, self.qmax.data_ptr(),
+            self.stash.data_ptr(), self.qa.data_ptr(), self.y.data_ptr(), self.d.data_ptr(),
+            self.ep_loss.data_ptr(), st))
+        N.check(self.lib.mz_drqn_pop_window_backward(
+            self.src.data_ptr(), HIDDEN, P, E, L, T, K, self.capacity, burn, due,
+            self.mem.data_ptr(), *dirs, self.stash.data_ptr(), self.d.data_ptr(),
+            self.ep_loss.data_ptr(), self.gpart.data_ptr(), self.grad.data_ptr(),
+            self.loss.data_ptr(), st))
 
     def _update(self, due):
         if self.launches % 256 == 0 and int(self.stats[3]):  # (one look every 256 updates)
@@ -390,10 +478,30 @@ class VectorRecurrentDQNPopulation(EpisodicTrainer):
         for k in ("mem", "mem_len", "mem_term"):
             sd[k] = [getattr(self, k)[p, :n].clone() for p, n in enumerate(counts)]
         sd["learners"] = {k: [int(v) for v in getattr(self, k)] for k in self._LISTS}
+        if self.window is not None:
+            sd["window"] = self._window_settings()
+        if any(self.stored):
+            sd["snap_rec"] = self.snap_rec.clone()
+            sd["mem_state"] = [self.mem_state[p, :n].clone() for p, n in enumerate(counts)]
         return sd
 
+    def _window_settings(self):
+        """T and the two per-learner lists (None without windows)."""
+        if self.window is None:
+            return None
+        return {"window": self.window, "burn_in": list(self.burn_in),
+                "initial_state": list(self.initial_state)}
+
     def load_state_dict(self, sd):
+        # (a checkpoint from before the window option has no "window" key: window=None)
+        if sd.get("window") != self._window_settings():
+            raise ValueError(f"the checkpoint's replay windows {sd.get('window')} differ from this "
+                             f"population's {self._window_settings()}")
         self._load_common(sd)
+        if any(self.stored):
+            self.snap_rec.copy_(sd["snap_rec"])
+            for p, part in enumerate(sd["mem_state"]):
+                self.mem_state[p, :part.shape[0]].copy_(part)
         for k in self._OWN:
             getattr(self, k).copy_(sd[k])
         for k in ("mem", "mem_len", "mem_term"):

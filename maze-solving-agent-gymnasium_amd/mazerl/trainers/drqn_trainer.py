@@ -62,8 +62,9 @@ option window=T, burn_in=K, initial_state="stored" | "zero"; window=None is the 
      them or through the state that enters step s. y_t = r_t + gamma max_a Q'_{t+1}[a] for the
      training steps, r_t alone only at t = n - 1 of a terminated episode (a window that ends
      before the episode does bootstraps from x_{s+m}); loss = sum (Q_t[a_t] - y_t)^2 / sum m.
-K must be a multiple of T. Overlapping windows (a stride other than T) are out of scope, and so
-are windows in VectorRecurrentDQNPopulation, which takes no such argument.
+K must be a multiple of T. Overlapping windows (a stride other than T) are out of scope.
+VectorRecurrentDQNPopulation takes the same three arguments (T shared, K and the initial state per
+learner); its learner p is this trainer with (T, K_p, S_p), departures 7-9 included.
 """
 import ctypes as C
 
