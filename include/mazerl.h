@@ -611,7 +611,10 @@ int mz_adamw_groups(float* param_dev, float* exp_avg_dev, float* exp_avg_sq_dev,
  * CDF of a Philox uniform: P(a) = softmax(logits)[a], torch.multinomial's distribution), the
  * draw's log-prob log(p[a]); records obs6, the 22 window-bit words, action (int64), log-prob and
  * value at [i][t_dev[i]] (do_episode's appends, :150-156) and writes the action to act_out_dev
- * (int32, mz_step's input). */
+ * (int32, mz_step's input). The draw is a function of (seed, counter, i) alone. Where t_dev[i] is
+ * outside [0, L) the instance is skipped: nothing is recorded, no draw is made and act_out_dev[i]
+ * is left as it was (unlike mz_rf_act, which still draws and writes the action); mz_ppo_scan
+ * keeps t_dev inside, so the caller never steps with such an entry. */
 int mz_ppo_act(const float* logits_dev, int32_t ldl, const float* value_dev, int32_t ldv,
                const float* obs6_dev, const uint32_t* bits_dev, int32_t B, int32_t L, uint64_t seed,
                uint64_t counter, const int32_t* t_dev, float* rec_s6_dev, uint32_t* rec_w_dev,
