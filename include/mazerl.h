@@ -324,6 +324,12 @@ int mz_greedy_rows(const float* eps_dev, float eps_all, uint64_t seed, uint64_t 
  * order (c*49 + q) | obs6], ld >= 1574, i.e. the f32 input of fc.0. drop_p = 0 (DQN) or the
  * Dropout p (DDQN); the mask key is read from rng_dev (a device u64 the caller advances between
  * calls, so a captured HIP graph draws fresh masks on every replay) mixed with `salt`.
+ * Dropout rule, the same in mz_stem_forward and mz_stem_backward*: thresh = floor(p * 65536 + 0.5)
+ * in f32; a position is kept iff its 16-bit draw >= thresh, and kept values (forward) / gradients
+ * (backward) are multiplied by scale = (float)(1 / (1 - (double)p)) when thresh > 0 and by 1 when
+ * thresh == 0 — so 0 < p < 2^-17, which can drop nothing, is the stem without dropout in both
+ * directions (rng_dev is still required for p > 0, but not read), and p >= 1 - 2^-17 drops every
+ * position (features +-0, code bytes 0).
  * code_dev [n][1568] u8 (NULL when no backward follows): per feature the pooled argmax (bits
  * 0-1) and its gradient class (bits 2-3: 0 dropped, 1 kept with a > 0, 2 kept with a <= 0). */
 int mz_stem_forward(const uint32_t* bits_dev, const float* obs6_dev, int32_t n,

@@ -301,13 +301,23 @@ __global__ void k_stem_reduce(const float* __restrict__ partial, int chunks, flo
 
 int mz_stem_chunks(int n) { return (n + CHUNK - 1) / CHUNK; }
 
+// The dropout rule both launches share: keep iff a 16-bit uniform >= thresh, so P(drop) =
+// thresh / 65536 (0.2 -> 13107), survivors scaled by 1 / (1 - p). A p that rounds to thresh 0
+// (0 < p < 2^-17) can drop nothing: the stem then runs without dropout, scale 1, forward AND
+// backward (the backward once kept 1 / (1 - p) there and described another function).
+static inline uint32_t stem_thresh(float drop_p) {
+  return drop_p > 0.0f ? (uint32_t)(drop_p * 65536.0f + 0.5f) : 0u;
+}
+static inline float stem_scale(float drop_p) {
+  return stem_thresh(drop_p) ? (float)(1.0 / (1.0 - (double)drop_p)) : 1.0f;
+}
+
 hipError_t mz_launch_stem_fwd(const uint32_t* bits, const float* obs6, int n, const float* w,
                               const float* b, float drop_p, const uint64_t* rng, uint32_t salt,
                               float* feat, int ld, uint8_t* code, hipStream_t s) {
   if (n <= 0) return hipSuccess;
-  // keep iff a 16-bit uniform >= thresh: P(drop) = thresh / 65536 (0.2 -> 13107)
-  const uint32_t thresh = drop_p > 0.0f ? (uint32_t)(drop_p * 65536.0f + 0.5f) : 0u;
-  const float scale = drop_p > 0.0f ? (float)(1.0 / (1.0 - (double)drop_p)) : 1.0f;
+  const uint32_t thresh = stem_thresh(drop_p);
+  const float scale = stem_scale(drop_p);
   int blocks = (n + 3) / 4;  // one workgroup per 4 samples
   if (blocks > 4096) blocks = 4096;
 #define MZ_SF(D, C)                                                                              \
@@ -331,7 +341,7 @@ hipError_t mz_launch_stem_bwd(const uint32_t* bits, const uint8_t* code, const f
                        reinterpret_cast<unsigned long long*>(advance));
     return hipGetLastError();
   }
-  const float scale = drop_p > 0.0f ? (float)(1.0 / (1.0 - (double)drop_p)) : 1.0f;
+  const float scale = stem_scale(drop_p);
   hipLaunchKernelGGL(k_stem_bwd, dim3(chunks, 32), dim3(256), 0, s, bits, code, g, ld, n, scale,
                      partial);
   hipLaunchKernelGGL(k_stem_reduce, dim3((32 * NACC + 255) / 256), dim3(256), 0, s, partial,
