@@ -1517,32 +1517,98 @@ int mz_rf_head_loss(const float* logits_dev, int32_t ldl, const int64_t* action_
 }
 
 // ---- recurrent DQN (mz_drqn.hip) ---------------------------------------------------------------
-static bool drqn_net(const float* const* params_dev, MzDrqnNet* p) {
-  if (!params_dev) return false;
+// Every stage has one kernel, which serves P learners, and here one validator: it takes the
+// caller's name, P and b, the per-learner device arrays and the stage's single-learner struct
+// (the net in it) as the exported function filled it, validates and launches. A single-learner
+// entry point is P = 1 with those arrays null (the kernel then keeps the struct's by-value field);
+// a population one has checked that its own are there. A null net is all-null.
+template <class T> static MzDrqnSix<T> drqn_net(T* const* six_dev) {  // (a net or its gradients)
+  if (!six_dev) return MzDrqnSix<T>{};
   for (int k = 0; k < 6; ++k)
-    if (!params_dev[k]) return false;
-  *p = MzDrqnNet{params_dev[0], params_dev[1], params_dev[2], params_dev[3], params_dev[4],
-                 params_dev[5]};
-  return true;
+    if (!six_dev[k]) return MzDrqnSix<T>{};
+  return MzDrqnSix<T>{six_dev[0], six_dev[1], six_dev[2], six_dev[3], six_dev[4], six_dev[5]};
+}
+template <class T> static MzDrqnSix<T> drqn_flat_net(T* flat_dev) {
+  return flat_dev ? mz_drqn_flat_net(flat_dev) : MzDrqnSix<T>{};
+}
+
+static int drqn_pop_args(const char* who, int32_t hidden, int32_t P, int64_t per, const char* what) {
+  if (hidden != MZ_DRQN_HIDDEN) return fail(MZ_EINVAL, "%s: hidden %d != 32", who, hidden);
+  if (P < 1 || P > 65535 || per < 1 || (int64_t)P * per > 0x7fffffffll)
+    return fail(MZ_EINVAL, "%s: learners %d (1..65535), %s %lld", who, P, what, (long long)per);
+  return MZ_OK;
+}
+static int drqn_seq_args(const char* who, int32_t E, int32_t L, int64_t capacity) {
+  if (E < 1 || L < 1 || capacity < E)
+    return fail(MZ_EINVAL, "%s: E %d, L %d, capacity %lld", who, E, L, (long long)capacity);
+  return MZ_OK;
+}
+static int drqn_win_args(const char* who, int32_t hidden, int32_t T, int32_t K) {
+  if (hidden != MZ_DRQN_HIDDEN) return fail(MZ_EINVAL, "%s: hidden %d != 32", who, hidden);
+  if (T < 1 || K < 0 || K % T != 0)
+    return fail(MZ_EINVAL, "%s: window %d (>= 1), burn-in %d (>= 0, a multiple of the window)",
+                who, T, K);
+  return MZ_OK;
+}
+static int drqn_sample_args(const char* who, int32_t P, int32_t E, int32_t L, int64_t capacity,
+                            int64_t filled) {
+  if (int rc = drqn_pop_args(who, MZ_DRQN_HIDDEN, P, E, "E")) return rc;
+  if (E > 8192 || L < 1 || capacity < E || filled > capacity || filled < E)
+    return fail(MZ_EINVAL, "%s: E %d (1..8192), L %d, capacity %lld, (smallest) filled %lld", who,
+                E, L, (long long)capacity, (long long)filled);
+  return MZ_OK;
+}
+
+static int drqn_act(const char* who, int32_t hidden, int32_t P, int32_t b, const float* eps_dev,
+                    const uint64_t* seed_dev, MzDrqnAct a, void* stream) {
+  if (!a.p.w_ih || !a.obs6 || !a.t || !a.h || !a.c || !a.act_out ||
+      (a.L > 0 && (!a.rec_x || !a.rec_a)))
+    return fail(MZ_EINVAL, "%s: null pointer", who);
+  if (int rc = drqn_pop_args(who, hidden, P, b, "instances per learner")) return rc;
+  if (a.L < 0 || !(a.eps >= 0.0f && a.eps <= 1.0f) || a.explore < 1 || a.explore > 4)
+    return fail(MZ_EINVAL, "%s: L %d, epsilon %g, explore_actions %d", who, a.L, a.eps, a.explore);
+  a.B = P * b;
+  StreamGuard g(stream);
+  MZ_HIP(mz_launch_drqn_act(MzDrqnPopAct{a, P, b, eps_dev, seed_dev},
+                            static_cast<hipStream_t>(stream)));
+  return MZ_OK;
 }
 
 int mz_drqn_act(const float* const* params_dev, int32_t hidden, const float* obs6_dev, int32_t B,
                 int32_t L, float epsilon, int32_t explore_actions, uint64_t seed, uint64_t counter,
                 const int32_t* t_dev, float* h_dev, float* c_dev, float* rec_x_dev,
                 int32_t* rec_a_dev, int32_t* act_out_dev, float* q_out_dev, void* stream) {
-  MzDrqnNet p;
-  if (!drqn_net(params_dev, &p) || !obs6_dev || !t_dev || !h_dev || !c_dev || !act_out_dev ||
-      (L > 0 && (!rec_x_dev || !rec_a_dev)))
-    return fail(MZ_EINVAL, "mz_drqn_act: null pointer");
-  if (hidden != MZ_DRQN_HIDDEN) return fail(MZ_EINVAL, "mz_drqn_act: hidden %d != 32", hidden);
-  if (B < 1 || L < 0) return fail(MZ_EINVAL, "mz_drqn_act: B %d, L %d", B, L);
-  if (!(epsilon >= 0.0f && epsilon <= 1.0f) || explore_actions < 1 || explore_actions > 4)
-    return fail(MZ_EINVAL, "mz_drqn_act: epsilon %g, explore_actions %d", epsilon,
-                explore_actions);
+  return drqn_act("mz_drqn_act", hidden, 1, B, nullptr, nullptr,
+                  MzDrqnAct{drqn_net(params_dev), obs6_dev, 0, L, epsilon, explore_actions, seed,
+                            counter, t_dev, h_dev, c_dev, h_dev, c_dev, rec_x_dev, rec_a_dev,
+                            act_out_dev, q_out_dev}, stream);
+}
+
+int mz_drqn_pop_act(const float* params_dev, int32_t hidden, int32_t P, int32_t b,
+                    const float* obs6_dev, int32_t L, const float* eps_dev,
+                    int32_t explore_actions, const uint64_t* seed_dev, uint64_t counter,
+                    const int32_t* t_dev, float* h_dev, float* c_dev, float* rec_x_dev,
+                    int32_t* rec_a_dev, int32_t* act_out_dev, float* q_out_dev, void* stream) {
+  if (!eps_dev || !seed_dev) return fail(MZ_EINVAL, "mz_drqn_pop_act: null pointer");
+  return drqn_act("mz_drqn_pop_act", hidden, P, b, eps_dev, seed_dev,
+                  MzDrqnAct{drqn_flat_net(params_dev), obs6_dev, 0, L, 0.0f, explore_actions, 0,
+                            counter, t_dev, h_dev, c_dev, h_dev, c_dev, rec_x_dev, rec_a_dev,
+                            act_out_dev, q_out_dev}, stream);
+}
+
+// max_blocks: the workgroups per learner the entry point has always launched
+static int drqn_store(const char* who, int32_t P, int32_t b, int32_t max_blocks, MzDrqnStore s,
+                      void* stream) {
+  if (!s.obs6 || !s.term || !s.fin_id || !s.fin_len || !s.fin_count || !s.rec_x || !s.rec_a ||
+      !s.rec_r || !s.mem || !s.mem_len || !s.mem_term || !s.ring)
+    return fail(MZ_EINVAL, "%s: null pointer", who);
+  if (int rc = drqn_pop_args(who, MZ_DRQN_HIDDEN, P, b, "instances per learner")) return rc;
+  if (s.L < 1 || s.cap < 1)
+    return fail(MZ_EINVAL, "%s: L %d, capacity %lld", who, s.L, (long long)s.cap);
+  s.B = P * b;
   StreamGuard g(stream);
-  MzDrqnAct q{p, obs6_dev, B, L, epsilon, explore_actions, seed, counter, t_dev, h_dev, c_dev,
-              h_dev, c_dev, rec_x_dev, rec_a_dev, act_out_dev, q_out_dev};
-  MZ_HIP(mz_launch_drqn_act(q, static_cast<hipStream_t>(stream)));
+  MZ_HIP(mz_launch_drqn_store(MzDrqnPopStore{s, P, b}, b < max_blocks ? b : max_blocks,
+                              static_cast<hipStream_t>(stream)));
   return MZ_OK;
 }
 
@@ -1551,15 +1617,33 @@ int mz_drqn_store(const float* obs6_dev, const uint8_t* term_dev, int32_t B, int
                   const int32_t* fin_count_dev, float* rec_x_dev, const int32_t* rec_a_dev,
                   const double* rec_r_dev, int64_t capacity, uint32_t* mem_dev,
                   int32_t* mem_len_dev, int32_t* mem_term_dev, int64_t* ring_dev, void* stream) {
-  if (!obs6_dev || !term_dev || !fin_id_dev || !fin_len_dev || !fin_count_dev || !rec_x_dev ||
-      !rec_a_dev || !rec_r_dev || !mem_dev || !mem_len_dev || !mem_term_dev || !ring_dev)
-    return fail(MZ_EINVAL, "mz_drqn_store: null pointer");
-  if (B < 1 || L < 1 || capacity < 1)
-    return fail(MZ_EINVAL, "mz_drqn_store: B %d, L %d, capacity %lld", B, L, (long long)capacity);
+  return drqn_store("mz_drqn_store", 1, B, 2048,
+                    MzDrqnStore{obs6_dev, term_dev, 0, L, fin_id_dev, fin_len_dev, fin_count_dev,
+                                rec_x_dev, rec_a_dev, rec_r_dev, capacity, mem_dev, mem_len_dev,
+                                mem_term_dev, ring_dev}, stream);
+}
+
+int mz_drqn_pop_store(const float* obs6_dev, const uint8_t* term_dev, int32_t P, int32_t b,
+                      int32_t L, const int32_t* fin_id_dev, const int32_t* fin_len_dev,
+                      const int32_t* fin_count_dev, float* rec_x_dev, const int32_t* rec_a_dev,
+                      const double* rec_r_dev, int64_t capacity, uint32_t* mem_dev,
+                      int32_t* mem_len_dev, int32_t* mem_term_dev, int64_t* ring_dev,
+                      void* stream) {
+  return drqn_store("mz_drqn_pop_store", P, b, 256,
+                    MzDrqnStore{obs6_dev, term_dev, 0, L, fin_id_dev, fin_len_dev, fin_count_dev,
+                                rec_x_dev, rec_a_dev, rec_r_dev, capacity, mem_dev, mem_len_dev,
+                                mem_term_dev, ring_dev}, stream);
+}
+
+static int drqn_sample(const char* who, int32_t P, int64_t filled, const uint64_t* seed_dev,
+                       const uint64_t* counter_dev, const int32_t* due_dev, const MzDrqnSample& s,
+                       void* stream) {
+  if (!s.ring || !s.mem_len || !s.d_slot || !s.d_len || !s.d_off || !s.d_tot)
+    return fail(MZ_EINVAL, "%s: null pointer", who);
+  if (int rc = drqn_sample_args(who, P, s.E, s.L, s.cap, filled)) return rc;
   StreamGuard g(stream);
-  MzDrqnStore q{obs6_dev, term_dev, B, L, fin_id_dev, fin_len_dev, fin_count_dev, rec_x_dev,
-                rec_a_dev, rec_r_dev, capacity, mem_dev, mem_len_dev, mem_term_dev, ring_dev};
-  MZ_HIP(mz_launch_drqn_store(q, static_cast<hipStream_t>(stream)));
+  MZ_HIP(mz_launch_drqn_sample(MzDrqnPopSample{s, P, seed_dev, counter_dev, due_dev},
+                               static_cast<hipStream_t>(stream)));
   return MZ_OK;
 }
 
@@ -1567,22 +1651,64 @@ int mz_drqn_sample(uint64_t seed, uint64_t counter, int32_t E, int32_t L, int64_
                    int64_t filled, const int64_t* ring_dev, const int32_t* mem_len_dev,
                    int32_t* dir_slot_dev, int32_t* dir_len_dev, int64_t* dir_off_dev,
                    int64_t* dir_tot_dev, void* stream) {
-  if (!ring_dev || !mem_len_dev || !dir_slot_dev || !dir_len_dev || !dir_off_dev || !dir_tot_dev)
-    return fail(MZ_EINVAL, "mz_drqn_sample: null pointer");
-  if (E < 1 || E > 8192 || L < 1 || capacity < E || filled > capacity || filled < E)
-    return fail(MZ_EINVAL, "mz_drqn_sample: E %d (1..8192), L %d, capacity %lld, filled %lld", E,
-                L, (long long)capacity, (long long)filled);
-  StreamGuard g(stream);
-  MzDrqnSample q{seed, counter, E, L, capacity, ring_dev, mem_len_dev, dir_slot_dev, dir_len_dev,
-                 dir_off_dev, dir_tot_dev};
-  MZ_HIP(mz_launch_drqn_sample(q, static_cast<hipStream_t>(stream)));
-  return MZ_OK;
+  return drqn_sample("mz_drqn_sample", 1, filled, nullptr, nullptr, nullptr,
+                     MzDrqnSample{seed, counter, E, L, capacity, ring_dev, mem_len_dev,
+                                  dir_slot_dev, dir_len_dev, dir_off_dev, dir_tot_dev}, stream);
 }
 
-static int drqn_seq_args(const char* who, int32_t hidden, int32_t E, int32_t L, int64_t capacity) {
-  if (hidden != MZ_DRQN_HIDDEN) return fail(MZ_EINVAL, "%s: hidden %d != 32", who, hidden);
-  if (E < 1 || L < 1 || capacity < E)
-    return fail(MZ_EINVAL, "%s: E %d, L %d, capacity %lld", who, E, L, (long long)capacity);
+int mz_drqn_pop_sample(const uint64_t* seed_dev, const uint64_t* counter_dev,
+                       const int32_t* due_dev, int32_t P, int32_t E, int32_t L, int64_t capacity,
+                       int64_t min_filled, const int64_t* ring_dev, const int32_t* mem_len_dev,
+                       int32_t* dir_slot_dev, int32_t* dir_len_dev, int64_t* dir_off_dev,
+                       int64_t* dir_tot_dev, void* stream) {
+  if (!seed_dev || !counter_dev) return fail(MZ_EINVAL, "mz_drqn_pop_sample: null pointer");
+  return drqn_sample("mz_drqn_pop_sample", P, min_filled, seed_dev, counter_dev, due_dev,
+                     MzDrqnSample{0, 0, E, L, capacity, ring_dev, mem_len_dev, dir_slot_dev,
+                                  dir_len_dev, dir_off_dev, dir_tot_dev}, stream);
+}
+
+// what the forwards and the backwards of both update kinds check of the shared fields; the
+// backwards also take the reduce's arguments: ep_loss, learner 0's six gradient segments, the loss
+static int drqn_forward_args(const char* who, int32_t hidden, int32_t P, const MzDrqnUnroll& u) {
+  if (!u.p.w_ih || !u.mem || !u.mem_term || !u.qmax ||
+      (!u.target && (!u.stash || !u.qa || !u.y || !u.d || !u.ep_loss)))
+    return fail(MZ_EINVAL, "%s: null pointer", who);
+  if (int rc = drqn_pop_args(who, hidden, P, u.E, "E")) return rc;
+  return drqn_seq_args(who, u.E, u.L, u.cap);
+}
+static int drqn_backward_args(const char* who, int32_t hidden, int32_t P, const MzDrqnUnroll& u,
+                              const double* ep_loss_dev, const MzDrqnGrads& grads,
+                              const float* loss_dev) {
+  if (!u.p.w_ih || !u.mem || !u.stash || !u.d || !u.gpart || !ep_loss_dev || !grads.w_ih ||
+      !loss_dev)
+    return fail(MZ_EINVAL, "%s: null pointer", who);
+  if (int rc = drqn_pop_args(who, hidden, P, u.E, "E")) return rc;
+  return drqn_seq_args(who, u.E, u.L, u.cap);
+}
+static MzDrqnUnroll drqn_backward(const MzDrqnNet& p, int32_t E, int32_t L, int64_t capacity,
+                                  const uint32_t* mem_dev, const float* stash_dev,
+                                  const float* d_dev, float* gpart_dev) {
+  return MzDrqnUnroll{p, 0, E, L, capacity, 0.0f, mem_dev, nullptr, nullptr,
+                      const_cast<float*>(stash_dev), nullptr, nullptr, const_cast<float*>(d_dev),
+                      nullptr, gpart_dev};
+}
+// d_len: the lengths the loss counts, ld int32 words between two learners' rows
+static hipError_t drqn_reduce(int32_t P, int32_t ld, const MzDrqnUnroll& u,
+                              const double* ep_loss_dev, const int32_t* d_len_dev,
+                              const int64_t* d_tot_dev, const MzDrqnGrads& grads, float* loss_dev,
+                              const int32_t* due_dev, void* stream) {
+  MzDrqnReduce r{P, u.E, ld, u.gpart, ep_loss_dev, d_len_dev, d_tot_dev, grads, loss_dev, due_dev};
+  return mz_launch_drqn_reduce(r, static_cast<hipStream_t>(stream));
+}
+
+static int drqn_seq_forward(const char* who, int32_t hidden, int32_t P, const float* gamma_dev,
+                            const int32_t* due_dev, const MzDrqnSeq& q, void* stream) {
+  if (!q.d_slot || !q.d_len || !q.d_off || !q.d_tot)
+    return fail(MZ_EINVAL, "%s: null pointer", who);
+  if (int rc = drqn_forward_args(who, hidden, P, q.u)) return rc;
+  StreamGuard g(stream);
+  MZ_HIP(mz_launch_drqn_seq_forward(MzDrqnPopSeq{q, P, gamma_dev, due_dev},
+                                    static_cast<hipStream_t>(stream)));
   return MZ_OK;
 }
 
@@ -1593,17 +1719,40 @@ int mz_drqn_seq_forward(const float* const* params_dev, int32_t hidden, int32_t 
                         const int64_t* dir_tot_dev, float* qmax_dev, float* stash_dev,
                         float* qa_dev, float* y_dev, float* d_dev, double* ep_loss_dev,
                         void* stream) {
-  MzDrqnNet p;
-  if (!drqn_net(params_dev, &p) || !mem_dev || !mem_term_dev || !dir_slot_dev || !dir_len_dev ||
-      !dir_off_dev || !dir_tot_dev || !qmax_dev ||
-      (!target && (!stash_dev || !qa_dev || !y_dev || !d_dev || !ep_loss_dev)))
-    return fail(MZ_EINVAL, "mz_drqn_seq_forward: null pointer");
-  if (int rc = drqn_seq_args("mz_drqn_seq_forward", hidden, E, L, capacity)) return rc;
+  return drqn_seq_forward(
+      "mz_drqn_seq_forward", hidden, 1, nullptr, nullptr,
+      MzDrqnSeq{{drqn_net(params_dev), target ? 1 : 0, E, L, capacity, gamma, mem_dev, mem_term_dev,
+                 qmax_dev, stash_dev, qa_dev, y_dev, d_dev, ep_loss_dev, nullptr},
+                dir_slot_dev, dir_len_dev, dir_off_dev, dir_tot_dev}, stream);
+}
+
+int mz_drqn_pop_seq_forward(const float* params_dev, int32_t hidden, int32_t target, int32_t P,
+                            int32_t E, int32_t L, int64_t capacity, const float* gamma_dev,
+                            const int32_t* due_dev, const uint32_t* mem_dev,
+                            const int32_t* mem_term_dev, const int32_t* dir_slot_dev,
+                            const int32_t* dir_len_dev, const int64_t* dir_off_dev,
+                            const int64_t* dir_tot_dev, float* qmax_dev, float* stash_dev,
+                            float* qa_dev, float* y_dev, float* d_dev, double* ep_loss_dev,
+                            void* stream) {
+  if (!target && !gamma_dev) return fail(MZ_EINVAL, "mz_drqn_pop_seq_forward: null pointer");
+  return drqn_seq_forward(
+      "mz_drqn_pop_seq_forward", hidden, P, gamma_dev, due_dev,
+      MzDrqnSeq{{drqn_flat_net(params_dev), target ? 1 : 0, E, L, capacity, 0.0f, mem_dev,
+                 mem_term_dev, qmax_dev, stash_dev, qa_dev, y_dev, d_dev, ep_loss_dev, nullptr},
+                dir_slot_dev, dir_len_dev, dir_off_dev, dir_tot_dev}, stream);
+}
+
+static int drqn_seq_backward(const char* who, int32_t hidden, int32_t P, const int32_t* due_dev,
+                             const MzDrqnSeq& q, const double* ep_loss_dev,
+                             const MzDrqnGrads& grads, float* loss_dev, void* stream) {
+  if (!q.d_slot || !q.d_len || !q.d_off || !q.d_tot)
+    return fail(MZ_EINVAL, "%s: null pointer", who);
+  if (int rc = drqn_backward_args(who, hidden, P, q.u, ep_loss_dev, grads, loss_dev)) return rc;
   StreamGuard g(stream);
-  MzDrqnSeq q{p, target ? 1 : 0, E, L, capacity, gamma, mem_dev, mem_term_dev, dir_slot_dev,
-              dir_len_dev, dir_off_dev, dir_tot_dev, qmax_dev, stash_dev, qa_dev, y_dev, d_dev,
-              ep_loss_dev, nullptr};
-  MZ_HIP(mz_launch_drqn_seq_forward(q, static_cast<hipStream_t>(stream)));
+  MZ_HIP(mz_launch_drqn_seq_backward(MzDrqnPopSeq{q, P, nullptr, due_dev},
+                                     static_cast<hipStream_t>(stream)));
+  MZ_HIP(drqn_reduce(P, q.u.E, q.u, ep_loss_dev, q.d_len, q.d_tot, grads, loss_dev, due_dev,
+                     stream));
   return MZ_OK;
 }
 
@@ -1613,35 +1762,28 @@ int mz_drqn_seq_backward(const float* const* params_dev, int32_t hidden, int32_t
                          const int64_t* dir_tot_dev, const float* stash_dev, const float* d_dev,
                          const double* ep_loss_dev, float* gpart_dev, float* const* grads_dev,
                          float* loss_dev, void* stream) {
-  MzDrqnNet p;
-  if (!drqn_net(params_dev, &p) || !mem_dev || !dir_slot_dev || !dir_len_dev || !dir_off_dev ||
-      !dir_tot_dev || !stash_dev || !d_dev || !ep_loss_dev || !gpart_dev || !grads_dev ||
-      !loss_dev)
-    return fail(MZ_EINVAL, "mz_drqn_seq_backward: null pointer");
-  for (int k = 0; k < 6; ++k)
-    if (!grads_dev[k]) return fail(MZ_EINVAL, "mz_drqn_seq_backward: null gradient segment");
-  if (int rc = drqn_seq_args("mz_drqn_seq_backward", hidden, E, L, capacity)) return rc;
-  StreamGuard g(stream);
-  MzDrqnSeq q{p, 0, E, L, capacity, 0.0f, mem_dev, nullptr, dir_slot_dev, dir_len_dev,
-              dir_off_dev, dir_tot_dev, nullptr, const_cast<float*>(stash_dev), nullptr, nullptr,
-              const_cast<float*>(d_dev), nullptr, gpart_dev};
-  MZ_HIP(mz_launch_drqn_seq_backward(q, static_cast<hipStream_t>(stream)));
-  MzDrqnReduce r{E, gpart_dev, ep_loss_dev, dir_len_dev, dir_tot_dev,
-                 {grads_dev[0], grads_dev[1], grads_dev[2], grads_dev[3], grads_dev[4],
-                  grads_dev[5]}, loss_dev};
-  MZ_HIP(mz_launch_drqn_reduce(r, static_cast<hipStream_t>(stream)));
-  return MZ_OK;
+  return drqn_seq_backward(
+      "mz_drqn_seq_backward", hidden, 1, nullptr,
+      MzDrqnSeq{drqn_backward(drqn_net(params_dev), E, L, capacity, mem_dev, stash_dev, d_dev,
+                              gpart_dev), dir_slot_dev, dir_len_dev, dir_off_dev, dir_tot_dev},
+      ep_loss_dev, drqn_net(grads_dev), loss_dev, stream);
+}
+
+int mz_drqn_pop_seq_backward(const float* params_dev, int32_t hidden, int32_t P, int32_t E,
+                             int32_t L, int64_t capacity, const int32_t* due_dev,
+                             const uint32_t* mem_dev, const int32_t* dir_slot_dev,
+                             const int32_t* dir_len_dev, const int64_t* dir_off_dev,
+                             const int64_t* dir_tot_dev, const float* stash_dev,
+                             const float* d_dev, const double* ep_loss_dev, float* gpart_dev,
+                             float* grads_dev, float* loss_dev, void* stream) {
+  return drqn_seq_backward(
+      "mz_drqn_pop_seq_backward", hidden, P, due_dev,
+      MzDrqnSeq{drqn_backward(drqn_flat_net(params_dev), E, L, capacity, mem_dev, stash_dev, d_dev,
+                              gpart_dev), dir_slot_dev, dir_len_dev, dir_off_dev, dir_tot_dev},
+      ep_loss_dev, drqn_flat_net(grads_dev), loss_dev, stream);
 }
 
 // ---- recurrent DQN replay windows (mz_drqn.hip k_drqn_snapshot .. k_drqn_win_bwd) ----------------
-static int drqn_win_args(const char* who, int32_t hidden, int32_t T, int32_t K) {
-  if (hidden != MZ_DRQN_HIDDEN) return fail(MZ_EINVAL, "%s: hidden %d != 32", who, hidden);
-  if (T < 1 || K < 0 || K % T != 0)
-    return fail(MZ_EINVAL, "%s: window %d (>= 1), burn-in %d (>= 0, a multiple of the window)",
-                who, T, K);
-  return MZ_OK;
-}
-
 int mz_drqn_snapshot(int32_t hidden, int32_t B, int32_t L, int32_t T, const int32_t* t_dev,
                      const float* h_dev, const float* c_dev, float* snap_rec_dev, void* stream) {
   if (!t_dev || !h_dev || !c_dev || !snap_rec_dev)
@@ -1654,20 +1796,55 @@ int mz_drqn_snapshot(int32_t hidden, int32_t B, int32_t L, int32_t T, const int3
   return MZ_OK;
 }
 
+static int drqn_snap_store(const char* who, int32_t hidden, int32_t P, int32_t b,
+                           int32_t max_blocks, MzDrqnSnapStore s, void* stream) {
+  if (!s.fin_id || !s.fin_len || !s.fin_count || !s.snap_rec || !s.mem_state || !s.ring)
+    return fail(MZ_EINVAL, "%s: null pointer", who);
+  if (int rc = drqn_pop_args(who, hidden, P, b, "instances per learner")) return rc;
+  if (int rc = drqn_win_args(who, hidden, s.T, 0)) return rc;
+  if (s.L < 1 || s.cap < 1)
+    return fail(MZ_EINVAL, "%s: L %d, capacity %lld", who, s.L, (long long)s.cap);
+  s.B = P * b;
+  StreamGuard g(stream);
+  MZ_HIP(mz_launch_drqn_snap_store(MzDrqnPopSnapStore{s, P, b}, b < max_blocks ? b : max_blocks,
+                                   static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
 int mz_drqn_snap_store(int32_t hidden, int32_t B, int32_t L, int32_t T, const int32_t* fin_id_dev,
                        const int32_t* fin_len_dev, const int32_t* fin_count_dev,
                        const float* snap_rec_dev, int64_t capacity, float* mem_state_dev,
                        const int64_t* ring_dev, void* stream) {
-  if (!fin_id_dev || !fin_len_dev || !fin_count_dev || !snap_rec_dev || !mem_state_dev || !ring_dev)
-    return fail(MZ_EINVAL, "mz_drqn_snap_store: null pointer");
-  if (int rc = drqn_win_args("mz_drqn_snap_store", hidden, T, 0)) return rc;
-  if (B < 1 || L < 1 || capacity < 1)
-    return fail(MZ_EINVAL, "mz_drqn_snap_store: B %d, L %d, capacity %lld", B, L,
-                (long long)capacity);
+  return drqn_snap_store("mz_drqn_snap_store", hidden, 1, B, 2048,
+                         MzDrqnSnapStore{0, L, T, fin_id_dev, fin_len_dev, fin_count_dev,
+                                         snap_rec_dev, capacity, mem_state_dev, ring_dev}, stream);
+}
+
+int mz_drqn_pop_snap_store(int32_t hidden, int32_t P, int32_t b, int32_t L, int32_t T,
+                           const int32_t* fin_id_dev, const int32_t* fin_len_dev,
+                           const int32_t* fin_count_dev, const float* snap_rec_dev,
+                           int64_t capacity, float* mem_state_dev, const int64_t* ring_dev,
+                           void* stream) {
+  return drqn_snap_store("mz_drqn_pop_snap_store", hidden, P, b, 256,
+                         MzDrqnSnapStore{0, L, T, fin_id_dev, fin_len_dev, fin_count_dev,
+                                         snap_rec_dev, capacity, mem_state_dev, ring_dev}, stream);
+}
+
+// w.s.d_slot / d_len are left null: they are the first two rows of wdir
+static int drqn_window_sample(const char* who, int32_t hidden, int32_t P, int64_t filled,
+                              const uint64_t* seed_dev, const uint64_t* counter_dev,
+                              const int32_t* burn_in_dev, const int32_t* due_dev,
+                              MzDrqnWinSample w, void* stream) {
+  if (!w.s.ring || !w.s.mem_len || !w.wdir || !w.s.d_off || !w.s.d_tot)
+    return fail(MZ_EINVAL, "%s: null pointer", who);
+  if (int rc = drqn_win_args(who, hidden, w.T, w.K)) return rc;
+  if (int rc = drqn_sample_args(who, P, w.s.E, w.s.L, w.s.cap, filled)) return rc;
+  w.s.d_slot = w.wdir + (size_t)MZ_DRQN_WDIR_SLOT * w.s.E;
+  w.s.d_len = w.wdir + (size_t)MZ_DRQN_WDIR_LEN * w.s.E;
   StreamGuard g(stream);
-  MzDrqnSnapStore q{B, L, T, fin_id_dev, fin_len_dev, fin_count_dev, snap_rec_dev, capacity,
-                    mem_state_dev, ring_dev};
-  MZ_HIP(mz_launch_drqn_snap_store(q, static_cast<hipStream_t>(stream)));
+  MZ_HIP(mz_launch_drqn_window_sample(
+      MzDrqnPopWinSample{w, P, seed_dev, counter_dev, burn_in_dev, due_dev},
+      static_cast<hipStream_t>(stream)));
   return MZ_OK;
 }
 
@@ -1675,17 +1852,36 @@ int mz_drqn_window_sample(uint64_t seed, uint64_t counter, int32_t hidden, int32
                           int32_t T, int32_t K, int64_t capacity, int64_t filled,
                           const int64_t* ring_dev, const int32_t* mem_len_dev, int32_t* wdir_dev,
                           int64_t* win_off_dev, int64_t* win_tot_dev, void* stream) {
-  if (!ring_dev || !mem_len_dev || !wdir_dev || !win_off_dev || !win_tot_dev)
-    return fail(MZ_EINVAL, "mz_drqn_window_sample: null pointer");
-  if (int rc = drqn_win_args("mz_drqn_window_sample", hidden, T, K)) return rc;
-  if (E < 1 || E > 8192 || L < 1 || capacity < E || filled > capacity || filled < E)
-    return fail(MZ_EINVAL, "mz_drqn_window_sample: E %d (1..8192), L %d, capacity %lld, filled "
-                "%lld", E, L, (long long)capacity, (long long)filled);
+  return drqn_window_sample(
+      "mz_drqn_window_sample", hidden, 1, filled, nullptr, nullptr, nullptr, nullptr,
+      MzDrqnWinSample{{seed, counter, E, L, capacity, ring_dev, mem_len_dev, nullptr, nullptr,
+                       win_off_dev, win_tot_dev}, T, K, wdir_dev}, stream);
+}
+
+int mz_drqn_pop_window_sample(const uint64_t* seed_dev, const uint64_t* counter_dev,
+                              const int32_t* burn_in_dev, const int32_t* due_dev, int32_t hidden,
+                              int32_t P, int32_t E, int32_t L, int32_t T, int32_t K_max,
+                              int64_t capacity, int64_t min_filled, const int64_t* ring_dev,
+                              const int32_t* mem_len_dev, int32_t* wdir_dev, int64_t* win_off_dev,
+                              int64_t* win_tot_dev, void* stream) {
+  if (!seed_dev || !counter_dev || !burn_in_dev)
+    return fail(MZ_EINVAL, "mz_drqn_pop_window_sample: null pointer");
+  return drqn_window_sample(
+      "mz_drqn_pop_window_sample", hidden, P, min_filled, seed_dev, counter_dev, burn_in_dev,
+      due_dev, MzDrqnWinSample{{0, 0, E, L, capacity, ring_dev, mem_len_dev, nullptr, nullptr,
+                                win_off_dev, win_tot_dev}, T, K_max, wdir_dev}, stream);
+}
+
+static int drqn_window_forward(const char* who, int32_t hidden, int32_t P, const float* gamma_dev,
+                               const int32_t* burn_in_dev, const int32_t* stored_dev,
+                               const int32_t* due_dev, const MzDrqnWin& q, void* stream) {
+  if (!q.wdir || !q.w_off || !q.w_tot) return fail(MZ_EINVAL, "%s: null pointer", who);
+  if (int rc = drqn_win_args(who, hidden, q.T, q.K)) return rc;
+  if (int rc = drqn_forward_args(who, hidden, P, q.u)) return rc;
   StreamGuard g(stream);
-  MzDrqnWinSample q{{seed, counter, E, L, capacity, ring_dev, mem_len_dev,
-                     wdir_dev + (size_t)MZ_DRQN_WDIR_SLOT * E, wdir_dev + (size_t)MZ_DRQN_WDIR_LEN * E,
-                     win_off_dev, win_tot_dev}, T, K, wdir_dev};
-  MZ_HIP(mz_launch_drqn_window_sample(q, static_cast<hipStream_t>(stream)));
+  MZ_HIP(mz_launch_drqn_window_forward(
+      MzDrqnPopWin{q, P, gamma_dev, burn_in_dev, stored_dev, due_dev},
+      static_cast<hipStream_t>(stream)));
   return MZ_OK;
 }
 
@@ -1696,206 +1892,11 @@ int mz_drqn_window_forward(const float* const* params_dev, int32_t hidden, int32
                            const int64_t* win_off_dev, const int64_t* win_tot_dev, float* qmax_dev,
                            float* stash_dev, float* qa_dev, float* y_dev, float* d_dev,
                            double* ep_loss_dev, void* stream) {
-  MzDrqnNet p;
-  if (!drqn_net(params_dev, &p) || !mem_dev || !mem_term_dev || !wdir_dev || !win_off_dev ||
-      !win_tot_dev || !qmax_dev ||
-      (!target && (!stash_dev || !qa_dev || !y_dev || !d_dev || !ep_loss_dev)))
-    return fail(MZ_EINVAL, "mz_drqn_window_forward: null pointer");
-  if (int rc = drqn_win_args("mz_drqn_window_forward", hidden, T, K)) return rc;
-  if (int rc = drqn_seq_args("mz_drqn_window_forward", hidden, E, L, capacity)) return rc;
-  StreamGuard g(stream);
-  MzDrqnWin q{p, target ? 1 : 0, E, L, T, K, capacity, gamma, mem_dev, mem_term_dev,
-              mem_state_dev, wdir_dev, win_off_dev, win_tot_dev, qmax_dev, stash_dev, qa_dev,
-              y_dev, d_dev, ep_loss_dev, nullptr};
-  MZ_HIP(mz_launch_drqn_window_forward(q, static_cast<hipStream_t>(stream)));
-  return MZ_OK;
-}
-
-int mz_drqn_window_backward(const float* const* params_dev, int32_t hidden, int32_t E, int32_t L,
-                            int32_t T, int32_t K, int64_t capacity, const uint32_t* mem_dev,
-                            const int32_t* wdir_dev, const int64_t* win_off_dev,
-                            const int64_t* win_tot_dev, const float* stash_dev,
-                            const float* d_dev, const double* ep_loss_dev, float* gpart_dev,
-                            float* const* grads_dev, float* loss_dev, void* stream) {
-  MzDrqnNet p;
-  if (!drqn_net(params_dev, &p) || !mem_dev || !wdir_dev || !win_off_dev || !win_tot_dev ||
-      !stash_dev || !d_dev || !ep_loss_dev || !gpart_dev || !grads_dev || !loss_dev)
-    return fail(MZ_EINVAL, "mz_drqn_window_backward: null pointer");
-  for (int k = 0; k < 6; ++k)
-    if (!grads_dev[k]) return fail(MZ_EINVAL, "mz_drqn_window_backward: null gradient segment");
-  if (int rc = drqn_win_args("mz_drqn_window_backward", hidden, T, K)) return rc;
-  if (int rc = drqn_seq_args("mz_drqn_window_backward", hidden, E, L, capacity)) return rc;
-  StreamGuard g(stream);
-  MzDrqnWin q{p, 0, E, L, T, K, capacity, 0.0f, mem_dev, nullptr, nullptr, wdir_dev, win_off_dev,
-              win_tot_dev, nullptr, const_cast<float*>(stash_dev), nullptr, nullptr,
-              const_cast<float*>(d_dev), nullptr, gpart_dev};
-  MZ_HIP(mz_launch_drqn_window_backward(q, static_cast<hipStream_t>(stream)));
-  MzDrqnReduce r{E, gpart_dev, ep_loss_dev, wdir_dev + (size_t)MZ_DRQN_WDIR_M * E, win_tot_dev,
-                 {grads_dev[0], grads_dev[1], grads_dev[2], grads_dev[3], grads_dev[4],
-                  grads_dev[5]}, loss_dev};
-  MZ_HIP(mz_launch_drqn_reduce(r, static_cast<hipStream_t>(stream)));
-  return MZ_OK;
-}
-
-// ---- populations of recurrent DQN learners (mz_drqn.hip k_drqn_pop_*) ----------------------------
-static int drqn_pop_args(const char* who, int32_t hidden, int32_t P, int64_t per, const char* what) {
-  if (hidden != MZ_DRQN_HIDDEN) return fail(MZ_EINVAL, "%s: hidden %d != 32", who, hidden);
-  if (P < 1 || P > 65535 || per < 1 || (int64_t)P * per > 0x7fffffffll)
-    return fail(MZ_EINVAL, "%s: learners %d (1..65535), %s %lld", who, P, what, (long long)per);
-  return MZ_OK;
-}
-
-int mz_drqn_pop_act(const float* params_dev, int32_t hidden, int32_t P, int32_t b,
-                    const float* obs6_dev, int32_t L, const float* eps_dev,
-                    int32_t explore_actions, const uint64_t* seed_dev, uint64_t counter,
-                    const int32_t* t_dev, float* h_dev, float* c_dev, float* rec_x_dev,
-                    int32_t* rec_a_dev, int32_t* act_out_dev, float* q_out_dev, void* stream) {
-  if (!params_dev || !obs6_dev || !eps_dev || !seed_dev || !t_dev || !h_dev || !c_dev ||
-      !act_out_dev || (L > 0 && (!rec_x_dev || !rec_a_dev)))
-    return fail(MZ_EINVAL, "mz_drqn_pop_act: null pointer");
-  if (int rc = drqn_pop_args("mz_drqn_pop_act", hidden, P, b, "instances per learner")) return rc;
-  if (L < 0 || explore_actions < 1 || explore_actions > 4)
-    return fail(MZ_EINVAL, "mz_drqn_pop_act: L %d, explore_actions %d", L, explore_actions);
-  StreamGuard g(stream);
-  MzDrqnPopAct q{{mz_drqn_flat_net(params_dev), obs6_dev, P * b, L, 0.0f, explore_actions, 0,
-                  counter, t_dev, h_dev, c_dev, h_dev, c_dev, rec_x_dev, rec_a_dev, act_out_dev,
-                  q_out_dev},
-                 P, b, eps_dev, seed_dev};
-  MZ_HIP(mz_launch_drqn_pop_act(q, static_cast<hipStream_t>(stream)));
-  return MZ_OK;
-}
-
-int mz_drqn_pop_store(const float* obs6_dev, const uint8_t* term_dev, int32_t P, int32_t b,
-                      int32_t L, const int32_t* fin_id_dev, const int32_t* fin_len_dev,
-                      const int32_t* fin_count_dev, float* rec_x_dev, const int32_t* rec_a_dev,
-                      const double* rec_r_dev, int64_t capacity, uint32_t* mem_dev,
-                      int32_t* mem_len_dev, int32_t* mem_term_dev, int64_t* ring_dev,
-                      void* stream) {
-  if (!obs6_dev || !term_dev || !fin_id_dev || !fin_len_dev || !fin_count_dev || !rec_x_dev ||
-      !rec_a_dev || !rec_r_dev || !mem_dev || !mem_len_dev || !mem_term_dev || !ring_dev)
-    return fail(MZ_EINVAL, "mz_drqn_pop_store: null pointer");
-  if (int rc = drqn_pop_args("mz_drqn_pop_store", MZ_DRQN_HIDDEN, P, b, "instances per learner"))
-    return rc;
-  if (L < 1 || capacity < 1)
-    return fail(MZ_EINVAL, "mz_drqn_pop_store: L %d, capacity %lld", L, (long long)capacity);
-  StreamGuard g(stream);
-  MzDrqnPopStore q{{obs6_dev, term_dev, P * b, L, fin_id_dev, fin_len_dev, fin_count_dev,
-                    rec_x_dev, rec_a_dev, rec_r_dev, capacity, mem_dev, mem_len_dev, mem_term_dev,
-                    ring_dev},
-                   P, b};
-  MZ_HIP(mz_launch_drqn_pop_store(q, static_cast<hipStream_t>(stream)));
-  return MZ_OK;
-}
-
-int mz_drqn_pop_sample(const uint64_t* seed_dev, const uint64_t* counter_dev,
-                       const int32_t* due_dev, int32_t P, int32_t E, int32_t L, int64_t capacity,
-                       int64_t min_filled, const int64_t* ring_dev, const int32_t* mem_len_dev,
-                       int32_t* dir_slot_dev, int32_t* dir_len_dev, int64_t* dir_off_dev,
-                       int64_t* dir_tot_dev, void* stream) {
-  if (!seed_dev || !counter_dev || !ring_dev || !mem_len_dev || !dir_slot_dev || !dir_len_dev ||
-      !dir_off_dev || !dir_tot_dev)
-    return fail(MZ_EINVAL, "mz_drqn_pop_sample: null pointer");
-  if (int rc = drqn_pop_args("mz_drqn_pop_sample", MZ_DRQN_HIDDEN, P, E, "E")) return rc;
-  if (E > 8192 || L < 1 || capacity < E || min_filled > capacity || min_filled < E)
-    return fail(MZ_EINVAL, "mz_drqn_pop_sample: E %d (1..8192), L %d, capacity %lld, smallest "
-                "filled %lld", E, L, (long long)capacity, (long long)min_filled);
-  StreamGuard g(stream);
-  MzDrqnPopSample q{{0, 0, E, L, capacity, ring_dev, mem_len_dev, dir_slot_dev, dir_len_dev,
-                     dir_off_dev, dir_tot_dev},
-                    P, seed_dev, counter_dev, due_dev};
-  MZ_HIP(mz_launch_drqn_pop_sample(q, static_cast<hipStream_t>(stream)));
-  return MZ_OK;
-}
-
-int mz_drqn_pop_seq_forward(const float* params_dev, int32_t hidden, int32_t target, int32_t P,
-                            int32_t E, int32_t L, int64_t capacity, const float* gamma_dev,
-                            const int32_t* due_dev, const uint32_t* mem_dev,
-                            const int32_t* mem_term_dev, const int32_t* dir_slot_dev,
-                            const int32_t* dir_len_dev, const int64_t* dir_off_dev,
-                            const int64_t* dir_tot_dev, float* qmax_dev, float* stash_dev,
-                            float* qa_dev, float* y_dev, float* d_dev, double* ep_loss_dev,
-                            void* stream) {
-  if (!params_dev || !mem_dev || !mem_term_dev || !dir_slot_dev || !dir_len_dev || !dir_off_dev ||
-      !dir_tot_dev || !qmax_dev ||
-      (!target && (!gamma_dev || !stash_dev || !qa_dev || !y_dev || !d_dev || !ep_loss_dev)))
-    return fail(MZ_EINVAL, "mz_drqn_pop_seq_forward: null pointer");
-  if (int rc = drqn_pop_args("mz_drqn_pop_seq_forward", hidden, P, E, "E")) return rc;
-  if (int rc = drqn_seq_args("mz_drqn_pop_seq_forward", hidden, E, L, capacity)) return rc;
-  StreamGuard g(stream);
-  MzDrqnPopSeq q{{mz_drqn_flat_net(params_dev), target ? 1 : 0, E, L, capacity, 0.0f, mem_dev,
-                  mem_term_dev, dir_slot_dev, dir_len_dev, dir_off_dev, dir_tot_dev, qmax_dev,
-                  stash_dev, qa_dev, y_dev, d_dev, ep_loss_dev, nullptr},
-                 P, gamma_dev, due_dev};
-  MZ_HIP(mz_launch_drqn_pop_seq_forward(q, static_cast<hipStream_t>(stream)));
-  return MZ_OK;
-}
-
-int mz_drqn_pop_seq_backward(const float* params_dev, int32_t hidden, int32_t P, int32_t E,
-                             int32_t L, int64_t capacity, const int32_t* due_dev,
-                             const uint32_t* mem_dev, const int32_t* dir_slot_dev,
-                             const int32_t* dir_len_dev, const int64_t* dir_off_dev,
-                             const int64_t* dir_tot_dev, const float* stash_dev,
-                             const float* d_dev, const double* ep_loss_dev, float* gpart_dev,
-                             float* grads_dev, float* loss_dev, void* stream) {
-  if (!params_dev || !mem_dev || !dir_slot_dev || !dir_len_dev || !dir_off_dev || !dir_tot_dev ||
-      !stash_dev || !d_dev || !ep_loss_dev || !gpart_dev || !grads_dev || !loss_dev)
-    return fail(MZ_EINVAL, "mz_drqn_pop_seq_backward: null pointer");
-  if (int rc = drqn_pop_args("mz_drqn_pop_seq_backward", hidden, P, E, "E")) return rc;
-  if (int rc = drqn_seq_args("mz_drqn_pop_seq_backward", hidden, E, L, capacity)) return rc;
-  StreamGuard g(stream);
-  MzDrqnPopSeq q{{mz_drqn_flat_net(params_dev), 0, E, L, capacity, 0.0f, mem_dev, nullptr,
-                  dir_slot_dev, dir_len_dev, dir_off_dev, dir_tot_dev, nullptr,
-                  const_cast<float*>(stash_dev), nullptr, nullptr, const_cast<float*>(d_dev),
-                  nullptr, gpart_dev},
-                 P, nullptr, due_dev};
-  MZ_HIP(mz_launch_drqn_pop_seq_backward(q, static_cast<hipStream_t>(stream)));
-  MzDrqnPopReduce r{P, E, E, gpart_dev, ep_loss_dev, dir_len_dev, dir_tot_dev, grads_dev, loss_dev,
-                    due_dev};
-  MZ_HIP(mz_launch_drqn_pop_reduce(r, static_cast<hipStream_t>(stream)));
-  return MZ_OK;
-}
-
-// ---- replay windows in populations (mz_drqn.hip k_drqn_pop_snap_store .. k_drqn_pop_win_bwd) ------
-int mz_drqn_pop_snap_store(int32_t hidden, int32_t P, int32_t b, int32_t L, int32_t T,
-                           const int32_t* fin_id_dev, const int32_t* fin_len_dev,
-                           const int32_t* fin_count_dev, const float* snap_rec_dev,
-                           int64_t capacity, float* mem_state_dev, const int64_t* ring_dev,
-                           void* stream) {
-  if (!fin_id_dev || !fin_len_dev || !fin_count_dev || !snap_rec_dev || !mem_state_dev || !ring_dev)
-    return fail(MZ_EINVAL, "mz_drqn_pop_snap_store: null pointer");
-  if (int rc = drqn_pop_args("mz_drqn_pop_snap_store", hidden, P, b, "instances per learner"))
-    return rc;
-  if (int rc = drqn_win_args("mz_drqn_pop_snap_store", hidden, T, 0)) return rc;
-  if (L < 1 || capacity < 1)
-    return fail(MZ_EINVAL, "mz_drqn_pop_snap_store: L %d, capacity %lld", L, (long long)capacity);
-  StreamGuard g(stream);
-  MzDrqnPopSnapStore q{{P * b, L, T, fin_id_dev, fin_len_dev, fin_count_dev, snap_rec_dev,
-                        capacity, mem_state_dev, ring_dev},
-                       P, b};
-  MZ_HIP(mz_launch_drqn_pop_snap_store(q, static_cast<hipStream_t>(stream)));
-  return MZ_OK;
-}
-
-int mz_drqn_pop_window_sample(const uint64_t* seed_dev, const uint64_t* counter_dev,
-                              const int32_t* burn_in_dev, const int32_t* due_dev, int32_t hidden,
-                              int32_t P, int32_t E, int32_t L, int32_t T, int32_t K_max,
-                              int64_t capacity, int64_t min_filled, const int64_t* ring_dev,
-                              const int32_t* mem_len_dev, int32_t* wdir_dev, int64_t* win_off_dev,
-                              int64_t* win_tot_dev, void* stream) {
-  if (!seed_dev || !counter_dev || !burn_in_dev || !ring_dev || !mem_len_dev || !wdir_dev ||
-      !win_off_dev || !win_tot_dev)
-    return fail(MZ_EINVAL, "mz_drqn_pop_window_sample: null pointer");
-  if (int rc = drqn_pop_args("mz_drqn_pop_window_sample", hidden, P, E, "E")) return rc;
-  if (int rc = drqn_win_args("mz_drqn_pop_window_sample", hidden, T, K_max)) return rc;
-  if (E > 8192 || L < 1 || capacity < E || min_filled > capacity || min_filled < E)
-    return fail(MZ_EINVAL, "mz_drqn_pop_window_sample: E %d (1..8192), L %d, capacity %lld, "
-                "smallest filled %lld", E, L, (long long)capacity, (long long)min_filled);
-  StreamGuard g(stream);
-  MzDrqnPopWinSample q{{{0, 0, E, L, capacity, ring_dev, mem_len_dev, wdir_dev, wdir_dev,
-                         win_off_dev, win_tot_dev}, T, K_max, wdir_dev},
-                       P, seed_dev, counter_dev, burn_in_dev, due_dev};
-  MZ_HIP(mz_launch_drqn_pop_window_sample(q, static_cast<hipStream_t>(stream)));
-  return MZ_OK;
+  return drqn_window_forward(
+      "mz_drqn_window_forward", hidden, 1, nullptr, nullptr, nullptr, nullptr,
+      MzDrqnWin{{drqn_net(params_dev), target ? 1 : 0, E, L, capacity, gamma, mem_dev, mem_term_dev,
+                 qmax_dev, stash_dev, qa_dev, y_dev, d_dev, ep_loss_dev, nullptr},
+                T, K, mem_state_dev, wdir_dev, win_off_dev, win_tot_dev}, stream);
 }
 
 int mz_drqn_pop_window_forward(const float* params_dev, int32_t hidden, int32_t target, int32_t P,
@@ -1907,20 +1908,42 @@ int mz_drqn_pop_window_forward(const float* params_dev, int32_t hidden, int32_t 
                                const int64_t* win_off_dev, const int64_t* win_tot_dev,
                                float* qmax_dev, float* stash_dev, float* qa_dev, float* y_dev,
                                float* d_dev, double* ep_loss_dev, void* stream) {
-  if (!params_dev || !burn_in_dev || !mem_dev || !mem_term_dev || !wdir_dev || !win_off_dev ||
-      !win_tot_dev || !qmax_dev || (mem_state_dev && !stored_dev) ||
-      (!target && (!gamma_dev || !stash_dev || !qa_dev || !y_dev || !d_dev || !ep_loss_dev)))
+  if (!burn_in_dev || (mem_state_dev && !stored_dev) || (!target && !gamma_dev))
     return fail(MZ_EINVAL, "mz_drqn_pop_window_forward: null pointer");
-  if (int rc = drqn_pop_args("mz_drqn_pop_window_forward", hidden, P, E, "E")) return rc;
-  if (int rc = drqn_win_args("mz_drqn_pop_window_forward", hidden, T, K_max)) return rc;
-  if (int rc = drqn_seq_args("mz_drqn_pop_window_forward", hidden, E, L, capacity)) return rc;
+  return drqn_window_forward(
+      "mz_drqn_pop_window_forward", hidden, P, gamma_dev, burn_in_dev, stored_dev, due_dev,
+      MzDrqnWin{{drqn_flat_net(params_dev), target ? 1 : 0, E, L, capacity, 0.0f, mem_dev,
+                 mem_term_dev, qmax_dev, stash_dev, qa_dev, y_dev, d_dev, ep_loss_dev, nullptr},
+                T, K_max, mem_state_dev, wdir_dev, win_off_dev, win_tot_dev}, stream);
+}
+
+static int drqn_window_backward(const char* who, int32_t hidden, int32_t P,
+                                const int32_t* burn_in_dev, const int32_t* due_dev,
+                                const MzDrqnWin& q, const double* ep_loss_dev,
+                                const MzDrqnGrads& grads, float* loss_dev, void* stream) {
+  if (!q.wdir || !q.w_off || !q.w_tot) return fail(MZ_EINVAL, "%s: null pointer", who);
+  if (int rc = drqn_win_args(who, hidden, q.T, q.K)) return rc;
+  if (int rc = drqn_backward_args(who, hidden, P, q.u, ep_loss_dev, grads, loss_dev)) return rc;
   StreamGuard g(stream);
-  MzDrqnPopWin q{{mz_drqn_flat_net(params_dev), target ? 1 : 0, E, L, T, K_max, capacity, 0.0f,
-                  mem_dev, mem_term_dev, mem_state_dev, wdir_dev, win_off_dev, win_tot_dev,
-                  qmax_dev, stash_dev, qa_dev, y_dev, d_dev, ep_loss_dev, nullptr},
-                 P, gamma_dev, burn_in_dev, stored_dev, due_dev};
-  MZ_HIP(mz_launch_drqn_pop_window_forward(q, static_cast<hipStream_t>(stream)));
+  MZ_HIP(mz_launch_drqn_window_backward(MzDrqnPopWin{q, P, nullptr, burn_in_dev, nullptr, due_dev},
+                                        static_cast<hipStream_t>(stream)));
+  // the lengths the loss counts: the m row of each learner's [5][E] directory block
+  MZ_HIP(drqn_reduce(P, 5 * q.u.E, q.u, ep_loss_dev, q.wdir + (size_t)MZ_DRQN_WDIR_M * q.u.E,
+                     q.w_tot, grads, loss_dev, due_dev, stream));
   return MZ_OK;
+}
+
+int mz_drqn_window_backward(const float* const* params_dev, int32_t hidden, int32_t E, int32_t L,
+                            int32_t T, int32_t K, int64_t capacity, const uint32_t* mem_dev,
+                            const int32_t* wdir_dev, const int64_t* win_off_dev,
+                            const int64_t* win_tot_dev, const float* stash_dev,
+                            const float* d_dev, const double* ep_loss_dev, float* gpart_dev,
+                            float* const* grads_dev, float* loss_dev, void* stream) {
+  return drqn_window_backward(
+      "mz_drqn_window_backward", hidden, 1, nullptr, nullptr,
+      MzDrqnWin{drqn_backward(drqn_net(params_dev), E, L, capacity, mem_dev, stash_dev, d_dev,
+                              gpart_dev), T, K, nullptr, wdir_dev, win_off_dev, win_tot_dev},
+      ep_loss_dev, drqn_net(grads_dev), loss_dev, stream);
 }
 
 int mz_drqn_pop_window_backward(const float* params_dev, int32_t hidden, int32_t P, int32_t E,
@@ -1931,23 +1954,12 @@ int mz_drqn_pop_window_backward(const float* params_dev, int32_t hidden, int32_t
                                 const float* stash_dev, const float* d_dev,
                                 const double* ep_loss_dev, float* gpart_dev, float* grads_dev,
                                 float* loss_dev, void* stream) {
-  if (!params_dev || !burn_in_dev || !mem_dev || !wdir_dev || !win_off_dev || !win_tot_dev ||
-      !stash_dev || !d_dev || !ep_loss_dev || !gpart_dev || !grads_dev || !loss_dev)
-    return fail(MZ_EINVAL, "mz_drqn_pop_window_backward: null pointer");
-  if (int rc = drqn_pop_args("mz_drqn_pop_window_backward", hidden, P, E, "E")) return rc;
-  if (int rc = drqn_win_args("mz_drqn_pop_window_backward", hidden, T, K_max)) return rc;
-  if (int rc = drqn_seq_args("mz_drqn_pop_window_backward", hidden, E, L, capacity)) return rc;
-  StreamGuard g(stream);
-  MzDrqnPopWin q{{mz_drqn_flat_net(params_dev), 0, E, L, T, K_max, capacity, 0.0f, mem_dev,
-                  nullptr, nullptr, wdir_dev, win_off_dev, win_tot_dev, nullptr,
-                  const_cast<float*>(stash_dev), nullptr, nullptr, const_cast<float*>(d_dev),
-                  nullptr, gpart_dev},
-                 P, nullptr, burn_in_dev, nullptr, due_dev};
-  MZ_HIP(mz_launch_drqn_pop_window_backward(q, static_cast<hipStream_t>(stream)));
-  MzDrqnPopReduce r{P, E, 5 * E, gpart_dev, ep_loss_dev, wdir_dev + (size_t)MZ_DRQN_WDIR_M * E,
-                    win_tot_dev, grads_dev, loss_dev, due_dev};
-  MZ_HIP(mz_launch_drqn_pop_reduce(r, static_cast<hipStream_t>(stream)));
-  return MZ_OK;
+  if (!burn_in_dev) return fail(MZ_EINVAL, "mz_drqn_pop_window_backward: null pointer");
+  return drqn_window_backward(
+      "mz_drqn_pop_window_backward", hidden, P, burn_in_dev, due_dev,
+      MzDrqnWin{drqn_backward(drqn_flat_net(params_dev), E, L, capacity, mem_dev, stash_dev, d_dev,
+                              gpart_dev), T, K_max, nullptr, wdir_dev, win_off_dev, win_tot_dev},
+      ep_loss_dev, drqn_flat_net(grads_dev), loss_dev, stream);
 }
 
 int mz_drqn_pop_sync(const float* src_dev, float* dst_dev, const int32_t* mask_dev, int32_t P,

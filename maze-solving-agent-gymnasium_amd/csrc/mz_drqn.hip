@@ -43,26 +43,27 @@
 //   k_drqn_win_sample  k_drqn_sample's body for the slots, then one window per episode and the
 //                      window directory; a window owns m + 2 rows (entry state, m steps, guard),
 //                      so the row buffers hold E (T + 2) rows whatever L and K are.
-//   k_drqn_win_fwd / k_drqn_win_bwd   the sequence kernels' lane layout and per-step arithmetic
-//                      over steps b .. of the episode from the stored state; the burn-in steps only
-//                      advance the state, BPTT covers the m training steps. k_drqn_reduce sums the
-//                      per-window partials.
+//   k_drqn_win_fwd / k_drqn_win_bwd   the sequence kernels' time loops (drqn_unroll_fwd / _bwd: a
+//                      whole episode is the window b = 0, k = 0, m = n from zero state) over steps
+//                      b .. of the episode from the stored state; the burn-in steps only advance the
+//                      state, BPTT covers the m training steps. k_drqn_reduce sums the per-window
+//                      partials.
 // Populations (trainers/drqn_population.py VectorRecurrentDQNPopulation): P independent learners
 // over B = P b instances, learner p owning instances [p b, (p + 1) b), flat [P][5252] parameters.
-// Every kernel above is a thin wrapper of a __device__ body; its k_drqn_pop_* twin moves the
-// single-learner argument struct to learner p's rows (parameters, ring, directory, row buffers,
-// eps / seed / gamma / update count) and calls the same body, so a learner's results are the
-// single-learner kernels' bits by construction. Grids: act P x ceil(b / 16) workgroups (none
-// straddles two learners); store (<= 256, P) workgroups, learner p's run of the finished list
-// found by two binary searches; sample P waves; the sequence kernels P E waves; reduce and the
-// target sync (21, P). Waves of a learner that is not due exit at once.
-// Replay windows in a population (T shared, burn-in K_p and stored / zero state per learner): the
-// same rule. k_drqn_snapshot serves B = P b as it is; k_drqn_pop_snap_store (grid as the store's,
-// launched before it), k_drqn_pop_win_sample (P waves), k_drqn_pop_win_fwd / _bwd (P E waves) move
-// the window structs to learner p's rows; k_drqn_pop_reduce reads the m row of learner p's
-// directory block. A K_p that breaks the rule (negative, no multiple of T, above K_max) lives on
-// the device and cannot be refused: that learner's view gets K = -1, which no window passes, so
-// its batch has no window, nothing of its row buffers is written and its partials are zero.
+// Every kernel above but k_drqn_snapshot (which serves B = P b as it is) moves its single-learner
+// argument struct to learner p's rows (parameters, ring, directory, row buffers, eps / seed /
+// gamma / update count / burn-in) and runs the __device__ body on it; the single learner is the
+// launch with P = 1, b = B and null per-learner arrays, where every row offset is zero and the
+// struct's by-value fields stand. Grids: act P x ceil(b / 16) workgroups (none straddles two
+// learners); store and snapshot store (., P) workgroups, learner p's run of the finished list
+// found by two binary searches; the samplers P waves; the sequence and window kernels P E waves;
+// reduce and the target sync k_drqn_pop_sync (21, P). Waves of a learner that is not due exit at
+// once.
+// Replay windows in a population: T is shared, the burn-in K_p and stored / zero state are per
+// learner; k_drqn_reduce reads the m row of learner p's directory block. A K_p that breaks the
+// rule (negative, no multiple of T, above K_max) lives on the device and cannot be refused: that
+// learner's view gets K = -1, which no window passes, so its batch has no window, nothing of its
+// row buffers is written and its partials are zero.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -203,28 +204,24 @@ __device__ __forceinline__ void drqn_act_body(const MzDrqnAct& q, const int blk,
   }
 }
 
-__global__ __launch_bounds__(ACT_T) void k_drqn_act(MzDrqnAct q) {
-  drqn_act_body(q, blockIdx.x, (size_t)q.B);
-}
-
 // learner p's view of a population's flat [P][5252] parameters
 __device__ __forceinline__ MzDrqnNet drqn_net_row(const MzDrqnNet& n, const int p) {
   const size_t o = (size_t)p * MZ_DRQN_PARAMS;
   return MzDrqnNet{n.w_ih + o, n.w_hh + o, n.b_ih + o, n.b_hh + o, n.fc_w + o, n.fc_b + o};
 }
 
-// The population's acting step: workgroup (p, blk) runs k_drqn_act's body on learner p's block of
-// b instances with its own parameters, eps and seed, so no workgroup straddles two learners (the
-// tail workgroup of a learner is partly idle).
-__global__ __launch_bounds__(ACT_T) void k_drqn_pop_act(MzDrqnPopAct q) {
+// The acting step: workgroup (p, blk) runs the body on learner p's block of b instances with its
+// own parameters, eps and seed, so no workgroup straddles two learners (the tail workgroup of a
+// learner is partly idle).
+__global__ __launch_bounds__(ACT_T) void k_drqn_act(MzDrqnPopAct q) {
   const int bpl = (q.b + IPB - 1) / IPB;
   const int p = blockIdx.x / bpl;
   const size_t i0 = (size_t)p * q.b;
   MzDrqnAct a = q.a;
   a.p = drqn_net_row(q.a.p, p);
   a.B = q.b;
-  a.eps = q.eps[p];
-  a.seed = q.seed[p];
+  if (q.eps) a.eps = q.eps[p];
+  if (q.seed) a.seed = q.seed[p];
   a.obs6 += i0 * NX;
   a.t += i0;
   a.h += i0;
@@ -274,10 +271,6 @@ __device__ __forceinline__ void drqn_store_body(const MzDrqnStore& q, const int3
   }
 }
 
-__global__ __launch_bounds__(256) void k_drqn_store(MzDrqnStore q) {
-  drqn_store_body(q, q.fin_id, q.fin_len, min(max(*q.fin_count, 0), q.B), blockIdx.x, gridDim.x);
-}
-
 __device__ __forceinline__ void drqn_ring_advance(int64_t* ring, const int64_t nfin,
                                                   const int64_t cap) {
   const int64_t head = ring[0], count = ring[1];
@@ -286,13 +279,11 @@ __device__ __forceinline__ void drqn_ring_advance(int64_t* ring, const int64_t n
   ring[1] = count + nfin < cap ? count + nfin : cap;
 }
 
-// after k_drqn_store (same stream): head and count move on by the stored episodes
-__global__ void k_drqn_ring(const int32_t* fin_count, int B, int64_t cap, int64_t* ring) {
-  drqn_ring_advance(ring, min(max(*fin_count, 0), B), cap);
-}
-
 // The finished list is in instance order, so learner p's episodes are the run [lo, hi) of it whose
-// instances lie in [p b, (p + 1) b): two binary searches.
+// instances lie in [p b, (p + 1) b): two binary searches. With P = 1 and mz_ppo_scan's list (ids in
+// [0, B), ascending) that is the whole list. The stores rely on that order also for one learner:
+// an id out of range or out of order in the list can hide entries after it from the searches, and
+// the ring then advances by hi - lo, not by the list's length.
 __device__ __forceinline__ int drqn_first_at_least(const int32_t* a, const int n, const int64_t v) {
   int lo = 0, hi = n;
   while (lo < hi) {
@@ -314,9 +305,9 @@ __device__ __forceinline__ void drqn_pop_run(const MzDrqnPopStore& q, const int 
   drqn_pop_run(q.s.fin_id, q.s.fin_count, q.s.B, q.b, p, lo, hi);
 }
 
-// workgroups (., p): k_drqn_store's body on learner p's run and learner p's ring. A learner with
-// no finished episode writes nothing.
-__global__ __launch_bounds__(256) void k_drqn_pop_store(MzDrqnPopStore q) {
+// workgroups (., p): learner p's run into learner p's ring. A learner with no finished episode
+// writes nothing.
+__global__ __launch_bounds__(256) void k_drqn_store(MzDrqnPopStore q) {
   const int p = blockIdx.y;
   int lo, hi;
   drqn_pop_run(q, p, &lo, &hi);
@@ -329,7 +320,8 @@ __global__ __launch_bounds__(256) void k_drqn_pop_store(MzDrqnPopStore q) {
   drqn_store_body(s, q.s.fin_id + lo, q.s.fin_len + lo, hi - lo, blockIdx.x, gridDim.x);
 }
 
-__global__ __launch_bounds__(WAVE) void k_drqn_pop_ring(MzDrqnPopStore q) {
+// after k_drqn_store (same stream): learner p's head and count move on by its stored episodes
+__global__ __launch_bounds__(WAVE) void k_drqn_ring(MzDrqnPopStore q) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= q.P) return;
   int lo, hi;
@@ -384,19 +376,14 @@ __device__ __forceinline__ void drqn_sample_body(const MzDrqnSample& q, int32_t*
   }
 }
 
-__global__ __launch_bounds__(WAVE) void k_drqn_sample(MzDrqnSample q) {
-  extern __shared__ int32_t chosen[];  // [E]
-  drqn_sample_body(q, chosen);
-}
-
-// one wave per learner: k_drqn_sample's body on learner p's ring with its seed and update count
-__global__ __launch_bounds__(WAVE) void k_drqn_pop_sample(MzDrqnPopSample q) {
+// one wave per learner: the body on learner p's ring with its seed and update count
+__global__ __launch_bounds__(WAVE) void k_drqn_sample(MzDrqnPopSample q) {
   extern __shared__ int32_t chosen[];  // [E]
   const int p = blockIdx.x;
   if (q.due && q.due[p] == 0) return;
   MzDrqnSample s = q.s;
-  s.seed = q.seed[p];
-  s.counter = q.counter[p];
+  if (q.seed) s.seed = q.seed[p];
+  if (q.counter) s.counter = q.counter[p];
   s.ring += 2 * (size_t)p;
   s.mem_len += (size_t)p * s.cap;
   s.d_slot += (size_t)p * s.E;
@@ -481,33 +468,51 @@ __device__ __forceinline__ void drqn_fwd_head(const DrqnFwdLane& w, const float 
   q3 = __shfl(qa, 3);
 }
 
-__device__ __forceinline__ void drqn_seq_fwd_body(const MzDrqnSeq& q, const int e) {
+// What one wave unrolls: steps b .. b + kb + m - 1 of the n-step episode in ring slot `slot`. The kb
+// burn-in steps only advance the state; training step i is row `row + i` of the row buffers. A
+// whole episode is b = kb = 0, m = n from zero state (snap null) with no entry row; a window
+// starts from snapshot b / T (or zero) and keeps the state that enters its first training step in
+// the row above `row` (entry).
+struct DrqnSpan {
+  int slot, n, b, kb, m;
+  int64_t row;
+  bool entry;
+  const float* snap;
+};
+
+// The forward time loop of both update kinds. Target mode: max_a Q'_t of the m training steps and
+// of the step after them (rows row .. row + m). Source mode: the stash, Q_t[a_t], y_t, the
+// residual scaled by 2 / tot[1] and the span's sum of squared residuals (float64, time order).
+__device__ __forceinline__ void drqn_unroll_fwd(const MzDrqnUnroll& q, const int e,
+                                                const DrqnSpan& w, const int64_t* tot) {
   __shared__ __attribute__((aligned(16))) float hs[H];
   const int lane = threadIdx.x, u = lane & (H - 1), half = lane >> 5;
-  const int n = q.d_len[e], slot = q.d_slot[e];
-  const int64_t off = q.d_off[e];
-  if (n < 1 || n > q.L || slot < 0 || slot >= q.cap || off < 0 ||
-      off + n + 1 > (int64_t)q.E * (q.L + 1))
-    return;
-  const uint32_t* ep = q.mem + (size_t)slot * (q.L + 1) * ROW;
+  const uint32_t* ep = q.mem + ((size_t)w.slot * (q.L + 1) + w.b) * ROW;
   const int r0 = half * 2 * H + u, r1 = r0 + H;  // (i_u, f_u) or (g_u, o_u)
-  DrqnFwdLane w;
-  drqn_fwd_lane(q.p, lane, w);
+  DrqnFwdLane lw;
+  drqn_fwd_lane(q.p, lane, lw);
   float hb[H];
 #pragma unroll
-  for (int k = 0; k < H; ++k) hb[k] = 0.0f;
-  float c = 0.0f;
-  const int steps = q.target ? n + 1 : n;
-  const float inv = q.target ? 0.0f : (float)(1.0 / (double)q.d_tot[1]);
-  const bool term = q.mem_term[slot] != 0;
+  for (int k = 0; k < H; ++k) hb[k] = w.snap ? w.snap[k] : 0.0f;
+  float c = w.snap ? w.snap[H + u] : 0.0f;
+  float h = w.snap ? w.snap[u] : 0.0f;
+  const int steps = w.kb + w.m + (q.target ? 1 : 0);
+  const float inv = q.target ? 0.0f : (float)(1.0 / (double)tot[1]);
+  const bool term = q.mem_term[w.slot] != 0;
   double sq = 0.0;
-  for (int t = 0; t < steps; ++t) {
-    const uint4 ra = *reinterpret_cast<const uint4*>(ep + (size_t)t * ROW);
-    const uint4 rb = *reinterpret_cast<const uint4*>(ep + (size_t)t * ROW + 4);
-    float h, v0, v1, q0, q1, q2, q3;
-    drqn_fwd_step(w, ra, rb, hs, u, half, hb, c, h, v0, v1);
-    drqn_fwd_head(w, hb, q0, q1, q2, q3);
-    const int64_t R = off + t;
+  for (int i = 0;; ++i) {
+    if (w.entry && !q.target && i == w.kb) {  // the state entering the first training step
+      float* st = q.stash + (size_t)(w.row - 1) * STASH;
+      if (!half) st[G4 + u] = c; else st[G4 + H + u] = h;
+    }
+    if (i >= steps) break;
+    const uint4 ra = *reinterpret_cast<const uint4*>(ep + (size_t)i * ROW);
+    const uint4 rb = *reinterpret_cast<const uint4*>(ep + (size_t)i * ROW + 4);
+    float v0, v1, q0, q1, q2, q3;
+    drqn_fwd_step(lw, ra, rb, hs, u, half, hb, c, h, v0, v1);
+    if (i < w.kb) continue;  // burn-in: no q, no loss term
+    drqn_fwd_head(lw, hb, q0, q1, q2, q3);
+    const int64_t R = w.row + (i - w.kb);
     if (q.target) {
       if (lane == 0) q.qmax[R] = fmaxf(fmaxf(q0, q1), fmaxf(q2, q3));
       continue;
@@ -519,7 +524,7 @@ __device__ __forceinline__ void drqn_seq_fwd_body(const MzDrqnSeq& q, const int 
     const int a = (int)rb.z & 3;
     const float rew = __uint_as_float(rb.w);
     const float qsel = a == 0 ? q0 : (a == 1 ? q1 : (a == 2 ? q2 : q3));
-    const bool last = t == n - 1;
+    const bool last = w.b + i == w.n - 1;
     const float y = (last && term) ? rew : fmaf(q.gamma, q.qmax[R + 1], rew);
     const float d = qsel - y;
     sq += (double)d * (double)d;
@@ -532,23 +537,15 @@ __device__ __forceinline__ void drqn_seq_fwd_body(const MzDrqnSeq& q, const int 
   if (!q.target && lane == 0) q.ep_loss[e] = sq;
 }
 
-__global__ __launch_bounds__(WAVE) void k_drqn_seq_fwd(MzDrqnSeq q) {
-  drqn_seq_fwd_body(q, blockIdx.x);
-}
-
-// learner p's view of a population's update: its parameters, ring, directory ([P][E]) and row
-// buffers ([P][E (L + 1)]), its discount factor
-__device__ __forceinline__ MzDrqnSeq drqn_seq_row(const MzDrqnPopSeq& q, const int p) {
-  MzDrqnSeq s = q.q;
-  const size_t E = (size_t)s.E, rows = E * (s.L + 1);
-  s.p = drqn_net_row(q.q.p, p);
-  if (q.gamma) s.gamma = q.gamma[p];
+// learner p's view of what both update kinds share: its parameters, ring, discount factor and row
+// buffers ([P][rows])
+__device__ __forceinline__ void drqn_unroll_row(MzDrqnUnroll& s, const float* gamma, const int p,
+                                                const size_t rows) {
+  const size_t E = (size_t)s.E;
+  s.p = drqn_net_row(s.p, p);
+  if (gamma) s.gamma = gamma[p];
   s.mem += (size_t)p * s.cap * (s.L + 1) * ROW;
   if (s.mem_term) s.mem_term += (size_t)p * s.cap;
-  s.d_slot += p * E;
-  s.d_len += p * E;
-  s.d_off += p * E;
-  s.d_tot += 2 * (size_t)p;
   if (s.qmax) s.qmax += p * rows;
   if (s.stash) s.stash += p * rows * STASH;
   if (s.qa) s.qa += p * rows;
@@ -556,14 +553,39 @@ __device__ __forceinline__ MzDrqnSeq drqn_seq_row(const MzDrqnPopSeq& q, const i
   if (s.d) s.d += p * rows;
   if (s.ep_loss) s.ep_loss += p * E;
   if (s.gpart) s.gpart += p * E * MZ_DRQN_PARAMS;
+}
+
+// learner p's view of a whole-episode update: also its directory ([P][E])
+__device__ __forceinline__ MzDrqnSeq drqn_seq_row(const MzDrqnPopSeq& q, const int p) {
+  MzDrqnSeq s = q.q;
+  const size_t E = (size_t)s.u.E;
+  drqn_unroll_row(s.u, q.gamma, p, E * (s.u.L + 1));
+  s.d_slot += p * E;
+  s.d_len += p * E;
+  s.d_off += p * E;
+  s.d_tot += 2 * (size_t)p;
   return s;
 }
 
+// episode e of the directory as a span; false where it is not one the sampler writes. Step t is
+// row off + t, the target's q of step n row off + n.
+__device__ __forceinline__ bool drqn_episode(const MzDrqnSeq& q, const int e, DrqnSpan* w) {
+  const int n = q.d_len[e], slot = q.d_slot[e];
+  const int64_t off = q.d_off[e];
+  if (n < 1 || n > q.u.L || slot < 0 || slot >= q.u.cap || off < 0 ||
+      off + n + 1 > (int64_t)q.u.E * (q.u.L + 1))
+    return false;
+  *w = DrqnSpan{slot, n, 0, 0, n, off, false, nullptr};
+  return true;
+}
+
 // one wave per (learner, episode); a learner that is not due exits at once
-__global__ __launch_bounds__(WAVE) void k_drqn_pop_seq_fwd(MzDrqnPopSeq q) {
-  const int p = blockIdx.x / q.q.E;
+__global__ __launch_bounds__(WAVE) void k_drqn_seq_fwd(MzDrqnPopSeq q) {
+  const int p = blockIdx.x / q.q.u.E, e = blockIdx.x % q.q.u.E;
   if (q.due && q.due[p] == 0) return;
-  drqn_seq_fwd_body(drqn_seq_row(q, p), blockIdx.x % q.q.E);
+  const MzDrqnSeq s = drqn_seq_row(q, p);
+  DrqnSpan w;
+  if (drqn_episode(s, e, &w)) drqn_unroll_fwd(s.u, e, w, s.d_tot);
 }
 
 // ---- back-propagation through time -----------------------------------------------------------
@@ -690,25 +712,26 @@ __device__ __forceinline__ void drqn_bwd_write(const DrqnBwdLane& g, float* gp, 
   }
 }
 
-__device__ __forceinline__ void drqn_seq_bwd_body(const MzDrqnSeq& q, const int e) {
+// the partial of a span that is not one the sampler writes
+__device__ __forceinline__ void drqn_zero_partial(float* gp) {
+  for (int k = threadIdx.x; k < MZ_DRQN_PARAMS; k += WAVE) gp[k] = 0.0f;
+}
+
+// The backward time loop of both update kinds: BPTT over the span's m training steps into partial
+// e. Every step finds (c, h) of its predecessor one row up; the first step's is the entry row, or
+// zero where there is none. Nothing flows into the burn-in.
+__device__ __forceinline__ void drqn_unroll_bwd(const MzDrqnUnroll& q, const int e,
+                                                const DrqnSpan& w) {
   __shared__ __attribute__((aligned(16))) float dzs[G4];
   const int lane = threadIdx.x, u = lane & (H - 1), half = lane >> 5;
-  const int n = q.d_len[e], slot = q.d_slot[e];
-  const int64_t off = q.d_off[e];
-  float* gp = q.gpart + (size_t)e * MZ_DRQN_PARAMS;
-  if (n < 1 || n > q.L || slot < 0 || slot >= q.cap || off < 0 ||
-      off + n + 1 > (int64_t)q.E * (q.L + 1)) {
-    for (int k = lane; k < MZ_DRQN_PARAMS; k += WAVE) gp[k] = 0.0f;
-    return;
-  }
-  const uint32_t* ep = q.mem + (size_t)slot * (q.L + 1) * ROW;
+  const uint32_t* ep = q.mem + ((size_t)w.slot * (q.L + 1) + w.b + w.kb) * ROW;
   DrqnBwdLane g;
   drqn_bwd_lane(q.p, u, half, g);
-  for (int t = n - 1; t >= 0; --t) {
-    const int64_t R = off + t;
+  for (int t = w.m - 1; t >= 0; --t) {
+    const int64_t R = w.row + t;
     const float* st = q.stash + (size_t)R * STASH;
     float cp = 0.0f, hp[H];
-    if (t) {
+    if (t || w.entry) {
       drqn_bwd_prev(st, u, cp, hp);
     } else {
 #pragma unroll
@@ -718,17 +741,19 @@ __device__ __forceinline__ void drqn_seq_bwd_body(const MzDrqnSeq& q, const int 
     const uint4 rb = *reinterpret_cast<const uint4*>(ep + (size_t)t * ROW + 4);
     drqn_bwd_step(g, st, cp, hp, ra, rb, q.d[R], dzs, u, half);
   }
-  drqn_bwd_write(g, gp, lane);
+  drqn_bwd_write(g, q.gpart + (size_t)e * MZ_DRQN_PARAMS, lane);
 }
 
-__global__ __launch_bounds__(WAVE) void k_drqn_seq_bwd(MzDrqnSeq q) {
-  drqn_seq_bwd_body(q, blockIdx.x);
-}
-
-__global__ __launch_bounds__(WAVE) void k_drqn_pop_seq_bwd(MzDrqnPopSeq q) {
-  const int p = blockIdx.x / q.q.E;
+__global__ __launch_bounds__(WAVE) void k_drqn_seq_bwd(MzDrqnPopSeq q) {
+  const int p = blockIdx.x / q.q.u.E, e = blockIdx.x % q.q.u.E;
   if (q.due && q.due[p] == 0) return;
-  drqn_seq_bwd_body(drqn_seq_row(q, p), blockIdx.x % q.q.E);
+  const MzDrqnSeq s = drqn_seq_row(q, p);
+  DrqnSpan w;
+  if (!drqn_episode(s, e, &w)) {
+    drqn_zero_partial(s.u.gpart + (size_t)e * MZ_DRQN_PARAMS);
+    return;
+  }
+  drqn_unroll_bwd(s.u, e, w);
 }
 
 // parameter k's partials summed over the episodes in index order (float64, rounded once)
@@ -748,33 +773,26 @@ __device__ __forceinline__ float drqn_reduce_loss(const double* ep_loss, const i
   return steps > 0 ? (float)(s / (double)steps) : 0.0f;
 }
 
+// workgroups (., p): learner p's E partials into its six gradient segments (learner 0's, moved by
+// p rows of the flat [P][5252] gradient), and its loss. Learner p's lengths are d_len + p ld:
+// ld = E for the [P][E] episode directory, 5 E for the m row of the [P][5][E] window directory.
 __global__ __launch_bounds__(256) void k_drqn_reduce(MzDrqnReduce q) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < MZ_DRQN_PARAMS) {
-    const float s = drqn_reduce_grad(q.gpart, q.E, k);
-    float* dst;
-    int o;
-    if (k < P_WHH) { dst = q.g[0]; o = k - P_WIH; }
-    else if (k < P_BIH) { dst = q.g[1]; o = k - P_WHH; }
-    else if (k < P_BHH) { dst = q.g[2]; o = k - P_BIH; }
-    else if (k < P_FCW) { dst = q.g[3]; o = k - P_BHH; }
-    else if (k < P_FCB) { dst = q.g[4]; o = k - P_FCW; }
-    else { dst = q.g[5]; o = k - P_FCB; }
-    dst[o] = s;
-  }
-  if (k == 0) *q.loss = drqn_reduce_loss(q.ep_loss, q.d_len, q.d_tot, q.E);
-}
-
-// workgroups (., p): learner p's E partials into row p of the flat [P][5252] gradient (the flat
-// order is the partials' order), and its loss. Learner p's lengths are d_len + p ld: ld = E for the
-// [P][E] episode directory, 5 E for the m row of the [P][5][E] window directory.
-__global__ __launch_bounds__(256) void k_drqn_pop_reduce(MzDrqnPopReduce q) {
   const int p = blockIdx.y;
   if (q.due && q.due[p] == 0) return;
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   const size_t E = (size_t)q.E;
-  if (k < MZ_DRQN_PARAMS)
-    q.g[(size_t)p * MZ_DRQN_PARAMS + k] = drqn_reduce_grad(q.gpart + p * E * MZ_DRQN_PARAMS, q.E, k);
+  if (k < MZ_DRQN_PARAMS) {
+    const float s = drqn_reduce_grad(q.gpart + p * E * MZ_DRQN_PARAMS, q.E, k);
+    float* dst;
+    int o;
+    if (k < P_WHH) { dst = q.g.w_ih; o = k - P_WIH; }
+    else if (k < P_BIH) { dst = q.g.w_hh; o = k - P_WHH; }
+    else if (k < P_BHH) { dst = q.g.b_ih; o = k - P_BIH; }
+    else if (k < P_FCW) { dst = q.g.b_hh; o = k - P_BHH; }
+    else if (k < P_FCB) { dst = q.g.fc_w; o = k - P_FCW; }
+    else { dst = q.g.fc_b; o = k - P_FCB; }
+    dst[(size_t)p * MZ_DRQN_PARAMS + o] = s;
+  }
   if (k == 0)
     q.loss[p] = drqn_reduce_loss(q.ep_loss + p * E, q.d_len + (size_t)p * q.ld,
                                  q.d_tot + 2 * (size_t)p, q.E);
@@ -828,15 +846,10 @@ __device__ __forceinline__ void drqn_snap_store_body(const MzDrqnSnapStore& q,
   }
 }
 
-__global__ __launch_bounds__(256) void k_drqn_snap_store(MzDrqnSnapStore q) {
-  drqn_snap_store_body(q, q.fin_id, q.fin_len, min(max(*q.fin_count, 0), q.B), blockIdx.x,
-                       gridDim.x);
-}
-
-// workgroups (., p), before k_drqn_pop_store: k_drqn_snap_store's body on learner p's run of the
-// finished list (k_drqn_pop_store's run), its ring and its state memory; snap_rec stays indexed by
-// the global instance. A learner with no finished episode writes nothing.
-__global__ __launch_bounds__(256) void k_drqn_pop_snap_store(MzDrqnPopSnapStore q) {
+// workgroups (., p), before k_drqn_store: learner p's run of the finished list (k_drqn_store's
+// run) with its ring and its state memory; snap_rec stays indexed by the global instance. A
+// learner with no finished episode writes nothing.
+__global__ __launch_bounds__(256) void k_drqn_snap_store(MzDrqnPopSnapStore q) {
   const int p = blockIdx.y;
   int lo, hi;
   drqn_pop_run(q.s.fin_id, q.s.fin_count, q.s.B, q.b, p, &lo, &hi);
@@ -887,11 +900,6 @@ __device__ __forceinline__ void drqn_win_sample_body(const MzDrqnWinSample& q, i
   }
 }
 
-__global__ __launch_bounds__(WAVE) void k_drqn_win_sample(MzDrqnWinSample q) {
-  extern __shared__ int32_t chosen[];  // [E]
-  drqn_win_sample_body(q, chosen);
-}
-
 // learner p's burn-in where it keeps the rule (0 <= K_p <= K_max, a multiple of T), else -1, which
 // no window passes: the sampler then writes none and drqn_window refuses every one
 __device__ __forceinline__ int drqn_pop_burn_in(const int32_t* burn_in, const int p, const int T,
@@ -900,18 +908,18 @@ __device__ __forceinline__ int drqn_pop_burn_in(const int32_t* burn_in, const in
   return (K >= 0 && K <= Kmax && K % T == 0) ? K : -1;
 }
 
-// one wave per learner: k_drqn_win_sample's body on learner p's ring with its seed, update count
-// and burn-in; its directory block [5][E] is the single layout
-__global__ __launch_bounds__(WAVE) void k_drqn_pop_win_sample(MzDrqnPopWinSample q) {
+// one wave per learner: the body on learner p's ring with its seed, update count and burn-in, and
+// its directory block [5][E]
+__global__ __launch_bounds__(WAVE) void k_drqn_win_sample(MzDrqnPopWinSample q) {
   extern __shared__ int32_t chosen[];  // [E]
   const int p = blockIdx.x;
   if (q.due && q.due[p] == 0) return;
   MzDrqnWinSample w = q.w;
   const size_t E = (size_t)w.s.E;
-  w.K = drqn_pop_burn_in(q.burn_in, p, w.T, q.w.K);
+  if (q.burn_in) w.K = drqn_pop_burn_in(q.burn_in, p, w.T, q.w.K);
   w.wdir += (size_t)p * 5 * E;
-  w.s.seed = q.seed[p];
-  w.s.counter = q.counter[p];
+  if (q.seed) w.s.seed = q.seed[p];
+  if (q.counter) w.s.counter = q.counter[p];
   w.s.ring += 2 * (size_t)p;
   w.s.mem_len += (size_t)p * w.s.cap;
   w.s.d_slot = w.wdir + MZ_DRQN_WDIR_SLOT * E;
@@ -921,195 +929,107 @@ __global__ __launch_bounds__(WAVE) void k_drqn_pop_win_sample(MzDrqnPopWinSample
   drqn_win_sample_body(w, chosen);
 }
 
-// window e of the directory; false where it is not one the sampler writes
-struct DrqnWindow {
-  int n, slot, b, kb, m;
-  int64_t off;
-};
-__device__ __forceinline__ bool drqn_window(const MzDrqnWin& q, const int e, DrqnWindow* w) {
-  w->slot = q.wdir[MZ_DRQN_WDIR_SLOT * q.E + e];
-  w->n = q.wdir[MZ_DRQN_WDIR_LEN * q.E + e];
-  w->b = q.wdir[MZ_DRQN_WDIR_B * q.E + e];
-  w->kb = q.wdir[MZ_DRQN_WDIR_K * q.E + e];
-  w->m = q.wdir[MZ_DRQN_WDIR_M * q.E + e];
-  w->off = q.w_off[e];
-  const int64_t rows = (int64_t)q.E * (min(q.T, q.L) + MZ_DRQN_WIN_PAD);
-  return w->n >= 1 && w->n <= q.L && w->slot >= 0 && w->slot < q.cap && w->m >= 1 && w->m <= q.T &&
-         w->b >= 0 && w->b % q.T == 0 && w->kb >= 0 && w->kb <= q.K &&
-         (int64_t)w->b + w->kb + w->m <= w->n && w->off >= 0 &&
-         w->off + w->m + MZ_DRQN_WIN_PAD <= rows;
+// Window e of the directory as a span; false where it is not one the sampler writes. Rows: the
+// window's first row (w_off) holds (c, h) entering the first training step, where the backward
+// finds them; training step i is row w_off + 1 + i; the target's q of step b + kb + m is in the
+// guard row. The entry state is snapshot b / T, zero where b == 0 or there is no state memory.
+__device__ __forceinline__ bool drqn_window(const MzDrqnWin& q, const int e, DrqnSpan* w) {
+  const int E = q.u.E;
+  w->slot = q.wdir[MZ_DRQN_WDIR_SLOT * E + e];
+  w->n = q.wdir[MZ_DRQN_WDIR_LEN * E + e];
+  w->b = q.wdir[MZ_DRQN_WDIR_B * E + e];
+  w->kb = q.wdir[MZ_DRQN_WDIR_K * E + e];
+  w->m = q.wdir[MZ_DRQN_WDIR_M * E + e];
+  const int64_t off = q.w_off[e];
+  w->row = off + 1;
+  w->entry = true;
+  const int64_t rows = (int64_t)E * (min(q.T, q.u.L) + MZ_DRQN_WIN_PAD);
+  if (!(w->n >= 1 && w->n <= q.u.L && w->slot >= 0 && w->slot < q.u.cap && w->m >= 1 &&
+        w->m <= q.T && w->b >= 0 && w->b % q.T == 0 && w->kb >= 0 && w->kb <= q.K &&
+        (int64_t)w->b + w->kb + w->m <= w->n && off >= 0 && off + w->m + MZ_DRQN_WIN_PAD <= rows))
+    return false;
+  w->snap = (q.mem_state && w->b > 0)
+      ? q.mem_state + ((size_t)w->slot * drqn_windows(q.u.L, q.T) + w->b / q.T) * SNAP : nullptr;
+  return true;
 }
 
-// drqn_seq_fwd_body over steps b .. b + kb + m - 1 (the target: one more) of the window's episode
-// from the stored state (snapshot b / T; zero where b == 0 or there is no state memory), the same
-// lane layout and per-step arithmetic. The kb burn-in steps only advance the state. Rows: the
-// window's first row holds (c, h) entering the first training step, where the backward finds them;
-// training step i is row off + 1 + i; the target's q of step b + kb + m is in the guard row.
-__device__ __forceinline__ void drqn_win_fwd_body(const MzDrqnWin& q, const int e) {
-  __shared__ __attribute__((aligned(16))) float hs[H];
-  const int lane = threadIdx.x, u = lane & (H - 1), half = lane >> 5;
-  DrqnWindow w;
-  if (!drqn_window(q, e, &w)) return;
-  const int n = w.n, kb = w.kb;
-  const int64_t off = w.off;
-  const uint32_t* ep = q.mem + ((size_t)w.slot * (q.L + 1) + w.b) * ROW;
-  const int r0 = half * 2 * H + u, r1 = r0 + H;  // (i_u, f_u) or (g_u, o_u)
-  DrqnFwdLane lw;
-  drqn_fwd_lane(q.p, lane, lw);
-  const float* snap = (q.mem_state && w.b > 0)
-      ? q.mem_state + ((size_t)w.slot * drqn_windows(q.L, q.T) + w.b / q.T) * SNAP : nullptr;
-  float hb[H];
-#pragma unroll
-  for (int k = 0; k < H; ++k) hb[k] = snap ? snap[k] : 0.0f;
-  float c = snap ? snap[H + u] : 0.0f;
-  float h = snap ? snap[u] : 0.0f;
-  const int steps = kb + w.m + (q.target ? 1 : 0);
-  const float inv = q.target ? 0.0f : (float)(1.0 / (double)q.w_tot[1]);
-  const bool term = q.mem_term[w.slot] != 0;
-  double sq = 0.0;
-  for (int i = 0;; ++i) {
-    if (!q.target && i == kb) {  // the state entering the first training step
-      float* st = q.stash + (size_t)off * STASH;
-      if (!half) st[G4 + u] = c; else st[G4 + H + u] = h;
-    }
-    if (i >= steps) break;
-    const uint4 ra = *reinterpret_cast<const uint4*>(ep + (size_t)i * ROW);
-    const uint4 rb = *reinterpret_cast<const uint4*>(ep + (size_t)i * ROW + 4);
-    float v0, v1, q0, q1, q2, q3;
-    drqn_fwd_step(lw, ra, rb, hs, u, half, hb, c, h, v0, v1);
-    if (i < kb) continue;  // burn-in: no q, no loss term
-    drqn_fwd_head(lw, hb, q0, q1, q2, q3);
-    const int64_t R = off + 1 + (i - kb);
-    if (q.target) {
-      if (lane == 0) q.qmax[R] = fmaxf(fmaxf(q0, q1), fmaxf(q2, q3));
-      continue;
-    }
-    float* st = q.stash + (size_t)R * STASH;
-    st[r0] = v0;
-    st[r1] = v1;
-    if (!half) st[G4 + u] = c; else st[G4 + H + u] = h;
-    const int a = (int)rb.z & 3;
-    const float rew = __uint_as_float(rb.w);
-    const float qsel = a == 0 ? q0 : (a == 1 ? q1 : (a == 2 ? q2 : q3));
-    const bool last = w.b + i == n - 1;
-    const float y = (last && term) ? rew : fmaf(q.gamma, q.qmax[R + 1], rew);
-    const float d = qsel - y;
-    sq += (double)d * (double)d;
-    if (lane == 0) {
-      q.qa[R] = qsel;
-      q.y[R] = y;
-      q.d[R] = 2.0f * d * inv;
-    }
-  }
-  if (!q.target && lane == 0) q.ep_loss[e] = sq;
-}
-
-__global__ __launch_bounds__(WAVE) void k_drqn_win_fwd(MzDrqnWin q) {
-  drqn_win_fwd_body(q, blockIdx.x);
-}
-
-// drqn_seq_bwd_body over the window's m training steps: the step before the first is the entry
-// row, so every step finds (c, h) of its predecessor one row up; nothing flows into the burn-in.
-__device__ __forceinline__ void drqn_win_bwd_body(const MzDrqnWin& q, const int e) {
-  __shared__ __attribute__((aligned(16))) float dzs[G4];
-  const int lane = threadIdx.x, u = lane & (H - 1), half = lane >> 5;
-  float* gp = q.gpart + (size_t)e * MZ_DRQN_PARAMS;
-  DrqnWindow w;
-  if (!drqn_window(q, e, &w)) {
-    for (int k = lane; k < MZ_DRQN_PARAMS; k += WAVE) gp[k] = 0.0f;
-    return;
-  }
-  const uint32_t* ep = q.mem + ((size_t)w.slot * (q.L + 1) + w.b + w.kb) * ROW;
-  DrqnBwdLane g;
-  drqn_bwd_lane(q.p, u, half, g);
-  for (int t = w.m - 1; t >= 0; --t) {
-    const int64_t R = w.off + 1 + t;
-    const float* st = q.stash + (size_t)R * STASH;
-    float cp, hp[H];
-    drqn_bwd_prev(st, u, cp, hp);
-    const uint4 ra = *reinterpret_cast<const uint4*>(ep + (size_t)t * ROW);
-    const uint4 rb = *reinterpret_cast<const uint4*>(ep + (size_t)t * ROW + 4);
-    drqn_bwd_step(g, st, cp, hp, ra, rb, q.d[R], dzs, u, half);
-  }
-  drqn_bwd_write(g, gp, lane);
-}
-
-__global__ __launch_bounds__(WAVE) void k_drqn_win_bwd(MzDrqnWin q) {
-  drqn_win_bwd_body(q, blockIdx.x);
-}
-
-// learner p's view of a population's windowed update: its parameters, ring, state memory (only
-// where stored[p] != 0: otherwise zero state), directory block ([P][5][E]), row buffers
-// ([P][E (min(T, L) + 2)]), discount factor and burn-in
+// learner p's view of a population's windowed update: also its state memory (only where
+// stored[p] != 0: otherwise zero state), directory block ([P][5][E]) and burn-in
 __device__ __forceinline__ MzDrqnWin drqn_win_row(const MzDrqnPopWin& q, const int p) {
   MzDrqnWin s = q.q;
-  const size_t E = (size_t)s.E, rows = E * (min(s.T, s.L) + MZ_DRQN_WIN_PAD);
-  s.p = drqn_net_row(q.q.p, p);
-  if (q.gamma) s.gamma = q.gamma[p];
-  s.K = drqn_pop_burn_in(q.burn_in, p, s.T, q.q.K);
-  s.mem += (size_t)p * s.cap * (s.L + 1) * ROW;
-  if (s.mem_term) s.mem_term += (size_t)p * s.cap;
-  s.mem_state = (s.mem_state && q.stored && q.stored[p] != 0)
-      ? s.mem_state + (size_t)p * s.cap * drqn_windows(s.L, s.T) * SNAP : nullptr;
+  const size_t E = (size_t)s.u.E;
+  drqn_unroll_row(s.u, q.gamma, p, E * (min(s.T, s.u.L) + MZ_DRQN_WIN_PAD));
+  if (q.burn_in) s.K = drqn_pop_burn_in(q.burn_in, p, s.T, q.q.K);
+  if (s.mem_state)
+    s.mem_state = (q.stored && q.stored[p] == 0)
+        ? nullptr : s.mem_state + (size_t)p * s.u.cap * drqn_windows(s.u.L, s.T) * SNAP;
   s.wdir += p * 5 * E;
   s.w_off += p * E;
   s.w_tot += 2 * (size_t)p;
-  if (s.qmax) s.qmax += p * rows;
-  if (s.stash) s.stash += p * rows * STASH;
-  if (s.qa) s.qa += p * rows;
-  if (s.y) s.y += p * rows;
-  if (s.d) s.d += p * rows;
-  if (s.ep_loss) s.ep_loss += p * E;
-  if (s.gpart) s.gpart += p * E * MZ_DRQN_PARAMS;
   return s;
 }
 
 // one wave per (learner, window); a learner that is not due exits at once
-__global__ __launch_bounds__(WAVE) void k_drqn_pop_win_fwd(MzDrqnPopWin q) {
-  const int p = blockIdx.x / q.q.E;
+__global__ __launch_bounds__(WAVE) void k_drqn_win_fwd(MzDrqnPopWin q) {
+  const int p = blockIdx.x / q.q.u.E, e = blockIdx.x % q.q.u.E;
   if (q.due && q.due[p] == 0) return;
-  drqn_win_fwd_body(drqn_win_row(q, p), blockIdx.x % q.q.E);
+  const MzDrqnWin s = drqn_win_row(q, p);
+  DrqnSpan w;
+  if (drqn_window(s, e, &w)) drqn_unroll_fwd(s.u, e, w, s.w_tot);
 }
 
-__global__ __launch_bounds__(WAVE) void k_drqn_pop_win_bwd(MzDrqnPopWin q) {
-  const int p = blockIdx.x / q.q.E;
+__global__ __launch_bounds__(WAVE) void k_drqn_win_bwd(MzDrqnPopWin q) {
+  const int p = blockIdx.x / q.q.u.E, e = blockIdx.x % q.q.u.E;
   if (q.due && q.due[p] == 0) return;
-  drqn_win_bwd_body(drqn_win_row(q, p), blockIdx.x % q.q.E);
+  const MzDrqnWin s = drqn_win_row(q, p);
+  DrqnSpan w;
+  if (!drqn_window(s, e, &w)) {
+    drqn_zero_partial(s.u.gpart + (size_t)e * MZ_DRQN_PARAMS);
+    return;
+  }
+  drqn_unroll_bwd(s.u, e, w);
 }
 
 }  // namespace
 
-hipError_t mz_launch_drqn_act(const MzDrqnAct& q, hipStream_t s) {
-  hipLaunchKernelGGL(k_drqn_act, dim3((q.B + IPB - 1) / IPB), dim3(ACT_T), 0, s, q);
+hipError_t mz_launch_drqn_act(const MzDrqnPopAct& q, hipStream_t s) {
+  const int bpl = (q.b + IPB - 1) / IPB;
+  hipLaunchKernelGGL(k_drqn_act, dim3((unsigned)q.P * bpl), dim3(ACT_T), 0, s, q);
   return hipGetLastError();
 }
 
-hipError_t mz_launch_drqn_store(const MzDrqnStore& q, hipStream_t s) {
-  const int blocks = q.B < 2048 ? q.B : 2048;
-  hipLaunchKernelGGL(k_drqn_store, dim3(blocks), dim3(256), 0, s, q);
+hipError_t mz_launch_drqn_store(const MzDrqnPopStore& q, int blocks, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_store, dim3(blocks, q.P), dim3(256), 0, s, q);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_drqn_ring, dim3(1), dim3(1), 0, s, q.fin_count, q.B, q.cap, q.ring);
+  hipLaunchKernelGGL(k_drqn_ring, dim3((q.P + WAVE - 1) / WAVE), dim3(WAVE), 0, s, q);
   return hipGetLastError();
 }
 
-hipError_t mz_launch_drqn_sample(const MzDrqnSample& q, hipStream_t s) {
-  hipLaunchKernelGGL(k_drqn_sample, dim3(1), dim3(WAVE), (size_t)q.E * sizeof(int32_t), s, q);
+hipError_t mz_launch_drqn_sample(const MzDrqnPopSample& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_sample, dim3(q.P), dim3(WAVE), (size_t)q.s.E * sizeof(int32_t), s, q);
   return hipGetLastError();
 }
 
-hipError_t mz_launch_drqn_seq_forward(const MzDrqnSeq& q, hipStream_t s) {
-  hipLaunchKernelGGL(k_drqn_seq_fwd, dim3(q.E), dim3(WAVE), 0, s, q);
+hipError_t mz_launch_drqn_seq_forward(const MzDrqnPopSeq& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_seq_fwd, dim3((unsigned)q.P * q.q.u.E), dim3(WAVE), 0, s, q);
   return hipGetLastError();
 }
 
-hipError_t mz_launch_drqn_seq_backward(const MzDrqnSeq& q, hipStream_t s) {
-  hipLaunchKernelGGL(k_drqn_seq_bwd, dim3(q.E), dim3(WAVE), 0, s, q);
+hipError_t mz_launch_drqn_seq_backward(const MzDrqnPopSeq& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_seq_bwd, dim3((unsigned)q.P * q.q.u.E), dim3(WAVE), 0, s, q);
   return hipGetLastError();
 }
 
 hipError_t mz_launch_drqn_reduce(const MzDrqnReduce& q, hipStream_t s) {
-  hipLaunchKernelGGL(k_drqn_reduce, dim3((MZ_DRQN_PARAMS + 255) / 256), dim3(256), 0, s, q);
+  hipLaunchKernelGGL(k_drqn_reduce, dim3((MZ_DRQN_PARAMS + 255) / 256, q.P), dim3(256), 0, s, q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_pop_sync(const float* src, float* dst, const int32_t* mask, int P,
+                                   hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_pop_sync, dim3((MZ_DRQN_PARAMS + 255) / 256, P), dim3(256), 0, s, src,
+                     dst, mask);
   return hipGetLastError();
 }
 
@@ -1119,90 +1039,23 @@ hipError_t mz_launch_drqn_snapshot(const MzDrqnSnap& q, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t mz_launch_drqn_snap_store(const MzDrqnSnapStore& q, hipStream_t s) {
-  const int blocks = q.B < 2048 ? q.B : 2048;
-  hipLaunchKernelGGL(k_drqn_snap_store, dim3(blocks), dim3(256), 0, s, q);
+hipError_t mz_launch_drqn_snap_store(const MzDrqnPopSnapStore& q, int blocks, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_snap_store, dim3(blocks, q.P), dim3(256), 0, s, q);
   return hipGetLastError();
 }
 
-hipError_t mz_launch_drqn_window_sample(const MzDrqnWinSample& q, hipStream_t s) {
-  hipLaunchKernelGGL(k_drqn_win_sample, dim3(1), dim3(WAVE), (size_t)q.s.E * sizeof(int32_t), s, q);
+hipError_t mz_launch_drqn_window_sample(const MzDrqnPopWinSample& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_win_sample, dim3(q.P), dim3(WAVE), (size_t)q.w.s.E * sizeof(int32_t),
+                     s, q);
   return hipGetLastError();
 }
 
-hipError_t mz_launch_drqn_window_forward(const MzDrqnWin& q, hipStream_t s) {
-  hipLaunchKernelGGL(k_drqn_win_fwd, dim3(q.E), dim3(WAVE), 0, s, q);
+hipError_t mz_launch_drqn_window_forward(const MzDrqnPopWin& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_win_fwd, dim3((unsigned)q.P * q.q.u.E), dim3(WAVE), 0, s, q);
   return hipGetLastError();
 }
 
-hipError_t mz_launch_drqn_window_backward(const MzDrqnWin& q, hipStream_t s) {
-  hipLaunchKernelGGL(k_drqn_win_bwd, dim3(q.E), dim3(WAVE), 0, s, q);
-  return hipGetLastError();
-}
-
-// ---- populations ----------------------------------------------------------------------------
-hipError_t mz_launch_drqn_pop_act(const MzDrqnPopAct& q, hipStream_t s) {
-  const int bpl = (q.b + IPB - 1) / IPB;
-  hipLaunchKernelGGL(k_drqn_pop_act, dim3((unsigned)q.P * bpl), dim3(ACT_T), 0, s, q);
-  return hipGetLastError();
-}
-
-hipError_t mz_launch_drqn_pop_store(const MzDrqnPopStore& q, hipStream_t s) {
-  const int blocks = q.b < 256 ? q.b : 256;
-  hipLaunchKernelGGL(k_drqn_pop_store, dim3(blocks, q.P), dim3(256), 0, s, q);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_drqn_pop_ring, dim3((q.P + WAVE - 1) / WAVE), dim3(WAVE), 0, s, q);
-  return hipGetLastError();
-}
-
-hipError_t mz_launch_drqn_pop_sample(const MzDrqnPopSample& q, hipStream_t s) {
-  hipLaunchKernelGGL(k_drqn_pop_sample, dim3(q.P), dim3(WAVE), (size_t)q.s.E * sizeof(int32_t), s,
-                     q);
-  return hipGetLastError();
-}
-
-hipError_t mz_launch_drqn_pop_seq_forward(const MzDrqnPopSeq& q, hipStream_t s) {
-  hipLaunchKernelGGL(k_drqn_pop_seq_fwd, dim3((unsigned)q.P * q.q.E), dim3(WAVE), 0, s, q);
-  return hipGetLastError();
-}
-
-hipError_t mz_launch_drqn_pop_seq_backward(const MzDrqnPopSeq& q, hipStream_t s) {
-  hipLaunchKernelGGL(k_drqn_pop_seq_bwd, dim3((unsigned)q.P * q.q.E), dim3(WAVE), 0, s, q);
-  return hipGetLastError();
-}
-
-hipError_t mz_launch_drqn_pop_reduce(const MzDrqnPopReduce& q, hipStream_t s) {
-  hipLaunchKernelGGL(k_drqn_pop_reduce, dim3((MZ_DRQN_PARAMS + 255) / 256, q.P), dim3(256), 0, s,
-                     q);
-  return hipGetLastError();
-}
-
-hipError_t mz_launch_drqn_pop_snap_store(const MzDrqnPopSnapStore& q, hipStream_t s) {
-  const int blocks = q.b < 256 ? q.b : 256;
-  hipLaunchKernelGGL(k_drqn_pop_snap_store, dim3(blocks, q.P), dim3(256), 0, s, q);
-  return hipGetLastError();
-}
-
-hipError_t mz_launch_drqn_pop_window_sample(const MzDrqnPopWinSample& q, hipStream_t s) {
-  hipLaunchKernelGGL(k_drqn_pop_win_sample, dim3(q.P), dim3(WAVE),
-                     (size_t)q.w.s.E * sizeof(int32_t), s, q);
-  return hipGetLastError();
-}
-
-hipError_t mz_launch_drqn_pop_window_forward(const MzDrqnPopWin& q, hipStream_t s) {
-  hipLaunchKernelGGL(k_drqn_pop_win_fwd, dim3((unsigned)q.P * q.q.E), dim3(WAVE), 0, s, q);
-  return hipGetLastError();
-}
-
-hipError_t mz_launch_drqn_pop_window_backward(const MzDrqnPopWin& q, hipStream_t s) {
-  hipLaunchKernelGGL(k_drqn_pop_win_bwd, dim3((unsigned)q.P * q.q.E), dim3(WAVE), 0, s, q);
-  return hipGetLastError();
-}
-
-hipError_t mz_launch_drqn_pop_sync(const float* src, float* dst, const int32_t* mask, int P,
-                                   hipStream_t s) {
-  hipLaunchKernelGGL(k_drqn_pop_sync, dim3((MZ_DRQN_PARAMS + 255) / 256, P), dim3(256), 0, s, src,
-                     dst, mask);
+hipError_t mz_launch_drqn_window_backward(const MzDrqnPopWin& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_win_bwd, dim3((unsigned)q.P * q.q.u.E), dim3(WAVE), 0, s, q);
   return hipGetLastError();
 }

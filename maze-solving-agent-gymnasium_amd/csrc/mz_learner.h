@@ -158,9 +158,11 @@ hipError_t mz_launch_rf_head(const MzRfHead& q, hipStream_t s);
 #define MZ_DRQN_PARAMS 5252     // 128 x 6 + 128 x 32 + 128 + 128 + 4 x 32 + 4
 #define MZ_DRQN_ROW_WORDS 8     // a replay row: x[6] f32, action i32, reward f32
 #define MZ_DRQN_STASH 192       // floats stashed per source step: i, f, g, o, c, h
-struct MzDrqnNet {              // torch's LSTMCell / Linear layouts, f32
-  const float *w_ih, *w_hh, *b_ih, *b_hh, *fc_w, *fc_b;
+template <class T> struct MzDrqnSix {  // torch's LSTMCell / Linear layouts, f32
+  T *w_ih, *w_hh, *b_ih, *b_hh, *fc_w, *fc_b;
 };
+using MzDrqnNet = MzDrqnSix<const float>;  // a net's parameters
+using MzDrqnGrads = MzDrqnSix<float>;      // its gradient segments
 struct MzDrqnAct {
   MzDrqnNet p;
   const float* obs6; int B, L;               // L == 0: evaluation (no record, every state advances)
@@ -183,25 +185,20 @@ struct MzDrqnSample {
   const int64_t* ring; const int32_t* mem_len;
   int32_t* d_slot; int32_t* d_len; int64_t* d_off; int64_t* d_tot;  // [E] x 3; rows, steps
 };
-struct MzDrqnSeq {
+// What the whole-episode and the window update share: the net, the replay memory and the row
+// buffers (E (L + 1) rows for whole episodes, E (min(T, L) + 2) for windows).
+struct MzDrqnUnroll {
   MzDrqnNet p;
   int target, E, L; int64_t cap; float gamma;
   const uint32_t* mem; const int32_t* mem_term;
-  const int32_t* d_slot; const int32_t* d_len; const int64_t* d_off; const int64_t* d_tot;
   float* qmax;                               // [rows] max_a Q'_t (target: out; source: in)
   float* stash; float* qa; float* y; float* d; double* ep_loss;  // source: out; backward: in
   float* gpart;                              // backward: [E][MZ_DRQN_PARAMS]
 };
-struct MzDrqnReduce {
-  int E; const float* gpart; const double* ep_loss; const int32_t* d_len; const int64_t* d_tot;
-  float* g[6]; float* loss;
+struct MzDrqnSeq {
+  MzDrqnUnroll u;
+  const int32_t* d_slot; const int32_t* d_len; const int64_t* d_off; const int64_t* d_tot;
 };
-hipError_t mz_launch_drqn_act(const MzDrqnAct& q, hipStream_t s);
-hipError_t mz_launch_drqn_store(const MzDrqnStore& q, hipStream_t s);
-hipError_t mz_launch_drqn_sample(const MzDrqnSample& q, hipStream_t s);
-hipError_t mz_launch_drqn_seq_forward(const MzDrqnSeq& q, hipStream_t s);
-hipError_t mz_launch_drqn_seq_backward(const MzDrqnSeq& q, hipStream_t s);
-hipError_t mz_launch_drqn_reduce(const MzDrqnReduce& q, hipStream_t s);
 
 // Replay windows of T steps with stored state and K burn-in steps. A state snapshot is 64 f32
 // (h[32], c[32]); an episode's snapshot j is the state before it acted at step j T (entry 0 is
@@ -230,52 +227,49 @@ struct MzDrqnWinSample {
   int32_t* wdir;
 };
 struct MzDrqnWin {
-  MzDrqnNet p;
-  int target, E, L, T, K; int64_t cap; float gamma;
-  const uint32_t* mem; const int32_t* mem_term;
+  MzDrqnUnroll u;
+  int T, K;
   const float* mem_state;                    // null: every window starts from zero state
   const int32_t* wdir; const int64_t* w_off; const int64_t* w_tot;  // rows, training steps
-  float* qmax;                               // [E (T + 2)] rows, as MzDrqnSeq's
-  float* stash; float* qa; float* y; float* d; double* ep_loss;
-  float* gpart;
 };
 hipError_t mz_launch_drqn_snapshot(const MzDrqnSnap& q, hipStream_t s);
-hipError_t mz_launch_drqn_snap_store(const MzDrqnSnapStore& q, hipStream_t s);
-hipError_t mz_launch_drqn_window_sample(const MzDrqnWinSample& q, hipStream_t s);
-hipError_t mz_launch_drqn_window_forward(const MzDrqnWin& q, hipStream_t s);
-hipError_t mz_launch_drqn_window_backward(const MzDrqnWin& q, hipStream_t s);
 
 // Populations: P independent learners over B = P b instances, learner p owning the block
 // [p b, (p + 1) b). Parameters, gradients and moments are flat [P][MZ_DRQN_PARAMS] f32, a row in
-// state_dict order. Each struct holds learner 0's single-learner view; the kernels move it to
-// learner p's rows. due: [P], 0 = the learner sits the update out (null: all due).
-inline MzDrqnNet mz_drqn_flat_net(const float* f) {  // the six tensors of one flat row
-  return MzDrqnNet{f, f + 768, f + 768 + 4096, f + 768 + 4096 + 128, f + 768 + 4096 + 256,
-                   f + 768 + 4096 + 256 + 128};
+// state_dict order. Every stage has one kernel and one launcher, which take the structs below: each
+// holds learner 0's single-learner view, and the kernel moves it to learner p's rows. A single
+// learner is P = 1, b = B with the per-learner arrays null: where one is null the kernel keeps the
+// by-value field of the embedded struct. due: [P], 0 = the learner sits the update out (null: all
+// due).
+template <class T> inline MzDrqnSix<T> mz_drqn_flat_net(T* f) {  // the six tensors of one flat row
+  return MzDrqnSix<T>{f, f + 768, f + 768 + 4096, f + 768 + 4096 + 128, f + 768 + 4096 + 256,
+                      f + 768 + 4096 + 256 + 128};
 }
 struct MzDrqnPopAct {
-  MzDrqnAct a;                               // a.B = P b (the pitch of h / c); a.eps, a.seed unused
+  MzDrqnAct a;                               // a.B = P b (the pitch of h / c)
   int P, b;
-  const float* eps; const uint64_t* seed;    // [P]
+  const float* eps; const uint64_t* seed;    // [P]; null: a.eps, a.seed
 };
 struct MzDrqnPopStore {
   MzDrqnStore s;                             // s.B = P b; mem [P][cap][L + 1][8], ring [P][2]
   int P, b;
 };
 struct MzDrqnPopSample {
-  MzDrqnSample s;                            // directory [P][E], d_tot [P][2]; s.seed, s.counter unused
+  MzDrqnSample s;                            // directory [P][E], d_tot [P][2]
   int P;
-  const uint64_t* seed; const uint64_t* counter; const int32_t* due;  // [P]
+  const uint64_t* seed; const uint64_t* counter;  // [P]; null: s.seed, s.counter
+  const int32_t* due;                        // [P]
 };
 struct MzDrqnPopSeq {
   MzDrqnSeq q;                               // row buffers [P][E (L + 1)], gpart [P][E][5252]
   int P;
-  const float* gamma; const int32_t* due;    // [P]
+  const float* gamma; const int32_t* due;    // [P]; gamma null: q.u.gamma
 };
-struct MzDrqnPopReduce {
+struct MzDrqnReduce {
   int P, E, ld;                              // ld: int32 words between two learners' d_len rows
   const float* gpart; const double* ep_loss; const int32_t* d_len; const int64_t* d_tot;
-  float* g; float* loss; const int32_t* due; // flat gradient [P][5252], [P], [P]
+  MzDrqnGrads g;                             // learner 0's gradient segments; learner p's are
+  float* loss; const int32_t* due;           // MZ_DRQN_PARAMS floats further on each; [P], [P]
 };
 // Replay windows in a population: T is shared (it fixes the layouts), the burn-in K_p and whether
 // the state memory is read are per learner. The window directory is one [5][E] block per learner.
@@ -286,25 +280,28 @@ struct MzDrqnPopSnapStore {
 struct MzDrqnPopWinSample {
   MzDrqnWinSample w;                         // wdir [P][5][E], d_off [P][E], d_tot [P][2]; w.K = K_max
   int P;
-  const uint64_t* seed; const uint64_t* counter; const int32_t* burn_in; const int32_t* due;  // [P]
+  const uint64_t* seed; const uint64_t* counter;  // [P]; null: w.s.seed, w.s.counter
+  const int32_t* burn_in; const int32_t* due;     // [P]; burn_in null: w.K, which the host checked
 };
 struct MzDrqnPopWin {
   MzDrqnWin q;                               // row buffers [P][E (min(T, L) + 2)]; q.K = K_max
   int P;
-  const float* gamma; const int32_t* burn_in; const int32_t* stored; const int32_t* due;  // [P]
+  const float* gamma; const int32_t* burn_in;  // [P]; null: q.u.gamma, q.K
+  const int32_t* stored; const int32_t* due;   // [P]; stored null: q.mem_state as given
 };
-hipError_t mz_launch_drqn_pop_act(const MzDrqnPopAct& q, hipStream_t s);
-hipError_t mz_launch_drqn_pop_store(const MzDrqnPopStore& q, hipStream_t s);
-hipError_t mz_launch_drqn_pop_sample(const MzDrqnPopSample& q, hipStream_t s);
-hipError_t mz_launch_drqn_pop_seq_forward(const MzDrqnPopSeq& q, hipStream_t s);
-hipError_t mz_launch_drqn_pop_seq_backward(const MzDrqnPopSeq& q, hipStream_t s);
-hipError_t mz_launch_drqn_pop_reduce(const MzDrqnPopReduce& q, hipStream_t s);
+// blocks: the store's workgroups per learner
+hipError_t mz_launch_drqn_act(const MzDrqnPopAct& q, hipStream_t s);
+hipError_t mz_launch_drqn_store(const MzDrqnPopStore& q, int blocks, hipStream_t s);
+hipError_t mz_launch_drqn_sample(const MzDrqnPopSample& q, hipStream_t s);
+hipError_t mz_launch_drqn_seq_forward(const MzDrqnPopSeq& q, hipStream_t s);
+hipError_t mz_launch_drqn_seq_backward(const MzDrqnPopSeq& q, hipStream_t s);
+hipError_t mz_launch_drqn_reduce(const MzDrqnReduce& q, hipStream_t s);
 hipError_t mz_launch_drqn_pop_sync(const float* src, float* dst, const int32_t* mask, int P,
                                    hipStream_t s);
-hipError_t mz_launch_drqn_pop_snap_store(const MzDrqnPopSnapStore& q, hipStream_t s);
-hipError_t mz_launch_drqn_pop_window_sample(const MzDrqnPopWinSample& q, hipStream_t s);
-hipError_t mz_launch_drqn_pop_window_forward(const MzDrqnPopWin& q, hipStream_t s);
-hipError_t mz_launch_drqn_pop_window_backward(const MzDrqnPopWin& q, hipStream_t s);
+hipError_t mz_launch_drqn_snap_store(const MzDrqnPopSnapStore& q, int blocks, hipStream_t s);
+hipError_t mz_launch_drqn_window_sample(const MzDrqnPopWinSample& q, hipStream_t s);
+hipError_t mz_launch_drqn_window_forward(const MzDrqnPopWin& q, hipStream_t s);
+hipError_t mz_launch_drqn_window_backward(const MzDrqnPopWin& q, hipStream_t s);
 // mz_optim.hip: k_adamw's element arithmetic over [P][n] rows with per-learner lr / step / due
 hipError_t mz_launch_adamw_pop(float* p, float* m, float* v, float* g, int P, int64_t n,
                                const float* lr, float* step, const int32_t* due, double b1,

@@ -1,6 +1,8 @@
 """Populations of recurrent DQN learners: P independent VectorRecurrentDQNTrainers advanced by the
-same launches (csrc/mz_drqn.hip k_drqn_pop_*, csrc/mz_optim.hip k_adamw_pop), so P seeds or P
-hyper-parameter settings of agents/lstm_dqn_agent.py cost about one run's launches.
+same launches (csrc/mz_drqn.hip's kernels, each of which serves P learners; csrc/mz_optim.hip
+k_adamw_pop), so P seeds or P hyper-parameter settings of agents/lstm_dqn_agent.py cost about one
+run's launches. The buffers, the scan and store of a vector step and the window settings are
+drqn_trainer.RecurrentDQNBase's, shared with that trainer.
 
 A population is P learners over B = P b instances; learner p owns the block [p b, (p + 1) b).
 Shared: the env, L = episode_bound, batch_size E, memory_size (capacity, in episodes),
@@ -9,9 +11,10 @@ starting_epsilon, final_epsilon, epsilon_decay, target_update_frequency, seed.
 
 Learner p is, by definition and bit for bit, what VectorRecurrentDQNTrainer (drqn_trainer.py: its
 six departures, its accumulation order, Philox streams and ring semantics) would be on its b
-instances with its hyper-parameters and seed: the population kernels run the single-learner
-device code on learner p's rows. The acting draw of instance i is keyed by (seed_p, counter,
-i - p b), the sample by (seed_p, updates_p); P = 1 is that trainer.
+instances with its hyper-parameters and seed: every stage has one kernel, which runs its device
+code on learner p's rows, and that trainer's entry points launch it with P = 1. The acting draw of
+instance i is keyed by (seed_p, counter, i - p b), the sample by (seed_p, updates_p); P = 1 is
+that trainer.
 
 Layout. Parameters, gradients and AdamW moments are flat [P][5252] f32, a row in state_dict order;
 h, c stay [32][B]; the replay memory is [P][capacity][L + 1][8] words with mem_len / mem_term
@@ -53,8 +56,9 @@ import torch
 from .. import _native as N
 from ..agents.lstm_dqn_agent import DQN, ETA_MIN, HIDDEN, T_MAX, epsilon_at
 from ..agents.rf_agent import cosine_lr
-from .drqn_trainer import EVAL_KEY, PARAMS, ROW, STASH, U64, _Evaluator, check_window
-from .episodic import EpisodicTrainer, episode_bound
+from .drqn_trainer import (EVAL_KEY, PARAMS, ROW, STASH, U64, RecurrentDQNBase, _Evaluator,
+                           check_window)
+from .episodic import episode_bound
 
 FORMAT = "mazerl.VectorRecurrentDQNPopulation/1"
 KEYS = ("lstm_cell.weight_ih", "lstm_cell.weight_hh", "lstm_cell.bias_ih", "lstm_cell.bias_hh",
@@ -115,11 +119,11 @@ class _LearnerView:
         self._ps = (C.c_void_p * 6)(*ptrs)
 
 
-class VectorRecurrentDQNPopulation(EpisodicTrainer):
+class VectorRecurrentDQNPopulation(RecurrentDQNBase):
     _FORMAT = FORMAT
     _SHAPE = ("L", "capacity", "P")
-    _REC = ("rec_x", "rec_a", "rec_r")
     _COUNTERS = ("counter", "launches")
+    _KIND = "population"
 
     def __init__(self, env, device, learners=1, lr=1e-3, starting_epsilon=0.9, final_epsilon=0.05,
                  epsilon_decay=1000.0, discount_factor=0.99, batch_size=32, memory_size=20000,
@@ -196,40 +200,10 @@ class VectorRecurrentDQNPopulation(EpisodicTrainer):
         self.cnt_dev = self.upd[:2 * P].view(i64)
         self.due_dev, self.sync_dev = self.upd[2 * P:3 * P], self.upd[3 * P:4 * P]
         self.lr_dev = self.upd[4 * P:].view(f32)
-        self.h = torch.zeros(HIDDEN, B, dtype=f32, **kw)
-        self.c = torch.zeros(HIDDEN, B, dtype=f32, **kw)
-        self.rec_x = torch.zeros(B, L + 1, 6, dtype=f32, **kw)
-        self.rec_a = torch.zeros(B, L, dtype=i32, **kw)
-        self.rec_r = torch.zeros(B, L, dtype=torch.float64, **kw)
-        self.r64 = torch.zeros(B, dtype=torch.float64, **kw)
-        self.pool = torch.zeros(2, dtype=i64, **kw)  # mz_ppo_scan's row counters (unused here)
-        self.mem = torch.zeros(P, self.capacity, L + 1, ROW, dtype=i32, **kw)
-        self.mem_len = torch.zeros(P, self.capacity, dtype=i32, **kw)
-        self.mem_term = torch.zeros(P, self.capacity, dtype=i32, **kw)
-        self.ring = torch.zeros(P, 2, dtype=i64, **kw)  # head, count
-        # an update's directory and row buffers: whole episodes, or windows of m <= T steps (+ the
-        # entry-state row and the guard row) whatever the burn-in is
-        rows = E * (L + 1) if self.window is None else E * (min(self.window, L) + 2)
+        self._alloc(P, any(self.stored))
         if self.window is not None:
-            self.wdir = torch.zeros(P, 5, E, dtype=i32, **kw)  # per learner: slot, n, b, k, m
-            self.snaps = (L - 1) // self.window + 1
             self.burn_in_dev = torch.tensor(self.burn_in, dtype=i32, **kw)
             self.stored_dev = torch.tensor([int(s) for s in self.stored], dtype=i32, **kw)
-        if any(self.stored):
-            self.snap_rec = torch.zeros(B, self.snaps, 2 * HIDDEN, dtype=f32, **kw)
-            self.mem_state = torch.zeros(P, self.capacity, self.snaps, 2 * HIDDEN, dtype=f32, **kw)
-        self.d_slot = torch.zeros(P, E, dtype=i32, **kw)
-        self.d_len = torch.zeros(P, E, dtype=i32, **kw)
-        self.d_off = torch.zeros(P, E, dtype=i64, **kw)
-        self.d_tot = torch.zeros(P, 2, dtype=i64, **kw)
-        self.qmax = torch.zeros(P, rows, dtype=f32, **kw)
-        self.stash = torch.zeros(P, rows, STASH, dtype=f32, **kw)
-        self.qa = torch.zeros(P, rows, dtype=f32, **kw)
-        self.y = torch.zeros(P, rows, dtype=f32, **kw)
-        self.d = torch.zeros(P, rows, dtype=f32, **kw)
-        self.ep_loss = torch.zeros(P, E, dtype=torch.float64, **kw)
-        self.gpart = torch.zeros(P, E, PARAMS, dtype=f32, **kw)
-        self.loss = torch.zeros(P, dtype=f32, **kw)
         self.last_lr = [None] * P
         self.last_due = [False] * P  # the learners the last vector step updated
 
@@ -290,23 +264,16 @@ class VectorRecurrentDQNPopulation(EpisodicTrainer):
         acts = torch.zeros(P * n, dtype=torch.int32, **kw)
         eps = torch.zeros(P, dtype=torch.float32, **kw)
         seeds = torch.tensor([_signed(s ^ EVAL_KEY) for s in self.seed], dtype=torch.int64, **kw)
-        finished = torch.zeros(P * n, dtype=torch.bool, **kw)
-        won = torch.zeros(P * n, dtype=torch.bool, **kw)
-        limit = episode_bound(dim, toroidal) + 1
-        k = 0
-        while k < limit:
+
+        def act(k):
             N.check(self.lib.mz_drqn_pop_act(
                 self.src.data_ptr(), HIDDEN, P, n, env.obs6.data_ptr(), 0, eps.data_ptr(),
                 self.explore_actions, seeds.data_ptr(), k, t.data_ptr(), h.data_ptr(),
                 c.data_ptr(), None, None, acts.data_ptr(), None, self._stream()))
             t.fill_(1)
-            env.step(torch.where(finished, torch.full_like(acts, -1), acts))
-            term = env.terminated.bool()
-            won |= term & ~finished
-            finished |= term | env.truncated.bool()
-            k += 1
-            if k % 32 == 0 and bool(finished.all()):
-                break
+            return acts
+
+        won, _ = self.greedy_rollout(env, act, episode_bound(dim, toroidal) + 1)
         rates = won.view(P, n).float().mean(dim=1).tolist()
         env.close()
         return rates
@@ -330,22 +297,13 @@ class VectorRecurrentDQNPopulation(EpisodicTrainer):
             self._stream()))
         self.counter += 1
 
-    def _scan_store(self):
-        env, st = self.env, self._stream()
-        self.r64.copy_(env.reward)
-        self._scan(self.r64, env.terminated, env.truncated, self.rec_r,
-                   self.pool[0:].data_ptr(), self.pool[1:].data_ptr())
-        if any(self.stored):  # (reads the rings' heads, which mz_drqn_pop_store advances)
-            N.check(self.lib.mz_drqn_pop_snap_store(
-                HIDDEN, self.P, self.b, self.L, self.window, self.fin_id.data_ptr(),
-                self.fin_len.data_ptr(), self.fin_count.data_ptr(), self.snap_rec.data_ptr(),
-                self.capacity, self.mem_state.data_ptr(), self.ring.data_ptr(), st))
-        N.check(self.lib.mz_drqn_pop_store(
-            env.obs6.data_ptr(), env.terminated.data_ptr(), self.P, self.b, self.L,
-            self.fin_id.data_ptr(), self.fin_len.data_ptr(), self.fin_count.data_ptr(),
-            self.rec_x.data_ptr(), self.rec_a.data_ptr(), self.rec_r.data_ptr(), self.capacity,
-            self.mem.data_ptr(), self.mem_len.data_ptr(), self.mem_term.data_ptr(),
-            self.ring.data_ptr(), st))
+    def _snap_store_call(self, *tail):
+        N.check(self.lib.mz_drqn_pop_snap_store(HIDDEN, self.P, self.b, *tail))
+
+    def _store_call(self, *tail):
+        env = self.env
+        N.check(self.lib.mz_drqn_pop_store(env.obs6.data_ptr(), env.terminated.data_ptr(), self.P,
+                                           self.b, *tail))
 
     def _upload(self, due, sync, lr):
         P = self.P
@@ -426,9 +384,7 @@ class VectorRecurrentDQNPopulation(EpisodicTrainer):
             self.loss.data_ptr(), st))
 
     def _update(self, due):
-        if self.launches % 256 == 0 and int(self.stats[3]):  # (one look every 256 updates)
-            raise RuntimeError(f"recurrent DQN episode records overflowed L = {self.L} steps "
-                               "(mz_ppo_scan stats[3])")
+        self._overflow_look(self.launches)
         self.launches += 1
         lr, sync = [0.0] * self.P, [0] * self.P
         for p in range(self.P):
@@ -485,18 +441,8 @@ class VectorRecurrentDQNPopulation(EpisodicTrainer):
             sd["mem_state"] = [self.mem_state[p, :n].clone() for p, n in enumerate(counts)]
         return sd
 
-    def _window_settings(self):
-        """T and the two per-learner lists (None without windows)."""
-        if self.window is None:
-            return None
-        return {"window": self.window, "burn_in": list(self.burn_in),
-                "initial_state": list(self.initial_state)}
-
     def load_state_dict(self, sd):
-        # (a checkpoint from before the window option has no "window" key: window=None)
-        if sd.get("window") != self._window_settings():
-            raise ValueError(f"the checkpoint's replay windows {sd.get('window')} differ from this "
-                             f"population's {self._window_settings()}")
+        self._check_window_settings(sd)
         self._load_common(sd)
         if any(self.stored):
             self.snap_rec.copy_(sd["snap_rec"])

@@ -64,8 +64,11 @@ option window=T, burn_in=K, initial_state="stored" | "zero"; window=None is the 
      before the episode does bootstraps from x_{s+m}); loss = sum (Q_t[a_t] - y_t)^2 / sum m.
 K must be a multiple of T. Overlapping windows (a stride other than T) are out of scope.
 VectorRecurrentDQNPopulation takes the same three arguments (T shared, K and the initial state per
-learner); its learner p is this trainer with (T, K_p, S_p), departures 7-9 included.
+learner); its learner p is this trainer with (T, K_p, S_p), departures 7-9 included. On the device
+the two are one: every mz_drqn_* entry point here launches the population's kernel with P = 1.
+RecurrentDQNBase holds what the two classes share on the host.
 """
+import copy
 import ctypes as C
 
 import torch
@@ -101,10 +104,111 @@ def check_window(window, burn_in, initial_state):
                          f"(got {window!r}, {burn_in!r}, {initial_state!r})")
 
 
-class VectorRecurrentDQNTrainer(EpisodicTrainer):
+class RecurrentDQNBase(EpisodicTrainer):
+    """What the trainer and the population (drqn_population.py) share: the buffers, the scan and
+    store of a vector step, the overflow look, the window settings and the greedy rollout. The
+    population's ring, directory and row buffers carry a leading P dimension and its store calls
+    (_snap_store_call, _store_call) take (P, b) where the trainer's take B; nothing else differs."""
+    _REC = ("rec_x", "rec_a", "rec_r")
+    _KIND = "trainer"  # (load_state_dict's error text)
+
+    def _alloc(self, P=None, state=False):
+        """The per-instance buffers, the replay ring, an update's directory and row buffers
+        (population: a leading P dimension) and, with `state`, the snapshots' two buffers."""
+        B, E, L = self.env.num_envs, self.batch_size, self.L
+        lead = () if P is None else (P,)
+        kw = dict(device=self.device)
+        i32, i64, f32 = torch.int32, torch.int64, torch.float32
+        self.h = torch.zeros(HIDDEN, B, dtype=f32, **kw)
+        self.c = torch.zeros(HIDDEN, B, dtype=f32, **kw)
+        self.rec_x = torch.zeros(B, L + 1, 6, dtype=f32, **kw)
+        self.rec_a = torch.zeros(B, L, dtype=i32, **kw)
+        self.rec_r = torch.zeros(B, L, dtype=torch.float64, **kw)
+        self.r64 = torch.zeros(B, dtype=torch.float64, **kw)
+        self.pool = torch.zeros(2, dtype=i64, **kw)  # mz_ppo_scan's row counters (unused here)
+        # the replay memory: fixed-stride slots of L + 1 rows of 32 B
+        self.mem = torch.zeros(*lead, self.capacity, L + 1, ROW, dtype=i32, **kw)
+        self.mem_len = torch.zeros(*lead, self.capacity, dtype=i32, **kw)
+        self.mem_term = torch.zeros(*lead, self.capacity, dtype=i32, **kw)
+        self.ring = torch.zeros(*lead, 2, dtype=i64, **kw)  # head, count
+        # an update's directory and row buffers: whole episodes, or windows of m <= T steps
+        # (+ the entry-state row and the guard row), which the burn-in does not lengthen
+        rows = E * (L + 1) if self.window is None else E * (min(self.window, L) + 2)
+        if self.window is not None:
+            self.wdir = torch.zeros(*lead, 5, E, dtype=i32, **kw)  # slot, n, b, k, m
+            self.snaps = (L - 1) // self.window + 1
+        self._state = bool(state)
+        if self._state:
+            self.snap_rec = torch.zeros(B, self.snaps, 2 * HIDDEN, dtype=f32, **kw)
+            self.mem_state = torch.zeros(*lead, self.capacity, self.snaps, 2 * HIDDEN, dtype=f32,
+                                         **kw)
+        self.d_slot = torch.zeros(*lead, E, dtype=i32, **kw)
+        self.d_len = torch.zeros(*lead, E, dtype=i32, **kw)
+        self.d_off = torch.zeros(*lead, E, dtype=i64, **kw)
+        self.d_tot = torch.zeros(*lead, 2, dtype=i64, **kw)
+        self.qmax = torch.zeros(*lead, rows, dtype=f32, **kw)
+        self.stash = torch.zeros(*lead, rows, STASH, dtype=f32, **kw)
+        self.qa = torch.zeros(*lead, rows, dtype=f32, **kw)
+        self.y = torch.zeros(*lead, rows, dtype=f32, **kw)
+        self.d = torch.zeros(*lead, rows, dtype=f32, **kw)
+        self.ep_loss = torch.zeros(*lead, E, dtype=torch.float64, **kw)
+        self.gpart = torch.zeros(*lead, E, PARAMS, dtype=f32, **kw)
+        self.loss = torch.zeros(*(lead or (1,)), dtype=f32, **kw)
+
+    def _scan_store(self):
+        env, L, st = self.env, self.L, self._stream()
+        self.r64.copy_(env.reward)
+        self._scan(self.r64, env.terminated, env.truncated, self.rec_r,
+                   self.pool[0:].data_ptr(), self.pool[1:].data_ptr())
+        fin = (self.fin_id.data_ptr(), self.fin_len.data_ptr(), self.fin_count.data_ptr())
+        if self._state:  # (reads the ring's head, which the store advances)
+            self._snap_store_call(L, self.window, *fin, self.snap_rec.data_ptr(), self.capacity,
+                                  self.mem_state.data_ptr(), self.ring.data_ptr(), st)
+        self._store_call(L, *fin, self.rec_x.data_ptr(), self.rec_a.data_ptr(),
+                         self.rec_r.data_ptr(), self.capacity, self.mem.data_ptr(),
+                         self.mem_len.data_ptr(), self.mem_term.data_ptr(), self.ring.data_ptr(), st)
+
+    def _overflow_look(self, clock):
+        if clock % 256 == 0 and int(self.stats[3]):  # (one look every 256 updates)
+            raise RuntimeError(f"recurrent DQN episode records overflowed L = {self.L} steps "
+                               "(mz_ppo_scan stats[3])")
+
+    def _window_settings(self):
+        """T with the burn-in and the initial state (a population's: the per-learner lists); None
+        without windows."""
+        if self.window is None:
+            return None
+        return {"window": self.window, "burn_in": copy.copy(self.burn_in),
+                "initial_state": copy.copy(self.initial_state)}
+
+    def _check_window_settings(self, sd):
+        # (a checkpoint from before the window option has no "window" key: window=None)
+        if sd.get("window") != self._window_settings():
+            raise ValueError(f"the checkpoint's replay windows {sd.get('window')} differ from this "
+                             f"{self._KIND}'s {self._window_settings()}")
+
+    @staticmethod
+    def greedy_rollout(env, act, limit):
+        """One greedy episode per row of `env`, at most `limit` vector steps: act(k) gives step
+        k's int32 actions. Returns (the rows that won, the vector steps made)."""
+        finished = torch.zeros(env.num_envs, dtype=torch.bool, device=env.device)
+        won = torch.zeros(env.num_envs, dtype=torch.bool, device=env.device)
+        k = 0
+        while k < limit:
+            acts = act(k)
+            env.step(torch.where(finished, torch.full_like(acts, -1), acts))
+            term = env.terminated.bool()
+            won |= term & ~finished
+            finished |= term | env.truncated.bool()
+            k += 1
+            if k % 32 == 0 and bool(finished.all()):
+                break
+        return won, k
+
+
+class VectorRecurrentDQNTrainer(RecurrentDQNBase):
     _FORMAT = FORMAT
     _SHAPE = ("L", "capacity")
-    _REC = ("rec_x", "rec_a", "rec_r")
     _COUNTERS = ("seed", "steps_done", "counter", "updates", "filled")
 
     def __init__(self, env, device, lr=1e-3, starting_epsilon=0.9, final_epsilon=0.05,
@@ -143,43 +247,8 @@ class VectorRecurrentDQNTrainer(EpisodicTrainer):
         self.counter = 0      # vector steps (the exploration draws' counter)
         self.updates = 0
         self.filled = 0       # the host's lower bound of the ring's count
-        B, E, L = env.num_envs, self.batch_size, self.L
-        kw = dict(device=self.device)
-        i32, i64, f32 = torch.int32, torch.int64, torch.float32
-        self.h = torch.zeros(HIDDEN, B, dtype=f32, **kw)
-        self.c = torch.zeros(HIDDEN, B, dtype=f32, **kw)
-        self.rec_x = torch.zeros(B, L + 1, 6, dtype=f32, **kw)
-        self.rec_a = torch.zeros(B, L, dtype=i32, **kw)
-        self.rec_r = torch.zeros(B, L, dtype=torch.float64, **kw)
-        self.r64 = torch.zeros(B, dtype=torch.float64, **kw)
-        self.pool = torch.zeros(2, dtype=i64, **kw)  # mz_ppo_scan's row counters (unused here)
-        # the replay memory: fixed-stride slots of L + 1 rows of 32 B
-        self.mem = torch.zeros(self.capacity, L + 1, ROW, dtype=i32, **kw)
-        self.mem_len = torch.zeros(self.capacity, dtype=i32, **kw)
-        self.mem_term = torch.zeros(self.capacity, dtype=i32, **kw)
-        self.ring = torch.zeros(2, dtype=i64, **kw)  # head, count
-        # an update's directory and row buffers: whole episodes, or windows of m <= T steps
-        # (+ the entry-state row and the guard row), which the burn-in does not lengthen
-        rows = E * (L + 1) if self.window is None else E * (min(self.window, L) + 2)
-        if self.window is not None:
-            self.wdir = torch.zeros(5, E, dtype=i32, **kw)  # slot, n, b, k, m
-            self.snaps = (L - 1) // self.window + 1
         self.stored = self.window is not None and initial_state == "stored"
-        if self.stored:
-            self.snap_rec = torch.zeros(B, self.snaps, 2 * HIDDEN, dtype=f32, **kw)
-            self.mem_state = torch.zeros(self.capacity, self.snaps, 2 * HIDDEN, dtype=f32, **kw)
-        self.d_slot = torch.zeros(E, dtype=i32, **kw)
-        self.d_len = torch.zeros(E, dtype=i32, **kw)
-        self.d_off = torch.zeros(E, dtype=i64, **kw)
-        self.d_tot = torch.zeros(2, dtype=i64, **kw)
-        self.qmax = torch.zeros(rows, dtype=f32, **kw)
-        self.stash = torch.zeros(rows, STASH, dtype=f32, **kw)
-        self.qa = torch.zeros(rows, dtype=f32, **kw)
-        self.y = torch.zeros(rows, dtype=f32, **kw)
-        self.d = torch.zeros(rows, dtype=f32, **kw)
-        self.ep_loss = torch.zeros(E, dtype=torch.float64, **kw)
-        self.gpart = torch.zeros(E, PARAMS, dtype=f32, **kw)
-        self.loss = torch.zeros(1, dtype=f32, **kw)
+        self._alloc(None, self.stored)
         self.last_lr = None
 
     def epsilon(self):
@@ -204,21 +273,13 @@ class VectorRecurrentDQNTrainer(EpisodicTrainer):
             self.act_out.data_ptr(), None, self._stream()))
         self.counter += 1
 
-    def _scan_store(self):
-        env, B, L, st = self.env, self.env.num_envs, self.L, self._stream()
-        self.r64.copy_(env.reward)
-        self._scan(self.r64, env.terminated, env.truncated, self.rec_r,
-                   self.pool[0:].data_ptr(), self.pool[1:].data_ptr())
-        if self.stored:  # (reads the ring's head, which mz_drqn_store advances)
-            N.check(self.lib.mz_drqn_snap_store(
-                HIDDEN, B, L, self.window, self.fin_id.data_ptr(), self.fin_len.data_ptr(),
-                self.fin_count.data_ptr(), self.snap_rec.data_ptr(), self.capacity,
-                self.mem_state.data_ptr(), self.ring.data_ptr(), st))
-        N.check(self.lib.mz_drqn_store(
-            env.obs6.data_ptr(), env.terminated.data_ptr(), B, L, self.fin_id.data_ptr(),
-            self.fin_len.data_ptr(), self.fin_count.data_ptr(), self.rec_x.data_ptr(),
-            self.rec_a.data_ptr(), self.rec_r.data_ptr(), self.capacity, self.mem.data_ptr(),
-            self.mem_len.data_ptr(), self.mem_term.data_ptr(), self.ring.data_ptr(), st))
+    def _snap_store_call(self, *tail):
+        N.check(self.lib.mz_drqn_snap_store(HIDDEN, self.env.num_envs, *tail))
+
+    def _store_call(self, *tail):
+        env = self.env
+        N.check(self.lib.mz_drqn_store(env.obs6.data_ptr(), env.terminated.data_ptr(),
+                                       env.num_envs, *tail))
 
     def sample(self):
         """E distinct slots and the directory (d_slot, d_len, d_off, d_tot), keyed by the update
@@ -279,9 +340,7 @@ class VectorRecurrentDQNTrainer(EpisodicTrainer):
             self.gpart.data_ptr(), self._pg, self.loss.data_ptr(), st))
 
     def _update(self):
-        if self.updates % 256 == 0 and int(self.stats[3]):  # (one look every 256 updates)
-            raise RuntimeError(f"recurrent DQN episode records overflowed L = {self.L} steps "
-                               "(mz_ppo_scan stats[3])")
+        self._overflow_look(self.updates)
         self.last_lr = cosine_lr(self.updates, self.lr, T_MAX, ETA_MIN)
         self.sample()
         self.update(self.last_lr)
@@ -344,17 +403,8 @@ class VectorRecurrentDQNTrainer(EpisodicTrainer):
                      "step": o._step_buf.clone(), "lr": o.param_groups[0]["lr"].clone()}
         return sd
 
-    def _window_settings(self):
-        if self.window is None:
-            return None
-        return {"window": self.window, "burn_in": self.burn_in,
-                "initial_state": self.initial_state}
-
     def load_state_dict(self, sd):
-        # (a checkpoint from before the window option has no "window" key: window=None)
-        if sd.get("window") != self._window_settings():
-            raise ValueError(f"the checkpoint's replay windows {sd.get('window')} differ from this "
-                             f"trainer's {self._window_settings()}")
+        self._check_window_settings(sd)
         self._load_common(sd)
         with torch.no_grad():
             self.source_net.load_state_dict(sd["source"])
@@ -382,19 +432,9 @@ def evaluate_plain(learner, num_mazes, dim, algorithm="r-prim", seed=0x7E57, tor
     from ..vector_env import VectorMazeEnv
     env = VectorMazeEnv(num_mazes, dim, toroidal=toroidal, enrich=False, device=device,
                         algorithm=algorithm, seed=seed, pos=False, done_list=False)
-    finished = torch.zeros(num_mazes, dtype=torch.bool, device=env.device)
-    won = torch.zeros(num_mazes, dtype=torch.bool, device=env.device)
-    limit = episode_bound(dim, toroidal) + 1
-    k = 0
-    while k < limit:
-        acts = learner.greedy(env.obs6, None, None).to(torch.int32)
-        env.step(torch.where(finished, torch.full_like(acts, -1), acts))
-        term = env.terminated.bool()
-        won |= term & ~finished
-        finished |= term | env.truncated.bool()
-        k += 1
-        if k % 32 == 0 and bool(finished.all()):
-            break
+    won, k = RecurrentDQNBase.greedy_rollout(
+        env, lambda k: learner.greedy(env.obs6, None, None).to(torch.int32),
+        episode_bound(dim, toroidal) + 1)
     rate = float(won.float().mean())
     env.close()
     return rate, k

@@ -342,10 +342,11 @@ def test_store_fills_the_ring_like_a_deque_and_sample_draws_distinct_slots(lib):
 
 # ---- sequence forward / backward ------------------------------------------------------------
 class _Seq:
-    """A hand-built memory and directory of E episodes (L = 8) and the three launches."""
+    """A hand-built memory and directory of E episodes (L = 8 unless given) and the three
+    launches."""
 
-    def __init__(self, lib, E, seed, lens=None):
-        self.lib, self.E, self.L = lib, E, 8
+    def __init__(self, lib, E, seed, lens=None, L=8):
+        self.lib, self.E, self.L = lib, E, L
         L = self.L
         rng = np.random.default_rng(seed)
         self.cap = E + 2
@@ -472,6 +473,29 @@ def test_seq_pad_and_guard_rows_keep_their_sentinels(seq):
     assert np.isnan(q[s.rows:]).all() and not np.isnan(q[:s.rows]).any()
     assert torch.isnan(o["gpart"][s.E]).all() and not torch.isnan(o["gpart"][:s.E]).any()
     assert torch.isnan(o["ep_loss"][s.E]) and torch.isnan(o["loss"][1])
+
+
+def test_seq_backward_writes_only_inside_six_separate_gradient_segments(lib):
+    """The reduce after the backward writes through six segment pointers. E = 3, L = 5: six
+    separately allocated tensors, each with NaN sentinels before and after its segment; the
+    sentinels are still NaN afterwards and the segments hold the bits of the plain run."""
+    from mazerl import _native as N
+    G = 4
+    s = _Seq(lib, 3, 91, lens=[1, 5, 3], L=5)
+    o = s.run()
+    sizes = [int(np.prod(sh)) for sh in SHAPES]
+    bufs = [torch.full((G + n + G,), float("nan"), device=DEV) for n in sizes]
+    pg = (C.c_void_p * 6)(*[b.data_ptr() + 4 * G for b in bufs])
+    loss = torch.full((1,), float("nan"), device=DEV)
+    N.check(s.lib.mz_drqn_seq_backward(
+        s.pps, H, s.E, s.L, s.cap, s.mem.data_ptr(), s.d_slot.data_ptr(), s.d_len.data_ptr(),
+        s.d_off.data_ptr(), s.d_tot.data_ptr(), o["stash"].data_ptr(), o["d"].data_ptr(),
+        o["ep_loss"].data_ptr(), o["gpart"].data_ptr(), pg, loss.data_ptr(), _stream()))
+    torch.cuda.synchronize()
+    for b, g, n in zip(bufs, o["grads"], sizes):
+        assert torch.isnan(b[:G]).all() and torch.isnan(b[G + n:]).all()
+        assert not torch.isnan(b[G:G + n]).any() and torch.equal(b[G:G + n], g[:n])
+    assert float(loss) == float(o["loss"][0])
 
 
 def test_seq_two_runs_are_bit_identical(seq):

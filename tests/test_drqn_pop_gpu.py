@@ -1,5 +1,5 @@
-"""The population kernels of the recurrent DQN (csrc/mz_drqn.hip k_drqn_pop_*, csrc/mz_optim.hip
-k_adamw_pop) through the C ABI.
+"""The recurrent DQN's kernels at P > 1 learners (csrc/mz_drqn.hip through the mz_drqn_pop_* entry
+points, csrc/mz_optim.hip k_adamw_pop) through the C ABI.
 
 The single-learner entry points are pinned to the float64 model by tests/test_drqn_gpu.py, so they
 are the yardstick here: learner p of a population call must give the bits the single-learner call

@@ -1,6 +1,6 @@
-"""Replay windows in recurrent DQN populations (csrc/mz_drqn.hip k_drqn_pop_snap_store,
-k_drqn_pop_win_sample, k_drqn_pop_win_fwd, k_drqn_pop_win_bwd, k_drqn_pop_reduce's strided
-lengths) through the C ABI.
+"""Replay windows in recurrent DQN populations (csrc/mz_drqn.hip k_drqn_snap_store,
+k_drqn_win_sample, k_drqn_win_fwd, k_drqn_win_bwd at P > 1, k_drqn_reduce's strided lengths)
+through the C ABI.
 
 The single-learner window entry points are pinned to the float64 model by
 tests/test_drqn_window_gpu.py, so they are the yardstick: learner p of a population call must give
