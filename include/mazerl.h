@@ -1082,7 +1082,7 @@ int mz_qtab_update(const float* obs6_dev, int32_t n, int32_t max_dim, const int3
                    int64_t* episodes_dev, int64_t* wins_dev, double* td_dev, int32_t episode_end,
                    void* stream);
 
-/* ---- The same learner on hashed tables (mz_qhash.hip) ------------------------------------------
+/* ---- The same learner on hashed tables (mz_qtab.hip) ------------------------------------------
  * QAgent's table is a defaultdict(lambda: np.zeros(4)) (agents/q_agent.py:8-79) that holds only
  * the states met; a dense table holds all 5 P^4 (452 MB at 41x41, 6.9 GB at 81x81). Here each of
  * the ntables tables is an open-addressing hash table of `capacity` slots (a power of two,
@@ -1142,7 +1142,7 @@ int mz_qtab_hash_lookup(const int32_t* keys_dev, const double* vals_dev, int64_t
                         const int64_t* query_keys_dev, int32_t m, double* rows_out_dev,
                         int32_t* slots_out_dev, void* stream);
 
-/* ---- Double Q-learning populations (mz_dqtab.hip) ----------------------------------------------
+/* ---- Double Q-learning populations (mz_qtab.hip) ----------------------------------------------
  * Replaces, per instance, DQAgent (agents/dq_agent.py:5-73: two dicts of 4-entry float64 rows,
  * q_a_values and q_b_values, keyed by str(obs)) under the same OffPolicyTrainer.train. Everything
  * above holds (the index, the per-table arrays, idle instances, the hash and its probe) except

@@ -2035,7 +2035,7 @@ int mz_qact(const uint32_t* bits_dev, const float* obs6_dev, const int32_t* rows
 }
 
 
-// ---- vectorised tabular Q-learning (mz_qtab.hip) ----------------------------------------------
+// ---- vectorised tabular learners (mz_qtab.hip): Q and double Q, dense and hashed tables -------
 int mz_qtab_states(int32_t max_dim, int64_t* rows) {
   if (!rows) return fail(MZ_EINVAL, "null argument");
   if (max_dim < 5 || max_dim > MZ_MAX_DIM)
@@ -2060,53 +2060,7 @@ int qtab_check(const void* obs6, int32_t n, int32_t max_dim, const void* table_o
   if (reinterpret_cast<uintptr_t>(obs6) & 7) return fail(MZ_EALIGN, "obs6 must be 8-byte aligned");
   return MZ_OK;
 }
-}  // namespace
 
-int mz_qtab_act(const float* obs6_dev, int32_t n, int32_t max_dim, const int32_t* table_of_dev,
-                int32_t ntables, const uint8_t* active_dev, const double* q_dev,
-                int64_t* steps_done_dev, const double* eps_init_dev, const double* eps_final_dev,
-                const double* eps_decay_dev, uint64_t seed, uint64_t counter, int32_t* actions_dev,
-                int64_t* sidx_dev, void* stream) {
-  if (int rc = qtab_check(obs6_dev, n, max_dim, table_of_dev, ntables, q_dev)) return rc;
-  if (!steps_done_dev || !eps_init_dev || !eps_final_dev || !eps_decay_dev || !actions_dev ||
-      !sidx_dev)
-    return fail(MZ_EINVAL, "null argument");
-  int64_t rows = 0;
-  mz_qtab_states(max_dim, &rows);
-  StreamGuard g(stream);
-  MzQtabAct a{obs6_dev, n, max_dim, table_of_dev, ntables, active_dev, q_dev, rows,
-              reinterpret_cast<const long long*>(steps_done_dev), eps_init_dev, eps_final_dev,
-              eps_decay_dev, seed, counter, actions_dev, sidx_dev};
-  MZ_HIP(mz_launch_qtab_act(a, reinterpret_cast<long long*>(steps_done_dev),
-                            static_cast<hipStream_t>(stream)));
-  return MZ_OK;
-}
-
-int mz_qtab_update(const float* obs6_dev, int32_t n, int32_t max_dim, const int32_t* table_of_dev,
-                   int32_t ntables, double* q_dev, const int64_t* sidx_dev,
-                   const int32_t* actions_dev, const double* reward64_dev,
-                   const uint8_t* terminated_dev, const uint8_t* truncated_dev, double* gamma_dev,
-                   const double* lr_dev, const double* eta_dev, double* cum_dev,
-                   int64_t* episodes_dev, int64_t* wins_dev, double* td_dev, int32_t episode_end,
-                   void* stream) {
-  if (int rc = qtab_check(obs6_dev, n, max_dim, table_of_dev, ntables, q_dev)) return rc;
-  if (!sidx_dev || !actions_dev || !reward64_dev || !terminated_dev || !truncated_dev ||
-      !gamma_dev || !lr_dev || !eta_dev || !cum_dev || !episodes_dev || !wins_dev)
-    return fail(MZ_EINVAL, "null argument");
-  if (table_of_dev && !td_dev) return fail(MZ_EINVAL, "shared tables need the td workspace");
-  int64_t rows = 0;
-  mz_qtab_states(max_dim, &rows);
-  StreamGuard g(stream);
-  MzQtabUpd u{obs6_dev, n, max_dim, table_of_dev, ntables, q_dev, rows, sidx_dev, actions_dev,
-              reward64_dev, terminated_dev, truncated_dev, gamma_dev, lr_dev, eta_dev, cum_dev,
-              reinterpret_cast<long long*>(episodes_dev), reinterpret_cast<long long*>(wins_dev),
-              td_dev, episode_end != 0};
-  MZ_HIP(mz_launch_qtab_update(u, static_cast<hipStream_t>(stream)));
-  return MZ_OK;
-}
-
-// ---- the same learner on hashed tables (mz_qhash.hip) -----------------------------------------
-namespace {
 // capacity: a power of two in [16, 2^30]; shift = 32 - log2 capacity
 int qhash_table(const void* keys, const void* vals, int64_t capacity, int32_t ntables, MzQhash* h) {
   if (!keys || !vals) return fail(MZ_EINVAL, "null hash table");
@@ -2125,7 +2079,159 @@ int qhash_table(const void* keys, const void* vals, int64_t capacity, int32_t nt
   h->shift = 32 - lg;
   return MZ_OK;
 }
+
+// width: 1 = Q-learning (a state is 4 f64), 2 = double Q (A and B side by side, one 64-B segment)
+int dq_align(int width, const void* q) {
+  if (width == 2 && (reinterpret_cast<uintptr_t>(q) & 63))
+    return fail(MZ_EALIGN, "double Q-tables must be 64-byte aligned");
+  return MZ_OK;
+}
+
+// What act and update check first, for every learner. keys null: dense tables at vals. Hashed
+// tables are checked before the common arguments, dense double-Q alignment after them.
+int qtab_tables(int width, const void* keys, const void* vals, int64_t capacity, const void* obs6,
+                int32_t n, int32_t max_dim, const void* table_of, int32_t ntables, bool hashed,
+                MzQhash* h) {
+  if (hashed) {
+    if (int rc = qhash_table(keys, vals, capacity, ntables, h)) return rc;
+    if (int rc = dq_align(width, vals)) return rc;
+  }
+  if (int rc = qtab_check(obs6, n, max_dim, table_of, ntables, vals)) return rc;
+  return hashed ? MZ_OK : dq_align(width, vals);
+}
+
+int qtab_act(int width, bool hashed, const float* obs6, int32_t n, int32_t max_dim,
+             const int32_t* table_of, int32_t ntables, const uint8_t* active, const int32_t* keys,
+             const double* vals, int64_t capacity, int64_t* steps_done, const double* eps_init,
+             const double* eps_final, const double* eps_decay, uint64_t seed, uint64_t counter,
+             int32_t* actions, int64_t* sidx, void* stream) {
+  MzQhash h{};
+  if (int rc = qtab_tables(width, keys, vals, capacity, obs6, n, max_dim, table_of, ntables, hashed,
+                           &h))
+    return rc;
+  if (!steps_done || !eps_init || !eps_final || !eps_decay || !actions || !sidx)
+    return fail(MZ_EINVAL, "null argument");
+  int64_t rows = 0;
+  mz_qtab_states(max_dim, &rows);
+  StreamGuard g(stream);
+  MzQtabAct a{obs6, n, max_dim, table_of, ntables, active, hashed ? nullptr : vals, rows,
+              reinterpret_cast<const long long*>(steps_done), eps_init, eps_final, eps_decay, seed,
+              counter, actions, sidx};
+  MZ_HIP(mz_launch_qtab_act(a, width, hashed ? &h : nullptr,
+                            reinterpret_cast<long long*>(steps_done),
+                            static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+// the arguments a double-Q update has beyond mz_qtab_update's
+int dq_update_check(const void* table_of, const void* td, const void* steps_done,
+                    const void* eps_init, const void* eps_final, const void* eps_decay,
+                    const void* took, const void* which) {
+  if (!steps_done || !eps_init || !eps_final || !eps_decay || !took)
+    return fail(MZ_EINVAL, "null argument");
+  if (table_of && (!td || !which))
+    return fail(MZ_EINVAL, "shared tables need the td and which workspaces");
+  return MZ_OK;
+}
+
+// Q-learning passes nothing from steps_done on (dq: the double-Q tail).
+int qtab_update(int width, bool hashed, const float* obs6, int32_t n, int32_t max_dim,
+                const int32_t* table_of, int32_t ntables, int32_t* keys, double* vals,
+                int64_t capacity, int32_t* load, int64_t* overflow, const int64_t* sidx,
+                const int32_t* actions, const double* reward64, const uint8_t* terminated,
+                const uint8_t* truncated, double* gamma, const double* lr, const double* eta,
+                double* cum, int64_t* episodes, int64_t* wins, double* td, int32_t episode_end,
+                int64_t* steps_done, const double* eps_init, const double* eps_final,
+                const double* eps_decay, uint64_t seed, uint64_t ucounter, const uint8_t* coin,
+                const int32_t* next_action, uint8_t* took, uint8_t* which, void* stream) {
+  MzQhash h{};
+  if (int rc = qtab_tables(width, keys, vals, capacity, obs6, n, max_dim, table_of, ntables, hashed,
+                           &h))
+    return rc;
+  if ((hashed && (!load || !overflow)) || !sidx || !actions || !reward64 || !terminated ||
+      !truncated || !gamma || !lr || !eta || !cum || !episodes || !wins)
+    return fail(MZ_EINVAL, "null argument");
+  if (width == 2) {
+    if (int rc = dq_update_check(table_of, td, steps_done, eps_init, eps_final, eps_decay, took,
+                                 which))
+      return rc;
+  } else if (table_of && !td) {
+    return fail(MZ_EINVAL, "shared tables need the td workspace");
+  }
+  h.load = load;
+  h.overflow = reinterpret_cast<long long*>(overflow);
+  int64_t rows = 0;
+  mz_qtab_states(max_dim, &rows);
+  StreamGuard g(stream);
+  MzDqtabUpd d{{obs6, n, max_dim, table_of, ntables, hashed ? nullptr : vals, rows, sidx, actions,
+                reward64, terminated, truncated, gamma, lr, eta, cum,
+                reinterpret_cast<long long*>(episodes), reinterpret_cast<long long*>(wins), td,
+                episode_end != 0},
+               reinterpret_cast<const long long*>(steps_done), eps_init, eps_final, eps_decay, seed,
+               ucounter, coin, next_action, took, which};
+  MZ_HIP(mz_launch_qtab_update(d, width, hashed ? &h : nullptr,
+                               reinterpret_cast<long long*>(steps_done),
+                               static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int qtab_rehash(int width, const int32_t* keys, const double* vals, int64_t capacity,
+                int32_t* new_keys, double* new_vals, int64_t new_capacity, int32_t ntables,
+                int64_t* overflow, void* stream) {
+  MzQhash from, to;
+  if (int rc = qhash_table(keys, vals, capacity, ntables, &from)) return rc;
+  if (int rc = qhash_table(new_keys, new_vals, new_capacity, ntables, &to)) return rc;
+  if (int rc = dq_align(width, vals)) return rc;
+  if (int rc = dq_align(width, new_vals)) return rc;
+  if (!overflow) return fail(MZ_EINVAL, "null argument");
+  if (keys == new_keys || vals == new_vals) return fail(MZ_EINVAL, "rehash needs fresh arrays");
+  to.overflow = reinterpret_cast<long long*>(overflow);
+  StreamGuard g(stream);
+  MZ_HIP(mz_launch_qtab_rehash(from, to, ntables, width, static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int qtab_lookup(int width, const int32_t* keys, const double* vals, int64_t capacity,
+                int32_t ntables, const int32_t* tables, const int64_t* query_keys, int32_t m,
+                double* rows_out, int32_t* slots_out, void* stream) {
+  MzQhash h;
+  if (int rc = qhash_table(keys, vals, capacity, ntables, &h)) return rc;
+  if (int rc = dq_align(width, vals)) return rc;
+  if (m < 0) return fail(MZ_EINVAL, "m %d must be >= 0", m);
+  if (m == 0) return MZ_OK;
+  if (!tables || !query_keys || !rows_out || !slots_out) return fail(MZ_EINVAL, "null argument");
+  if (reinterpret_cast<uintptr_t>(rows_out) & 15)
+    return fail(MZ_EALIGN, "rows_out must be 16-byte aligned");
+  StreamGuard g(stream);
+  MZ_HIP(mz_launch_qtab_lookup(h, ntables, width, tables, query_keys, m, rows_out, slots_out,
+                               static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
 }  // namespace
+
+int mz_qtab_act(const float* obs6_dev, int32_t n, int32_t max_dim, const int32_t* table_of_dev,
+                int32_t ntables, const uint8_t* active_dev, const double* q_dev,
+                int64_t* steps_done_dev, const double* eps_init_dev, const double* eps_final_dev,
+                const double* eps_decay_dev, uint64_t seed, uint64_t counter, int32_t* actions_dev,
+                int64_t* sidx_dev, void* stream) {
+  return qtab_act(1, false, obs6_dev, n, max_dim, table_of_dev, ntables, active_dev, nullptr, q_dev,
+                  0, steps_done_dev, eps_init_dev, eps_final_dev, eps_decay_dev, seed, counter,
+                  actions_dev, sidx_dev, stream);
+}
+
+int mz_qtab_update(const float* obs6_dev, int32_t n, int32_t max_dim, const int32_t* table_of_dev,
+                   int32_t ntables, double* q_dev, const int64_t* sidx_dev,
+                   const int32_t* actions_dev, const double* reward64_dev,
+                   const uint8_t* terminated_dev, const uint8_t* truncated_dev, double* gamma_dev,
+                   const double* lr_dev, const double* eta_dev, double* cum_dev,
+                   int64_t* episodes_dev, int64_t* wins_dev, double* td_dev, int32_t episode_end,
+                   void* stream) {
+  return qtab_update(1, false, obs6_dev, n, max_dim, table_of_dev, ntables, nullptr, q_dev, 0,
+                     nullptr, nullptr, sidx_dev, actions_dev, reward64_dev, terminated_dev,
+                     truncated_dev, gamma_dev, lr_dev, eta_dev, cum_dev, episodes_dev, wins_dev,
+                     td_dev, episode_end, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr,
+                     nullptr, nullptr, nullptr, stream);
+}
 
 int mz_qtab_hash_act(const float* obs6_dev, int32_t n, int32_t max_dim,
                      const int32_t* table_of_dev, int32_t ntables, const uint8_t* active_dev,
@@ -2133,21 +2239,9 @@ int mz_qtab_hash_act(const float* obs6_dev, int32_t n, int32_t max_dim,
                      int64_t* steps_done_dev, const double* eps_init_dev,
                      const double* eps_final_dev, const double* eps_decay_dev, uint64_t seed,
                      uint64_t counter, int32_t* actions_dev, int64_t* sidx_dev, void* stream) {
-  MzQhash h;
-  if (int rc = qhash_table(keys_dev, vals_dev, capacity, ntables, &h)) return rc;
-  if (int rc = qtab_check(obs6_dev, n, max_dim, table_of_dev, ntables, vals_dev)) return rc;
-  if (!steps_done_dev || !eps_init_dev || !eps_final_dev || !eps_decay_dev || !actions_dev ||
-      !sidx_dev)
-    return fail(MZ_EINVAL, "null argument");
-  int64_t rows = 0;
-  mz_qtab_states(max_dim, &rows);
-  StreamGuard g(stream);
-  MzQtabAct a{obs6_dev, n, max_dim, table_of_dev, ntables, active_dev, nullptr, rows,
-              reinterpret_cast<const long long*>(steps_done_dev), eps_init_dev, eps_final_dev,
-              eps_decay_dev, seed, counter, actions_dev, sidx_dev};
-  MZ_HIP(mz_launch_qhash_act(a, h, reinterpret_cast<long long*>(steps_done_dev),
-                             static_cast<hipStream_t>(stream)));
-  return MZ_OK;
+  return qtab_act(1, true, obs6_dev, n, max_dim, table_of_dev, ntables, active_dev, keys_dev,
+                  vals_dev, capacity, steps_done_dev, eps_init_dev, eps_final_dev, eps_decay_dev,
+                  seed, counter, actions_dev, sidx_dev, stream);
 }
 
 int mz_qtab_hash_update(const float* obs6_dev, int32_t n, int32_t max_dim,
@@ -2158,99 +2252,36 @@ int mz_qtab_hash_update(const float* obs6_dev, int32_t n, int32_t max_dim,
                         const uint8_t* truncated_dev, double* gamma_dev, const double* lr_dev,
                         const double* eta_dev, double* cum_dev, int64_t* episodes_dev,
                         int64_t* wins_dev, double* td_dev, int32_t episode_end, void* stream) {
-  MzQhash h;
-  if (int rc = qhash_table(keys_dev, vals_dev, capacity, ntables, &h)) return rc;
-  if (int rc = qtab_check(obs6_dev, n, max_dim, table_of_dev, ntables, vals_dev)) return rc;
-  if (!load_dev || !overflow_dev || !sidx_dev || !actions_dev || !reward64_dev ||
-      !terminated_dev || !truncated_dev || !gamma_dev || !lr_dev || !eta_dev || !cum_dev ||
-      !episodes_dev || !wins_dev)
-    return fail(MZ_EINVAL, "null argument");
-  if (table_of_dev && !td_dev) return fail(MZ_EINVAL, "shared tables need the td workspace");
-  h.load = load_dev;
-  h.overflow = reinterpret_cast<long long*>(overflow_dev);
-  int64_t rows = 0;
-  mz_qtab_states(max_dim, &rows);
-  StreamGuard g(stream);
-  MzQtabUpd u{obs6_dev, n, max_dim, table_of_dev, ntables, nullptr, rows, sidx_dev, actions_dev,
-              reward64_dev, terminated_dev, truncated_dev, gamma_dev, lr_dev, eta_dev, cum_dev,
-              reinterpret_cast<long long*>(episodes_dev), reinterpret_cast<long long*>(wins_dev),
-              td_dev, episode_end != 0};
-  MZ_HIP(mz_launch_qhash_update(u, h, static_cast<hipStream_t>(stream)));
-  return MZ_OK;
+  return qtab_update(1, true, obs6_dev, n, max_dim, table_of_dev, ntables, keys_dev, vals_dev,
+                     capacity, load_dev, overflow_dev, sidx_dev, actions_dev, reward64_dev,
+                     terminated_dev, truncated_dev, gamma_dev, lr_dev, eta_dev, cum_dev,
+                     episodes_dev, wins_dev, td_dev, episode_end, nullptr, nullptr, nullptr,
+                     nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int mz_qtab_hash_rehash(const int32_t* keys_dev, const double* vals_dev, int64_t capacity,
                         int32_t* new_keys_dev, double* new_vals_dev, int64_t new_capacity,
                         int32_t ntables, int64_t* overflow_dev, void* stream) {
-  MzQhash from, to;
-  if (int rc = qhash_table(keys_dev, vals_dev, capacity, ntables, &from)) return rc;
-  if (int rc = qhash_table(new_keys_dev, new_vals_dev, new_capacity, ntables, &to)) return rc;
-  if (!overflow_dev) return fail(MZ_EINVAL, "null argument");
-  if (keys_dev == new_keys_dev || vals_dev == new_vals_dev)
-    return fail(MZ_EINVAL, "rehash needs fresh arrays");
-  to.overflow = reinterpret_cast<long long*>(overflow_dev);
-  StreamGuard g(stream);
-  MZ_HIP(mz_launch_qhash_rehash(from, to, ntables, static_cast<hipStream_t>(stream)));
-  return MZ_OK;
+  return qtab_rehash(1, keys_dev, vals_dev, capacity, new_keys_dev, new_vals_dev, new_capacity,
+                     ntables, overflow_dev, stream);
 }
 
 int mz_qtab_hash_lookup(const int32_t* keys_dev, const double* vals_dev, int64_t capacity,
                         int32_t ntables, const int32_t* tables_dev,
                         const int64_t* query_keys_dev, int32_t m, double* rows_out_dev,
                         int32_t* slots_out_dev, void* stream) {
-  MzQhash h;
-  if (int rc = qhash_table(keys_dev, vals_dev, capacity, ntables, &h)) return rc;
-  if (m < 0) return fail(MZ_EINVAL, "m %d must be >= 0", m);
-  if (m == 0) return MZ_OK;
-  if (!tables_dev || !query_keys_dev || !rows_out_dev || !slots_out_dev)
-    return fail(MZ_EINVAL, "null argument");
-  if (reinterpret_cast<uintptr_t>(rows_out_dev) & 15)
-    return fail(MZ_EALIGN, "rows_out must be 16-byte aligned");
-  StreamGuard g(stream);
-  MZ_HIP(mz_launch_qhash_lookup(h, ntables, tables_dev, query_keys_dev, m, rows_out_dev,
-                                slots_out_dev, static_cast<hipStream_t>(stream)));
-  return MZ_OK;
+  return qtab_lookup(1, keys_dev, vals_dev, capacity, ntables, tables_dev, query_keys_dev, m,
+                     rows_out_dev, slots_out_dev, stream);
 }
-
-// ---- double Q-learning on either storage (mz_dqtab.hip) ---------------------------------------
-namespace {
-int dq_align(const void* q) {
-  if (reinterpret_cast<uintptr_t>(q) & 63)
-    return fail(MZ_EALIGN, "double Q-tables must be 64-byte aligned");
-  return MZ_OK;
-}
-
-// the arguments an update has beyond mz_qtab_update's
-int dq_update_check(const void* table_of, const void* td, const void* steps_done,
-                    const void* eps_init, const void* eps_final, const void* eps_decay,
-                    const void* took, const void* which) {
-  if (!steps_done || !eps_init || !eps_final || !eps_decay || !took)
-    return fail(MZ_EINVAL, "null argument");
-  if (table_of && (!td || !which))
-    return fail(MZ_EINVAL, "shared tables need the td and which workspaces");
-  return MZ_OK;
-}
-}  // namespace
 
 int mz_dqtab_act(const float* obs6_dev, int32_t n, int32_t max_dim, const int32_t* table_of_dev,
                  int32_t ntables, const uint8_t* active_dev, const double* q_dev,
                  int64_t* steps_done_dev, const double* eps_init_dev, const double* eps_final_dev,
                  const double* eps_decay_dev, uint64_t seed, uint64_t counter, int32_t* actions_dev,
                  int64_t* sidx_dev, void* stream) {
-  if (int rc = qtab_check(obs6_dev, n, max_dim, table_of_dev, ntables, q_dev)) return rc;
-  if (int rc = dq_align(q_dev)) return rc;
-  if (!steps_done_dev || !eps_init_dev || !eps_final_dev || !eps_decay_dev || !actions_dev ||
-      !sidx_dev)
-    return fail(MZ_EINVAL, "null argument");
-  int64_t rows = 0;
-  mz_qtab_states(max_dim, &rows);
-  StreamGuard g(stream);
-  MzQtabAct a{obs6_dev, n, max_dim, table_of_dev, ntables, active_dev, q_dev, rows,
-              reinterpret_cast<const long long*>(steps_done_dev), eps_init_dev, eps_final_dev,
-              eps_decay_dev, seed, counter, actions_dev, sidx_dev};
-  MZ_HIP(mz_launch_dqtab_act(a, nullptr, reinterpret_cast<long long*>(steps_done_dev),
-                             static_cast<hipStream_t>(stream)));
-  return MZ_OK;
+  return qtab_act(2, false, obs6_dev, n, max_dim, table_of_dev, ntables, active_dev, nullptr, q_dev,
+                  0, steps_done_dev, eps_init_dev, eps_final_dev, eps_decay_dev, seed, counter,
+                  actions_dev, sidx_dev, stream);
 }
 
 int mz_dqtab_update(const float* obs6_dev, int32_t n, int32_t max_dim, const int32_t* table_of_dev,
@@ -2263,26 +2294,12 @@ int mz_dqtab_update(const float* obs6_dev, int32_t n, int32_t max_dim, const int
                     const double* eps_final_dev, const double* eps_decay_dev, uint64_t seed,
                     uint64_t ucounter, const uint8_t* coin_dev, const int32_t* next_action_dev,
                     uint8_t* took_dev, uint8_t* which_dev, void* stream) {
-  if (int rc = qtab_check(obs6_dev, n, max_dim, table_of_dev, ntables, q_dev)) return rc;
-  if (int rc = dq_align(q_dev)) return rc;
-  if (!sidx_dev || !actions_dev || !reward64_dev || !terminated_dev || !truncated_dev ||
-      !gamma_dev || !lr_dev || !eta_dev || !cum_dev || !episodes_dev || !wins_dev)
-    return fail(MZ_EINVAL, "null argument");
-  if (int rc = dq_update_check(table_of_dev, td_dev, steps_done_dev, eps_init_dev, eps_final_dev,
-                               eps_decay_dev, took_dev, which_dev))
-    return rc;
-  int64_t rows = 0;
-  mz_qtab_states(max_dim, &rows);
-  StreamGuard g(stream);
-  MzDqtabUpd d{{obs6_dev, n, max_dim, table_of_dev, ntables, q_dev, rows, sidx_dev, actions_dev,
-                reward64_dev, terminated_dev, truncated_dev, gamma_dev, lr_dev, eta_dev, cum_dev,
-                reinterpret_cast<long long*>(episodes_dev), reinterpret_cast<long long*>(wins_dev),
-                td_dev, episode_end != 0},
-               reinterpret_cast<const long long*>(steps_done_dev), eps_init_dev, eps_final_dev,
-               eps_decay_dev, seed, ucounter, coin_dev, next_action_dev, took_dev, which_dev};
-  MZ_HIP(mz_launch_dqtab_update(d, nullptr, reinterpret_cast<long long*>(steps_done_dev),
-                                static_cast<hipStream_t>(stream)));
-  return MZ_OK;
+  return qtab_update(2, false, obs6_dev, n, max_dim, table_of_dev, ntables, nullptr, q_dev, 0,
+                     nullptr, nullptr, sidx_dev, actions_dev, reward64_dev, terminated_dev,
+                     truncated_dev, gamma_dev, lr_dev, eta_dev, cum_dev, episodes_dev, wins_dev,
+                     td_dev, episode_end, steps_done_dev, eps_init_dev, eps_final_dev,
+                     eps_decay_dev, seed, ucounter, coin_dev, next_action_dev, took_dev, which_dev,
+                     stream);
 }
 
 int mz_dqtab_hash_act(const float* obs6_dev, int32_t n, int32_t max_dim,
@@ -2291,22 +2308,9 @@ int mz_dqtab_hash_act(const float* obs6_dev, int32_t n, int32_t max_dim,
                       int64_t* steps_done_dev, const double* eps_init_dev,
                       const double* eps_final_dev, const double* eps_decay_dev, uint64_t seed,
                       uint64_t counter, int32_t* actions_dev, int64_t* sidx_dev, void* stream) {
-  MzQhash h;
-  if (int rc = qhash_table(keys_dev, vals_dev, capacity, ntables, &h)) return rc;
-  if (int rc = dq_align(vals_dev)) return rc;
-  if (int rc = qtab_check(obs6_dev, n, max_dim, table_of_dev, ntables, vals_dev)) return rc;
-  if (!steps_done_dev || !eps_init_dev || !eps_final_dev || !eps_decay_dev || !actions_dev ||
-      !sidx_dev)
-    return fail(MZ_EINVAL, "null argument");
-  int64_t rows = 0;
-  mz_qtab_states(max_dim, &rows);
-  StreamGuard g(stream);
-  MzQtabAct a{obs6_dev, n, max_dim, table_of_dev, ntables, active_dev, nullptr, rows,
-              reinterpret_cast<const long long*>(steps_done_dev), eps_init_dev, eps_final_dev,
-              eps_decay_dev, seed, counter, actions_dev, sidx_dev};
-  MZ_HIP(mz_launch_dqtab_act(a, &h, reinterpret_cast<long long*>(steps_done_dev),
-                             static_cast<hipStream_t>(stream)));
-  return MZ_OK;
+  return qtab_act(2, true, obs6_dev, n, max_dim, table_of_dev, ntables, active_dev, keys_dev,
+                  vals_dev, capacity, steps_done_dev, eps_init_dev, eps_final_dev, eps_decay_dev,
+                  seed, counter, actions_dev, sidx_dev, stream);
 }
 
 int mz_dqtab_hash_update(const float* obs6_dev, int32_t n, int32_t max_dim,
@@ -2322,65 +2326,25 @@ int mz_dqtab_hash_update(const float* obs6_dev, int32_t n, int32_t max_dim,
                          uint64_t ucounter, const uint8_t* coin_dev,
                          const int32_t* next_action_dev, uint8_t* took_dev, uint8_t* which_dev,
                          void* stream) {
-  MzQhash h;
-  if (int rc = qhash_table(keys_dev, vals_dev, capacity, ntables, &h)) return rc;
-  if (int rc = dq_align(vals_dev)) return rc;
-  if (int rc = qtab_check(obs6_dev, n, max_dim, table_of_dev, ntables, vals_dev)) return rc;
-  if (!load_dev || !overflow_dev || !sidx_dev || !actions_dev || !reward64_dev ||
-      !terminated_dev || !truncated_dev || !gamma_dev || !lr_dev || !eta_dev || !cum_dev ||
-      !episodes_dev || !wins_dev)
-    return fail(MZ_EINVAL, "null argument");
-  if (int rc = dq_update_check(table_of_dev, td_dev, steps_done_dev, eps_init_dev, eps_final_dev,
-                               eps_decay_dev, took_dev, which_dev))
-    return rc;
-  h.load = load_dev;
-  h.overflow = reinterpret_cast<long long*>(overflow_dev);
-  int64_t rows = 0;
-  mz_qtab_states(max_dim, &rows);
-  StreamGuard g(stream);
-  MzDqtabUpd d{{obs6_dev, n, max_dim, table_of_dev, ntables, nullptr, rows, sidx_dev, actions_dev,
-                reward64_dev, terminated_dev, truncated_dev, gamma_dev, lr_dev, eta_dev, cum_dev,
-                reinterpret_cast<long long*>(episodes_dev), reinterpret_cast<long long*>(wins_dev),
-                td_dev, episode_end != 0},
-               reinterpret_cast<const long long*>(steps_done_dev), eps_init_dev, eps_final_dev,
-               eps_decay_dev, seed, ucounter, coin_dev, next_action_dev, took_dev, which_dev};
-  MZ_HIP(mz_launch_dqtab_update(d, &h, reinterpret_cast<long long*>(steps_done_dev),
-                                static_cast<hipStream_t>(stream)));
-  return MZ_OK;
+  return qtab_update(2, true, obs6_dev, n, max_dim, table_of_dev, ntables, keys_dev, vals_dev,
+                     capacity, load_dev, overflow_dev, sidx_dev, actions_dev, reward64_dev,
+                     terminated_dev, truncated_dev, gamma_dev, lr_dev, eta_dev, cum_dev,
+                     episodes_dev, wins_dev, td_dev, episode_end, steps_done_dev, eps_init_dev,
+                     eps_final_dev, eps_decay_dev, seed, ucounter, coin_dev, next_action_dev,
+                     took_dev, which_dev, stream);
 }
 
 int mz_dqtab_hash_rehash(const int32_t* keys_dev, const double* vals_dev, int64_t capacity,
                          int32_t* new_keys_dev, double* new_vals_dev, int64_t new_capacity,
                          int32_t ntables, int64_t* overflow_dev, void* stream) {
-  MzQhash from, to;
-  if (int rc = qhash_table(keys_dev, vals_dev, capacity, ntables, &from)) return rc;
-  if (int rc = qhash_table(new_keys_dev, new_vals_dev, new_capacity, ntables, &to)) return rc;
-  if (int rc = dq_align(vals_dev)) return rc;
-  if (int rc = dq_align(new_vals_dev)) return rc;
-  if (!overflow_dev) return fail(MZ_EINVAL, "null argument");
-  if (keys_dev == new_keys_dev || vals_dev == new_vals_dev)
-    return fail(MZ_EINVAL, "rehash needs fresh arrays");
-  to.overflow = reinterpret_cast<long long*>(overflow_dev);
-  StreamGuard g(stream);
-  MZ_HIP(mz_launch_dqhash_rehash(from, to, ntables, static_cast<hipStream_t>(stream)));
-  return MZ_OK;
+  return qtab_rehash(2, keys_dev, vals_dev, capacity, new_keys_dev, new_vals_dev, new_capacity,
+                     ntables, overflow_dev, stream);
 }
 
 int mz_dqtab_hash_lookup(const int32_t* keys_dev, const double* vals_dev, int64_t capacity,
                          int32_t ntables, const int32_t* tables_dev,
                          const int64_t* query_keys_dev, int32_t m, double* rows_out_dev,
                          int32_t* slots_out_dev, void* stream) {
-  MzQhash h;
-  if (int rc = qhash_table(keys_dev, vals_dev, capacity, ntables, &h)) return rc;
-  if (int rc = dq_align(vals_dev)) return rc;
-  if (m < 0) return fail(MZ_EINVAL, "m %d must be >= 0", m);
-  if (m == 0) return MZ_OK;
-  if (!tables_dev || !query_keys_dev || !rows_out_dev || !slots_out_dev)
-    return fail(MZ_EINVAL, "null argument");
-  if (reinterpret_cast<uintptr_t>(rows_out_dev) & 15)
-    return fail(MZ_EALIGN, "rows_out must be 16-byte aligned");
-  StreamGuard g(stream);
-  MZ_HIP(mz_launch_dqhash_lookup(h, ntables, tables_dev, query_keys_dev, m, rows_out_dev,
-                                 slots_out_dev, static_cast<hipStream_t>(stream)));
-  return MZ_OK;
+  return qtab_lookup(2, keys_dev, vals_dev, capacity, ntables, tables_dev, query_keys_dev, m,
+                     rows_out_dev, slots_out_dev, stream);
 }

@@ -326,12 +326,13 @@ hipError_t mz_launch_qact(const MzQAct& q, int relu, hipStream_t s);
 hipError_t mz_launch_qact_prepare(const float* w1, const float* w2, uint16_t* w1h, uint16_t* w1l,
                                   uint16_t* w2h, uint16_t* w2l, hipStream_t s);
 
-// ---- vectorised tabular Q-learning (mz_qtab.hip) ----------------------------------------------
+// ---- vectorised tabular learners: Q and double Q, dense or hashed tables (mz_qtab.hip) --------
 struct MzQtabAct {
   const float* obs6; int n, P;               // plain observations [n][6], pitch of the index
   const int32_t* table_of; int T;            // instance -> table (null: i), tables
   const uint8_t* active;                     // [n] 0 = the instance idles (null: all act)
-  const double* q; int64_t rows;             // [T][rows][4] f64
+  const double* q; int64_t rows;             // dense: [T][rows][4] f64; hashed: null, rows stays
+                                             // 5 P^4, the key range
   const long long* steps_done;               // [T]
   const double* eps_init; const double* eps_final; const double* eps_decay;  // [T]
   uint64_t seed, counter;
@@ -349,29 +350,14 @@ struct MzQtabUpd {
   double* td;                                // [n] lr * td between the two shared-table passes
   int episode_end;                           // 0: QAgent.update alone (no gamma drift, no counters)
 };
-hipError_t mz_launch_qtab_act(const MzQtabAct& a, long long* steps_done, hipStream_t s);
-hipError_t mz_launch_qtab_update(const MzQtabUpd& u, hipStream_t s);
-hipError_t mz_launch_qtab_advance(const int32_t* table_of, const uint8_t* active, int n, int T,
-                                  long long* steps_done, hipStream_t s);
-
-// ---- hashed tables of the same learner (mz_qhash.hip) -----------------------------------------
+// hashed tables of the same learners
 struct MzQhash {
   int32_t* keys;                             // [T][C] dense state index, -1 = empty
   double* vals;                              // [T][C][4] f64, zero until written
   int32_t* load; long long* overflow;        // [T] occupied slots, dropped updates
   uint32_t C; int shift;                     // capacity (a power of two), 32 - log2 C
 };
-// act / update: the dense launch's arguments with q == nullptr (rows stays 5 P^4, the key range)
-hipError_t mz_launch_qhash_act(const MzQtabAct& a, const MzQhash& h, long long* steps_done,
-                               hipStream_t s);
-hipError_t mz_launch_qhash_update(const MzQtabUpd& u, const MzQhash& h, hipStream_t s);
-hipError_t mz_launch_qhash_rehash(const MzQhash& from, const MzQhash& to, int T, hipStream_t s);
-hipError_t mz_launch_qhash_lookup(const MzQhash& h, int T, const int32_t* tables,
-                                  const int64_t* keys, int m, double* rows_out, int32_t* slots_out,
-                                  hipStream_t s);
-
-// ---- double Q-learning on either storage (mz_dqtab.hip) ---------------------------------------
-// A state's A row and B row sit side by side, [2][4] f64 = 64 B: MzQtabAct::q / MzQtabUpd::q are
+// double Q-learning. A state's A row and B row sit side by side, [2][4] f64 = 64 B: MzQtabAct::q / MzQtabUpd::q are
 // [T][rows][2][4] and MzQhash::vals is [T][C][2][4] (64-B aligned).
 struct MzDqtabUpd {
   MzQtabUpd u;                               // u.td: lr * td between the two shared-table passes
@@ -383,13 +369,18 @@ struct MzDqtabUpd {
   uint8_t* took;                             // [n] 1 where a td was computed
   uint8_t* which;                            // [n] the table updated, between the shared passes
 };
-// act: k_qtab_act on the A row, then the advance. update: independent tables one launch, shared
-// tables two; then mz_launch_qtab_advance(table_of, took, ...) for the inner get_actions.
-hipError_t mz_launch_dqtab_act(const MzQtabAct& a, const MzQhash* h, long long* steps_done,
-                               hipStream_t s);
-hipError_t mz_launch_dqtab_update(const MzDqtabUpd& d, const MzQhash* h, long long* steps_done,
-                                  hipStream_t s);
-hipError_t mz_launch_dqhash_rehash(const MzQhash& from, const MzQhash& to, int T, hipStream_t s);
-hipError_t mz_launch_dqhash_lookup(const MzQhash& h, int T, const int32_t* tables,
-                                   const int64_t* keys, int m, double* rows_out,
-                                   int32_t* slots_out, hipStream_t s);
+// One launcher per stage. width: 1 = Q-learning, 2 = double Q. h: the hashed tables (null: dense,
+// a.q / d.u.q). act: k_qtab_act (double Q: on the A row), then the advance. update: independent
+// tables one launch, shared tables two (td, apply); Q-learning reads d.u alone; double Q then
+// advances steps_done by took, for the inner get_actions.
+hipError_t mz_launch_qtab_act(const MzQtabAct& a, int width, const MzQhash* h,
+                              long long* steps_done, hipStream_t s);
+hipError_t mz_launch_qtab_update(const MzDqtabUpd& d, int width, const MzQhash* h,
+                                 long long* steps_done, hipStream_t s);
+hipError_t mz_launch_qtab_advance(const int32_t* table_of, const uint8_t* active, int n, int T,
+                                  long long* steps_done, hipStream_t s);
+hipError_t mz_launch_qtab_rehash(const MzQhash& from, const MzQhash& to, int T, int width,
+                                 hipStream_t s);
+hipError_t mz_launch_qtab_lookup(const MzQhash& h, int T, int width, const int32_t* tables,
+                                 const int64_t* keys, int m, double* rows_out, int32_t* slots_out,
+                                 hipStream_t s);

@@ -1,5 +1,5 @@
-// mz_qhash.h — the probe and the claim of the hashed Q-tables, shared by mz_qhash.hip (one 4-wide
-// row per slot) and mz_dqtab.hip (an A row and a B row per slot). Only the keys are touched here:
+// mz_qhash.h — the probe and the claim of the hashed Q-tables (mz_qtab.h's Hashed<W>: one 4-wide
+// row per slot for Q, an A row and a B row per slot for double Q). Only the keys are touched here:
 // int32 [C] per table, -1 = empty, slot0 = (uint32(key) * 0x9E3779B1u) >> shift, then +1 mod C.
 // Every loop runs at most C iterations, so a full table terminates.
 #pragma once

@@ -20,8 +20,8 @@ LIBDIR = os.path.join(PKG, "_lib")
 LIB = os.path.join(LIBDIR, "libmazerl.so")
 SOURCES = ["mz_env.hip", "mz_api.hip", "mz_difficulty.hip", "mz_qnet.hip", "mz_metrics.hip",
            "mz_stem.hip", "mz_optim.hip", "mz_trainer.hip", "mz_ppo.hip",
-           "mz_qact.hip", "mz_mcclendon.hip", "mz_screen.hip", "mz_qtab.hip", "mz_qhash.hip",
-           "mz_dqtab.hip", "mz_reinforce.hip", "mz_drqn.hip", "mz_archive.hip", "mz_cae.hip"]
+           "mz_qact.hip", "mz_mcclendon.hip", "mz_screen.hip", "mz_qtab.hip",
+           "mz_reinforce.hip", "mz_drqn.hip", "mz_archive.hip", "mz_cae.hip"]
 EXTRA_FLAGS = {"mz_qnet.hip": ["-ffinite-math-only"],
                "mz_qact.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall"]

@@ -1,7 +1,7 @@
 """VectorDoubleQAgent — a population of the reference's double Q-learning agent, DQAgent
 (agents/dq_agent.py:5-73), on the vector engine of VectorQAgent: the constructor contract, the
 per-table hyper-parameters, the state index, the two storages and the trainer are VectorQAgent's
-(vector_q.py); the learner is csrc/mz_dqtab.hip.
+(vector_q.py); the learner is RuleDQ of csrc/mz_qtab.hip.
 
 A state holds two rows, Q_A and Q_B, side by side ([2, 4] float64, 64 B): self.q is
 [T, rows, 2, 4] (dense, 2.1 MB per table at 9x9), self.vals [T, C, 2, 4] (hashed, 68 B per slot,

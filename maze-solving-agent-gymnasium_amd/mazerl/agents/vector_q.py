@@ -15,7 +15,7 @@ can sweep learning rate, gamma, eta and the epsilon schedule.
 
 storage="hash" keeps each table as the reference's own sparse structure instead (its defaultdict
 holds only the states met): an open-addressing hash table of `capacity` slots in HBM, keyed by
-the same state index (csrc/mz_qhash.hip; hash_slot is the mirror of its hash). A dense table is
+the same state index (csrc/mz_qtab.hip; hash_slot is the mirror of its hash). A dense table is
 452 MB at 41x41 and 6.9 GB at 81x81; a hashed one is 36 B per slot, so thousands of learners fit
 at the reference's maze sizes. Acting never inserts; an update inserts its state's key. A full
 table drops the value update and counts it in `overflow` — size `capacity` for the states a

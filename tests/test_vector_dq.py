@@ -1,4 +1,4 @@
-"""VectorDoubleQAgent (csrc/mz_dqtab.hip): a population of the reference's double Q-learning agent,
+"""VectorDoubleQAgent (csrc/mz_qtab.hip): a population of the reference's double Q-learning agent,
 DQAgent (agents/dq_agent.py:5-73), on the GPU — against the reference's own fixture
 (tests/golden/dq_agent.npz, written by tests/golden/make_golden_dq.py) and against a CPU
 restatement written here, as Restated in test_vector_q.py: one oracle env per instance, a dict of

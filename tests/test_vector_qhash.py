@@ -1,4 +1,4 @@
-"""VectorQAgent(storage="hash") (csrc/mz_qhash.hip): the population of tabular Q-learners on
+"""VectorQAgent(storage="hash") (csrc/mz_qtab.hip, Hashed): the population of tabular Q-learners on
 open-addressing hash tables in HBM, against the CPU restatement of tests/test_vector_q.py (shared,
 never modified) and against the dense storage. Everything is compared with == on float64 bits."""
 import ctypes
