@@ -193,6 +193,7 @@ double hallway_complexity(const Graph& G, const std::unordered_map<int64_t, int>
       if (!nodes.count(u) || seen.count(u)) continue;
       auto it = dmap.find(Graph::key(v, u));
       if (it == dmap.end()) continue;  // get_edge_attributes skips edges without "d"
+      if (it->second == 0) return NAN;  // 1 / (2 d): ZeroDivisionError in the reference
       D += it->second;
       const double t = 1.0 / (2.0 * (double)it->second);
       s = first ? (0 + t) : s + t;  // sum() starts from int 0
@@ -238,7 +239,15 @@ std::vector<std::vector<int>> components(const Graph& G, const std::unordered_se
 int mcclendon(const uint8_t* g, int32_t H, int32_t W, int32_t sr, int32_t sc, int32_t gr,
               int32_t gc, double* difficulty, double* complexity, double* prod_out = nullptr) {
   if (!g || H < 3 || W < 3) return MZ_EINVAL;
-  auto open = [&](int r, int c) { return g[r * W + c] != 0; };
+  // maze[r][c] as the reference indexes it next to a border square: row / column -1 is Python's
+  // last one, row H / column W raises IndexError (reported as MZ_EINVAL below)
+  bool past = false;
+  auto open = [&](int r, int c) {
+    if (r < 0) r += H;
+    if (c < 0) c += W;
+    if (r >= H || c >= W) { past = true; return false; }
+    return g[r * W + c] != 0;
+  };
   auto nbrs = [&](int v) {
     const int r = v / W, c = v % W;
     return (int)open(r - 1, c) + (int)open(r + 1, c) + (int)open(r, c - 1) + (int)open(r, c + 1);
@@ -413,6 +422,7 @@ int mcclendon(const uint8_t* g, int32_t H, int32_t W, int32_t sr, int32_t sc, in
   const double c0 = hallway_complexity(H0, d_sol, h0_nodes, h0_order);  // branch 0 = [0], last
   prod *= c0;
   sum += c0;
+  if (past) return MZ_EINVAL;
   if (prod_out) *prod_out = prod;
   if (difficulty) {
     if (!(prod > 0.0)) return MZ_EINVAL;  // math.log domain error in the reference

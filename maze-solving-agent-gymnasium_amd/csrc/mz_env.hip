@@ -1011,6 +1011,17 @@ __global__ __launch_bounds__(WAVE) void k_compact_from_handle(MzDev d, const int
     const uint32_t* cw = d.cells + (size_t)e * P * P;
     auto open = [&](int r, int c) { return r >= 0 && c >= 0 && r < N && c < N && (cw[r * P + c] & MZ_CELL_OPEN); };
     bool lattice = !d.toroidal && (N & 1) && N < 128 && (sr & 1) && (sc & 1) && (gr & 1) && (gc & 1);
+    // every open square a cell or a passage between two cells: none on the border, none at an
+    // even-even position (the compact form has no place for them, and the reference counts them
+    // as neighbours)
+    int off = 0;
+    for (int q = lane; q < N * N && lattice; q += WAVE) {
+      const int r = q / N, c = q - r * N;
+      if ((cw[r * P + c] & MZ_CELL_OPEN) &&
+          (r == 0 || c == 0 || r == N - 1 || c == N - 1 || !((r | c) & 1)))
+        off = 1;
+    }
+    if (__any(off)) lattice = false;
     uint8_t* gp = cc.pas + (size_t)i * cc.Qp;
     uint16_t* ga = cc.dist + (size_t)i * cc.Qp;
     uint32_t* gs = cc.sol + (size_t)i * cc.QWp;

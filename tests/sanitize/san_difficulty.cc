@@ -76,6 +76,19 @@ int main() {
         CHECK(mzo_generate(m.data(), M, M, 0, algo, ++seed, &sr, &sc, &gr, &gc) == 0, "gen");
         score(m, M, sr, sc, gr, gc, true);
       }
+  // a start on an open border square (a leaf next to a cell, on each side): the reference's
+  // neighbour count indexes row / column -1 (Python: the far side) or N (IndexError) there — a
+  // status or a value, never a read outside the grid (the vectors hold exactly N * N squares)
+  for (int side = 0; side < 4; ++side) {
+    const int N = 15;
+    int sr, sc, gr, gc;
+    std::vector<uint8_t> m(N * N);
+    CHECK(mzo_generate(m.data(), N, N, 0, side % 3, ++seed, &sr, &sc, &gr, &gc) == 0, "gen");
+    const int br = side == 0 ? 0 : side == 2 ? N - 1 : 7, bc = side == 1 ? 0 : side == 3 ? N - 1 : 7;
+    m[br * N + bc] = 1;
+    score(m, N, br, bc, gr, gc, false);
+    score(m, N, sr, sc, gr, gc, false);  // and the leaf as a bystander
+  }
   // argument validation
   double d;
   CHECK(mz_difficulty(g.data(), 15, 15, 1, 1, 13, 13, nullptr) != MZ_OK, "null out accepted");

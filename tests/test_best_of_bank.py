@@ -236,3 +236,172 @@ def test_bank_slots_with_host_scored_candidates():
     st = env.select_stats()
     assert st["groups"] == 4 * K and st["host_scored"] == 4 * K * 3 and st["unresolved"] == 0, st
     env.close()
+
+
+# ---- past the caps: kXCap = 256 groups for the order-exact kernel, kHCap = 256 declined candidates
+# for the host restatement per run (mz_api.hip). What the code promises there: a group past kXCap
+# keeps the screen's pick and is counted unresolved; a group with a declined candidate past kHCap
+# picks among its scored candidates and is counted unresolved. Never a stale or foreign maze.
+def _marker(dim):
+    """A recognisable maze no generator makes: one corridor down column 1 and along the last row."""
+    g = np.zeros((dim, dim), np.uint8)
+    g[1:dim - 1, 1] = 1
+    g[dim - 2, 1:dim - 1] = 1
+    g[dim - 2, dim - 2] = 2
+    return g, (1, 1, dim - 2, dim - 2)
+
+
+def _gen_over_marker(n, dim, algo, seed, dbg):
+    """_gen, every instance holding the marker maze before the best-of-6 generation."""
+    from mazerl import VectorMazeEnv
+    env = VectorMazeEnv(n, dim, enrich=True, device="cuda:0", seed=seed, generate=False,
+                        done_list=False)
+    g, sg = _marker(dim)
+    env.load_mazes(np.repeat(g[None], n, 0), np.repeat(np.array([sg], np.int32), n, 0))
+    assert np.array_equal(env.grid(n - 1), g)
+    env.set_debug(dbg)
+    env.select_stats(reset=True)
+    env.generate(algorithm=algo, dim=dim, seed=seed, candidates=6)
+    torch.cuda.synchronize()
+    return env
+
+
+class Candidates:
+    """Candidate c of group e = instance 6 e + c of a plain env with the same seed."""
+
+    def __init__(self, n, dim, algo, seed, toroidal=False):
+        from mazerl import VectorMazeEnv
+        self.env = VectorMazeEnv(6 * n, dim, enrich=True, device="cuda:0", seed=seed,
+                                 algorithm=algo, done_list=False, toroidal=toroidal)
+        self.toroidal = toroidal
+
+    def maze(self, e, c):
+        q = self.env.query(6 * e + c)
+        return self.env.grid(6 * e + c), (q["start_r"], q["start_c"], q["goal_r"], q["goal_c"])
+
+    def which(self, e, grid, sg):
+        """The candidates of group e equal to (grid, sg)."""
+        out = []
+        for c in range(6):
+            g, s = self.maze(e, c)
+            if np.array_equal(g, grid) and tuple(s) == tuple(sg):
+                out.append(c)
+        return out
+
+    def host_difficulties(self, e):
+        from mazerl import difficulty as D
+        fn = D.toroidal_difficulty if self.toroidal else D.maze_difficulty
+        return [fn(g, s[:2], s[2:]) for g, s in (self.maze(e, c) for c in range(6))]
+
+
+def _held(env, e):
+    q = env.query(e)
+    return env.grid(e), (q["start_r"], q["start_c"], q["goal_r"], q["goal_c"])
+
+
+def test_more_groups_than_the_exact_kernel_takes_keep_the_screens_pick():
+    """300 groups, every one sent to the order-exact kernel (debug flag 1): 256 go through it, 44
+    keep the screen's pick, counted unresolved — one of the group's own six candidates, its host
+    difficulty within the screen's bound ceiling (a relative 2^-30, tests/test_screen_gpu.py) of
+    the group's minimum."""
+    from mazerl.trainers.vector_trainer import best_of_mazes
+    n, dim, seed = 300, 21, 0x0CA9E1
+    env = _gen_over_marker(n, dim, "dfs", seed, 1)
+    st = env.select_stats()
+    assert st["groups"] == 300 and st["exact"] == 256 and st["unresolved"] == 44, st
+    grids, sg, _ = best_of_mazes(n, dim, "dfs", seed=seed, device="cuda:0", candidates=6)
+    cand = Candidates(n, dim, "dfs", seed)
+    other = 0
+    for e in range(n):
+        g, s = _held(env, e)
+        if np.array_equal(g, grids[e]) and s == tuple(sg[e]):
+            continue
+        other += 1  # not the first minimum: only a group past the cap may differ
+        cs = cand.which(e, g, s)
+        assert cs, e  # a stale or foreign maze
+        d = cand.host_difficulties(e)
+        assert abs(d[cs[0]] - min(d)) <= 2.0 ** -30 * abs(min(d)), (e, cs, d)
+    assert other <= 44, other
+    env.close()
+    cand.env.close()
+
+
+def _check_host_cap(held, n_groups, unresolved, grids, sg, cand):
+    equal = 0
+    for e in range(n_groups):
+        g, s = held(e)
+        assert cand.which(e, g, s), e  # one of its own six: no stale or foreign maze
+        equal += int(np.array_equal(g, grids[e][:g.shape[0], :g.shape[1]]) and tuple(s) == tuple(sg[e]))
+    assert equal >= n_groups - unresolved, (equal, unresolved)
+
+
+def test_more_declined_candidates_than_the_host_takes():
+    """100 groups through the exact kernel with every even candidate declined (debug flags 1 | 2):
+    300 declined candidates, 256 host slots. The 44 left without a score lie in 15 .. 44 groups,
+    counted unresolved; those pick among their scored candidates, every other group is the first
+    minimum."""
+    from mazerl.trainers.vector_trainer import best_of_mazes
+    n, dim, seed = 100, 21, 0x0CA9E2
+    env = _gen_over_marker(n, dim, "dfs", seed, 3)
+    st = env.select_stats()
+    assert st["groups"] == n and st["exact"] == n and st["host_scored"] == 256, st
+    assert 15 <= st["unresolved"] <= 44, st
+    grids, sg, _ = best_of_mazes(n, dim, "dfs", seed=seed, device="cuda:0", candidates=6)
+    cand = Candidates(n, dim, "dfs", seed)
+    _check_host_cap(lambda e: _held(env, e), n, st["unresolved"], grids, sg, cand)
+    env.close()
+    cand.env.close()
+
+
+def test_more_declined_candidates_than_the_host_takes_toroidal_bank():
+    """A toroidal best-of-6 bank block of 100 slots at 17 squares (every candidate through the
+    exact kernel) with the even candidates declined (debug flag 2): 300 declined candidates per
+    block against 256 host slots, for each of the two banks' fills."""
+    from mazerl import VectorMazeEnv
+    from mazerl.trainers.vector_trainer import best_of_mazes
+    from mazerl.vector_env import ALGOS
+    B, K, dim, seed = 16, 100, 17, 0xBA4C0055
+    env = VectorMazeEnv(B, dim, enrich=True, device="cuda:0", seed=3, algorithm="dfs",
+                        done_list=False, toroidal=True)
+    env.set_debug(2)
+    env.select_stats(reset=True)
+    env.enable_bank(slots=K, swap_every=10 ** 9, algorithms=["dfs"], seed=seed, candidates=6)
+    torch.cuda.synchronize()
+    st = env.select_stats()
+    assert st["groups"] == 2 * K and st["host_scored"] == 2 * 256, st
+    assert 2 * 15 <= st["unresolved"] <= 2 * 44, st
+    equal = 0
+    for bank in (0, 1):
+        key = bank_key(seed, bank, ALGOS["dfs"])
+        grids, sg, _ = best_of_mazes(K, dim, "dfs", seed=key, device="cuda:0", candidates=6,
+                                     toroidal=True)
+        cand = Candidates(K, dim, "dfs", key, toroidal=True)
+        for j in range(K):
+            g, info = env.bank_slot(bank, "dfs", dim, j)
+            assert cand.which(j, g, info), (bank, j)
+            equal += int(np.array_equal(g, grids[j, :dim, :dim]) and info == tuple(int(x) for x in sg[j]))
+        cand.env.close()
+    assert equal >= 2 * K - st["unresolved"], (equal, st)
+    env.close()
+
+
+def test_generate_best_second_chunk():
+    """mz_generate_best works in chunks of 49,152 / C groups: 8,200 groups of 6 at 15 squares put
+    groups 8,192 .. 8,199 into a second chunk — instance e still holds the first minimum of
+    candidates 6 e .. 6 e + 5 (checked on groups 8,190 .. 8,199, across the chunk boundary)."""
+    from mazerl import VectorMazeEnv, difficulty as D
+    n, dim, seed = 8200, 15, 0x0CA9E3
+    env = VectorMazeEnv(n, dim, enrich=True, device="cuda:0", seed=seed, algorithm="dfs",
+                        done_list=False, candidates=6)
+    st = env.select_stats()
+    assert st["groups"] == n and st["unresolved"] == 0, st
+    cand = Candidates(n, dim, "dfs", seed)
+    lo = 8190
+    ids = np.arange(6 * lo, 6 * n, dtype=np.int32)
+    d = D.difficulty_batch(cand.env, ids).reshape(n - lo, 6)
+    for k, e in enumerate(range(lo, n)):
+        g, s = cand.maze(e, int(d[k].argmin()))
+        hg, hs = _held(env, e)
+        assert np.array_equal(hg, g) and hs == s, e
+    env.close()
+    cand.env.close()
