@@ -1304,6 +1304,27 @@ int mz_archive_push_pool(mz_handle* h, const uint8_t* flags_dev, int32_t capacit
                          int32_t* owner_dev, int32_t* stamp_dev, int32_t* count_dev, int32_t stamp,
                          void* stream);
 
+/* One pool per learner of a population of learners: the handle's B instances are `groups` groups
+ * of b = B / groups consecutive instances, and group g has a pool of its own — rows
+ * [g * capacity, (g + 1) * capacity) of bits_dev [groups * capacity][words], meta_dev
+ * [groups * capacity][2], algo_dev / owner_dev / stamp_dev [groups * capacity] — and a two-word
+ * counter of its own, count_dev [groups][2] (8-byte aligned). One launch appends the flagged
+ * instances of every group g (flags_dev [B], NULL: all) to pool g in ascending instance id, from
+ * entry count_dev[g][parity] on, exactly as mz_archive_push_pool would on a handle that held
+ * group g's b instances alone: owner is the instance's id within its group, i - g * b; nothing is
+ * written at or past entry `capacity` of a pool; count_dev[g][parity ^ 1] becomes
+ * min(count + flagged in group g, INT32_MAX) and count_dev[g][parity] is only read. The caller
+ * passes parity ^ 1 to its next call. groups == 1 is mz_archive_push_pool, bit for bit. No
+ * atomics and nothing exchanged between workgroups: every slot is a function of the flags alone.
+ * One launch, asynchronous, no host read. The handle's state is only read.
+ * MZ_EINVAL before any launch: a null handle or array, groups < 1, B % groups != 0,
+ * capacity < 1, words != mz_archive_words(the handle's max_dim), a count_dev that is not 8-byte
+ * aligned, a parity other than 0 or 1. */
+int mz_archive_push_pools(mz_handle* h, const uint8_t* flags_dev, int32_t groups, int32_t capacity,
+                          int32_t words, int32_t* bits_dev, int32_t* meta_dev, uint8_t* algo_dev,
+                          int32_t* owner_dev, int32_t* stamp_dev, int32_t* count_dev,
+                          int32_t parity, int32_t stamp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,9 +19,11 @@
 //                   the cell words) gathered by a wave ballot — two words per pass, lane k keeps
 //                   the ballot of pass k — and stored 8 B per lane, 512 B per wave instruction.
 //                   One writer per instance, no atomics; the handle's state is only read.
-//   k_archive_push_pool  the same entry, appended to one pool for the whole population in
-//                   instance order (its own comment below): the explored-maze pool of the DQN /
-//                   DDQN populations, mazerl.archive.MazePool.
+//   k_archive_push_pools  the same entry, appended in instance order to the pool of the
+//                   instance's group (its own comment below): with one group the explored-maze
+//                   pool of a whole population, mazerl.archive.MazePool (mz_archive_push_pool);
+//                   with G groups one pool per learner of a population of learners,
+//                   mazerl.archive.MazePoolSet (mz_archive_push_pools).
 //   k_archive_load  one wave per target: validates the entry (nothing is stored for a bad one:
 //                   it is counted in *errors), unpacks the bits into the build's LDS grid and
 //                   runs the import branch of mz_build_one with the entry's own N — the launch of
@@ -99,64 +101,76 @@ __device__ __forceinline__ int nonzero_bytes(uint32_t x) {
   return __popc(y);
 }
 
-// k_archive_push_pool — one pool for the whole population, filled in instance order.
+// k_archive_push_pools — G pools, one per group of b = B / G consecutive instances, each filled in
+// instance order (G = 1: one pool for the whole population, mz_archive_push_pool).
 //
-// Workgroup b owns the POOL_SPAN instances [b S, (b + 1) S). The slot of a flagged instance is
-// c + (flagged instances with a smaller id), so no workgroup waits for another:
-//   1. the workgroup counts the nonzero flags before its span itself (flags[0 .. b S): 16-B loads
-//      when the array is 16-B aligned, byte loads otherwise; at B = 65,536 at most 63 KB, out of
-//      L2) and reduces the count over its waves through LDS;
-//   2. it ranks its own S flags by a wave ballot, popcount of the lanes below, and a table of the
+// Group g has nblk = ceil(b / S) workgroups, S = POOL_SPAN; workgroup (g, k) = block g nblk + k
+// owns the instances [g b + k S, min(g b + (k + 1) S, (g + 1) b)) and nothing of another group:
+// with b < S one workgroup serves one small group (and is launched with ceil(b / 64) waves
+// only). The slot of a flagged instance in pool g is c_g + (flagged instances of group g with a
+// smaller id), so no workgroup waits for another:
+//   1. the workgroup counts the nonzero flags of its group before its span itself (flags[g b ..
+//      g b + k S): byte loads up to the first 16-B boundary — a group start need not be a multiple
+//      of 16 — then 16-B loads, then the bytes left; at B = 65,536 at most 63 KB, out of L2) and
+//      reduces the count over its waves through LDS;
+//   2. it ranks its own flags by a wave ballot, popcount of the lanes below, and a table of the
 //      wave counts in LDS, and writes the local ids of its flagged instances to an LDS list in
 //      rank order;
-//   3. its waves take list items in turn (wave w: items w, w + 16, ...), and pack item j into
-//      entry c + prefix + j when that is below `capacity`: anything at or past it is dropped
-//      before any address is formed. Lane 0 adds owner and stamp.
-// flags == NULL: every instance is flagged, the prefix is b S and nothing is read for it.
+//   3. its waves take list items in turn (wave w: items w, w + waves, ...), and pack item j into
+//      entry c_g + prefix + j of pool g (row g capacity + that) when that is below `capacity`:
+//      anything at or past it is dropped before any address is formed. Lane 0 adds owner — the
+//      instance's id within its group — and stamp.
+// flags == NULL: every instance is flagged, the prefix is k S and nothing is read for it.
 //
-// The count. It is a two-word counter whose parity the caller keeps: `count_in` is read by every
-// workgroup and written by none, the other word of the pair, `count_out`, is written once, by
-// the last workgroup (its prefix + its own flagged instances is |F|), as min(c + |F|, INT32_MAX).
-// Nothing is exchanged between workgroups inside the launch — no atomic, no fence, no ticket —
-// so the result cannot depend on the order in which they run, and two launches back to back on a
-// stream are ordered by the stream alone: the second reads the word the first wrote.
-__global__ __launch_bounds__(POOL_SPAN) void k_archive_push_pool(
-    MzDev d, const uint8_t* __restrict__ flags, int capacity, int words,
+// The counts. Each group has a two-word counter whose parity the caller keeps: `count_in[2 g]` is
+// read by every workgroup of the group and written by none, the other word of the pair,
+// `count_out[2 g]`, is written once, by the group's last workgroup (its prefix + its own flagged
+// instances is |F_g|), as min(c_g + |F_g|, INT32_MAX). Nothing is exchanged between workgroups
+// inside the launch — no atomic, no fence, no ticket — so the result cannot depend on the order
+// in which they run, and two launches back to back on a stream are ordered by the stream alone:
+// the second reads the words the first wrote.
+__global__ __launch_bounds__(POOL_SPAN) void k_archive_push_pools(
+    MzDev d, const uint8_t* __restrict__ flags, int b, int nblk, int capacity, int words,
     int32_t* __restrict__ bits, int32_t* __restrict__ meta, uint8_t* __restrict__ algo,
     int32_t* __restrict__ owner, int32_t* __restrict__ stamps, const int32_t* __restrict__ count_in,
     int32_t* __restrict__ count_out, int32_t stamp) {
   __shared__ int s_wave[POOL_SPAN / WAVE];      // per-wave partial sums, then per-wave flag counts
   __shared__ uint16_t s_list[POOL_SPAN];        // local ids of the flagged instances, in order
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid >> 6;
-  const int base = blockIdx.x * POOL_SPAN;      // (< B <= INT32_MAX)
-  // 1. flagged instances before this span
-  int before = base;
+  const int nthr = blockDim.x, nwav = nthr >> 6;  // (a multiple of 64, <= POOL_SPAN)
+  const int g = blockIdx.x / nblk, k = blockIdx.x - g * nblk;
+  const int gbase = g * b;                      // (< B <= INT32_MAX)
+  const int off = k * POOL_SPAN;                // this span's first instance within the group (< b)
+  // 1. flagged instances of this group before this span
+  int before = off;
   if (flags) {
+    const uint8_t* f = flags + gbase;           // f[0 .. off) lies inside the group
     int part = 0;
-    if ((reinterpret_cast<uintptr_t>(flags) & 15u) == 0) {  // base is a multiple of 16
-      const uint4* f4 = reinterpret_cast<const uint4*>(flags);
-      for (int i = tid; i < base / 16; i += POOL_SPAN) {
-        const uint4 v = f4[i];
-        part += nonzero_bytes(v.x) + nonzero_bytes(v.y) + nonzero_bytes(v.z) + nonzero_bytes(v.w);
-      }
-    } else {
-      for (int i = tid; i < base; i += POOL_SPAN) part += flags[i] != 0;
+    const int head = min(off, (int)((16u - (unsigned)(reinterpret_cast<uintptr_t>(f) & 15u)) & 15u));
+    const int body = (off - head) >> 4;         // whole 16-B words from the boundary on
+    if (tid < head) part += f[tid] != 0;
+    const uint4* f4 = reinterpret_cast<const uint4*>(f + head);
+    for (int i = tid; i < body; i += nthr) {
+      const uint4 v = f4[i];
+      part += nonzero_bytes(v.x) + nonzero_bytes(v.y) + nonzero_bytes(v.z) + nonzero_bytes(v.w);
     }
+    const int tail = head + (body << 4) + tid;  // (fewer than 16 bytes are left)
+    if (tail < off) part += f[tail] != 0;
     for (int o = WAVE / 2; o > 0; o >>= 1) part += __shfl_down(part, o);
     if (lane == 0) s_wave[wave] = part;
     __syncthreads();
     before = 0;
-    for (int w = 0; w < POOL_SPAN / WAVE; ++w) before += s_wave[w];
+    for (int w = 0; w < nwav; ++w) before += s_wave[w];
     __syncthreads();  // s_wave is reused below
   }
   // 2. rank this span's flags
-  const int e = base + tid;
-  const bool mine = e < d.B && (!flags || flags[e] != 0);
+  const int loc = off + tid;                    // id within the group
+  const bool mine = loc < b && (!flags || flags[gbase + loc] != 0);
   const unsigned long long vote = __ballot(mine);
   if (lane == 0) s_wave[wave] = __popcll(vote);
   __syncthreads();
   int woff = 0, here = 0;
-  for (int w = 0; w < POOL_SPAN / WAVE; ++w) {
+  for (int w = 0; w < nwav; ++w) {
     const int c = s_wave[w];
     if (w < wave) woff += c;
     here += c;
@@ -164,21 +178,38 @@ __global__ __launch_bounds__(POOL_SPAN) void k_archive_push_pool(
   if (mine) s_list[woff + __popcll(vote & ((1ull << lane) - 1ull))] = (uint16_t)tid;
   __syncthreads();
   // 3. pack: one wave per list item (everything below is uniform per wave)
-  const long long c0 = (long long)count_in[0] + before;  // entry of this span's first item
-  for (int j = wave; j < here; j += POOL_SPAN / WAVE) {
+  const long long c0 = (long long)count_in[2 * g] + before;  // pool entry of this span's first item
+  const size_t row0 = (size_t)g * (size_t)capacity;          // pool g's first row
+  for (int j = wave; j < here; j += nwav) {
     const long long ent = c0 + j;
     if (ent >= capacity) break;  // dropped, and so is every later item of this wave
-    const int inst = base + (int)s_list[j];
-    archive_pack_entry(d, inst, lane, words, (size_t)ent, bits, meta, algo);
+    const int local = off + (int)s_list[j];
+    const size_t row = row0 + (size_t)ent;
+    archive_pack_entry(d, gbase + local, lane, words, row, bits, meta, algo);
     if (lane == 0) {
-      owner[ent] = inst;
-      stamps[ent] = stamp;
+      owner[row] = local;
+      stamps[row] = stamp;
     }
   }
-  if (blockIdx.x == gridDim.x - 1 && tid == 0) {
-    const long long total = (long long)count_in[0] + before + here;
-    count_out[0] = (int32_t)(total > 0x7FFFFFFFll ? 0x7FFFFFFFll : total);
+  if (k == nblk - 1 && tid == 0) {
+    const long long total = (long long)count_in[2 * g] + before + here;
+    count_out[2 * g] = (int32_t)(total > 0x7FFFFFFFll ? 0x7FFFFFFFll : total);
   }
+}
+
+// The launch of k_archive_push_pools: `groups` pools of `capacity` rows over the handle's B
+// instances (B % groups == 0), group g reading count_in[2 g] and writing count_out[2 g].
+hipError_t launch_push_pools(const MzDev& d, const uint8_t* flags, int groups, int capacity,
+                             int words, int32_t* bits, int32_t* meta, uint8_t* algo,
+                             int32_t* owner, int32_t* stamps, const int32_t* count_in,
+                             int32_t* count_out, int32_t stamp, hipStream_t stream) {
+  const int b = d.B / groups;
+  const int nblk = (b + POOL_SPAN - 1) / POOL_SPAN;  // (groups nblk <= B)
+  const int threads = b < POOL_SPAN ? (b + WAVE - 1) / WAVE * WAVE : POOL_SPAN;
+  hipLaunchKernelGGL(k_archive_push_pools, dim3(groups * nblk), dim3(threads), 0, stream, d, flags,
+                     b, nblk, capacity, words, bits, meta, algo, owner, stamps, count_in, count_out,
+                     stamp);
+  return hipGetLastError();
 }
 
 __global__ __launch_bounds__(WAVE) void k_archive_load(
@@ -275,11 +306,33 @@ int mz_archive_push_pool(mz_handle* h, const uint8_t* flags_dev, int32_t capacit
   // the two-word counter: the other word of count_dev's 8-byte-aligned pair is written
   int32_t* cout = reinterpret_cast<int32_t*>(cin ^ 4u);
   MzDeviceGuard g(mz_handle_device(h));
-  hipLaunchKernelGGL(k_archive_push_pool, dim3((d.B + POOL_SPAN - 1) / POOL_SPAN), dim3(POOL_SPAN),
-                     0, static_cast<hipStream_t>(stream), d, flags_dev, capacity, words, bits_dev,
-                     meta_dev, algo_dev, owner_dev, stamp_dev,
-                     static_cast<const int32_t*>(count_dev), cout, stamp);
-  const hipError_t e = hipGetLastError();
+  const hipError_t e = launch_push_pools(d, flags_dev, 1, capacity, words, bits_dev, meta_dev,
+                                         algo_dev, owner_dev, stamp_dev,
+                                         static_cast<const int32_t*>(count_dev), cout, stamp,
+                                         static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? MZ_OK : hip_fail(e);
+}
+
+int mz_archive_push_pools(mz_handle* h, const uint8_t* flags_dev, int32_t groups, int32_t capacity,
+                          int32_t words, int32_t* bits_dev, int32_t* meta_dev, uint8_t* algo_dev,
+                          int32_t* owner_dev, int32_t* stamp_dev, int32_t* count_dev,
+                          int32_t parity, int32_t stamp, void* stream) {
+  if (!h || !bits_dev || !meta_dev || !algo_dev || !owner_dev || !stamp_dev || !count_dev)
+    return mz_fail_msg(MZ_EINVAL, "null argument");
+  const MzDev& d = mz_handle_dev(h);
+  if (groups < 1) return mz_fail_msg(MZ_EINVAL, "groups must be >= 1");
+  if (d.B % groups) return mz_fail_msg(MZ_EINVAL, "the handle's instances must divide into the groups");
+  if (capacity < 1) return mz_fail_msg(MZ_EINVAL, "capacity must be >= 1");
+  if (words != mz_archive_entry_words(d.P))
+    return mz_fail_msg(MZ_EINVAL, "words must equal mz_archive_words(the handle's max_dim)");
+  if (reinterpret_cast<uintptr_t>(count_dev) & 7u)
+    return mz_fail_msg(MZ_EINVAL, "count_dev must be 8-byte aligned");
+  if (parity != 0 && parity != 1) return mz_fail_msg(MZ_EINVAL, "parity must be 0 or 1");
+  MzDeviceGuard g(mz_handle_device(h));
+  const hipError_t e = launch_push_pools(d, flags_dev, groups, capacity, words, bits_dev, meta_dev,
+                                         algo_dev, owner_dev, stamp_dev, count_dev + parity,
+                                         count_dev + (parity ^ 1), stamp,
+                                         static_cast<hipStream_t>(stream));
   return e == hipSuccess ? MZ_OK : hip_fail(e);
 }
 

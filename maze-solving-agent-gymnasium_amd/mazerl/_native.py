@@ -63,7 +63,7 @@ EXPORTS = ["mz_last_error", "mz_device_count", "mz_create", "mz_destroy", "mz_lo
            "mz_dqtab_act", "mz_dqtab_update", "mz_dqtab_hash_act", "mz_dqtab_hash_update",
            "mz_dqtab_hash_rehash", "mz_dqtab_hash_lookup",
            "mz_archive_words", "mz_archive_push", "mz_archive_load",
-           "mz_archive_pool_span", "mz_archive_push_pool",
+           "mz_archive_pool_span", "mz_archive_push_pool", "mz_archive_push_pools",
            "mz_cae_decode", "mz_cae_loss", "mz_cae_workspace_floats"]
 
 _lib = None
@@ -252,6 +252,8 @@ def load(build_if_missing=True):
     L.mz_archive_pool_span.argtypes = [c_i32p]
     L.mz_archive_push_pool.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp,
                                        C.c_int32, vp]
+    L.mz_archive_push_pools.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp,
+                                        vp, C.c_int32, C.c_int32, vp]
     L.mz_host_alloc.argtypes = [C.c_uint64, C.c_int32, C.POINTER(vp), C.POINTER(vp)]
     L.mz_host_free.argtypes = [vp]
     for f in EXPORTS:

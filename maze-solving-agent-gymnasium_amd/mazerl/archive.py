@@ -12,6 +12,9 @@ asynchronous launch with no host copy, exactly as load_mazes would build it.
 The ring keeps the newest `slots` entries of an instance where the reference keeps all of them:
 size `slots` for the wins expected and report `dropped`.
 
+MazePool is one list for a whole population in exploration order (a learner that trains on B envs
+at once), MazePoolSet one such list per learner of a population of learners, filled by one launch.
+
 All archive memory is torch tensors owned by this object (the env handle keeps no pointer to
 it), so an archive outlives its env, is saved by state_dict() and loads into another handle.
 """
@@ -22,6 +25,7 @@ from . import _native as N
 
 _FORMAT = "mazerl.MazeArchive/1"
 _POOL_FORMAT = "mazerl.MazePool/1"
+_POOLS_FORMAT = "mazerl.MazePoolSet/1"
 
 
 def archive_words(max_dim):
@@ -344,6 +348,172 @@ class MazePool:
         for k in self._TENSORS:
             getattr(self, k).copy_(sd[k])
         self._count2[self._cur:self._cur + 1].copy_(sd["count"])
+
+
+class MazePoolSet:
+    """One MazePool per learner of a population of learners that share an env: the env's B
+    instances are `groups` blocks of b = B / groups consecutive instances, and block g has a pool
+    of `capacity` entries of its own — rows [g C, (g + 1) C) of the arrays below and a counter of
+    its own. record() fills all of them in ONE launch (mz_archive_push_pools). Pool g is, bit for
+    bit, the MazePool of an env that holds block g's instances alone: its owners are the ids
+    within the block."""
+
+    def __init__(self, env, groups, capacity):
+        """bits int32 [G C, W], meta int32 [G C, 2], algo uint8 / owner int32 / stamp int32 [G C],
+        the counts int32 [G] (entries offered to each pool so far) and errors int32 [1] (entries
+        load() refused, over all pools; never cleared here)."""
+        groups, capacity = int(groups), int(capacity)
+        if groups < 1 or env.num_envs % groups:
+            raise ValueError(f"the env's {env.num_envs} instances must divide into groups "
+                             f"{groups} >= 1")
+        if capacity < 1:
+            raise ValueError("capacity must be >= 1")
+        self.env, self.lib, self.device = env, env.lib, env.device
+        self.groups, self.capacity, self.pitch = groups, capacity, env.max_dim
+        self.block = env.num_envs // groups
+        self.toroidal = bool(getattr(env, "toroidal", False))
+        self.enrich = bool(getattr(env, "enrich", False))
+        self.words = archive_words(self.pitch)
+        R, dev = groups * capacity, self.device
+        self.bits = torch.zeros(R, self.words, dtype=torch.int32, device=dev)
+        self.meta = torch.zeros(R, 2, dtype=torch.int32, device=dev)
+        self.algo = torch.zeros(R, dtype=torch.uint8, device=dev)
+        self.owner = torch.zeros(R, dtype=torch.int32, device=dev)
+        self.stamp = torch.zeros(R, dtype=torch.int32, device=dev)
+        # every pool's two-word counter: a call reads word _cur of each pair and writes the other
+        self._count2 = torch.zeros(groups, 2, dtype=torch.int32, device=dev)
+        self._cur = 0
+        self.errors = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    # -------------------------------------------------------------------------------------------
+    def record(self, flags=None, stamp=0):
+        """env.mazes.append(maze) of every learner: the instances with flags != 0 (None: all) go
+        to their block's pool, in ascending id, each stamped `stamp`: one launch on the current
+        stream for all pools, no host read."""
+        f = None
+        if flags is not None:
+            f = flags.to(device=self.device, dtype=torch.uint8).contiguous()
+            if f.numel() != self.env.num_envs:
+                raise ValueError("one flag per instance")
+        N.check(self.lib.mz_archive_push_pools(
+            self.env._h, None if f is None else f.data_ptr(), self.groups, self.capacity,
+            self.words, self.bits.data_ptr(), self.meta.data_ptr(), self.algo.data_ptr(),
+            self.owner.data_ptr(), self.stamp.data_ptr(), self._count2.data_ptr(), self._cur,
+            int(stamp), self._stream()))
+        self._cur ^= 1
+
+    def load(self, env, slot, env_ids=None):
+        """MazePool.load over all pools: slot[j] is a linear row, g C + k for pool g's entry k
+        (negative: left alone), so one launch fills an env from every pool. The caller keeps
+        k < held[g]."""
+        _load_entries(self, env, slot, env_ids)
+
+    def pool(self, g):
+        """Pool g through MazePool's reading interface (views of this set's arrays: bits, meta,
+        algo, owner, stamp, count, held, dropped, errors, load, to_mazes, state_dict), for
+        evaluate_explored; record() stays the set's."""
+        g = int(g)
+        if g < 0 or g >= self.groups:
+            raise ValueError(f"pool {g} of {self.groups}")
+        return _PoolOfSet(self, g)
+
+    # -------------------------------------------------------------------------------------------
+    @property
+    def count(self):
+        """Entries offered to each pool so far (int32 [G] device tensor; saturates at 2^31 - 1)."""
+        return self._count2[:, self._cur]
+
+    @property
+    def held(self):
+        """Entries each pool holds: min(count, capacity)."""
+        return self.count.clamp(max=self.capacity)
+
+    @property
+    def dropped(self):
+        """Entries offered to each pool after it was full: max(count - capacity, 0)."""
+        return (self.count - self.capacity).clamp(min=0)
+
+    # -------------------------------------------------------------------------------------------
+    _TENSORS = MazePool._TENSORS
+    _GEOMETRY = ("pitch", "capacity", "groups", "toroidal", "enrich")
+
+    def state_dict(self):
+        sd = {k: getattr(self, k).clone() for k in self._TENSORS}
+        sd["count"] = self.count.clone()
+        sd.update(format=_POOLS_FORMAT, **{k: getattr(self, k) for k in self._GEOMETRY})
+        return sd
+
+    def check_state_dict(self, sd):
+        """ValueError unless `sd` is a state_dict() of a set of this pitch, capacity, group count
+        and geometry (nothing is changed)."""
+        if not isinstance(sd, dict) or sd.get("format") != _POOLS_FORMAT:
+            raise ValueError("not a MazePoolSet state_dict")
+        for k in self._GEOMETRY:
+            if k not in sd or int(sd[k]) != int(getattr(self, k)):
+                raise ValueError(f"the saved set's {k} {sd.get(k)} differs from this set's "
+                                 f"{getattr(self, k)}")
+        for k in self._TENSORS + ("count",):
+            want = (self.groups,) if k == "count" else tuple(getattr(self, k).shape)
+            if k not in sd or not torch.is_tensor(sd[k]) or tuple(sd[k].shape) != want or \
+                    sd[k].dtype != (torch.int32 if k == "count" else getattr(self, k).dtype):
+                raise ValueError(f"the saved set's {k} has another shape or type")
+
+    def load_state_dict(self, sd):
+        self.check_state_dict(sd)
+        for k in self._TENSORS:
+            getattr(self, k).copy_(sd[k])
+        self._count2[:, self._cur].copy_(sd["count"])
+
+
+class _PoolOfSet(MazePool):
+    """MazePoolSet.pool(g): a MazePool whose arrays are the set's rows [g C, (g + 1) C) and whose
+    counter is the set's pair g (read when used, so the view follows the set's record() calls)."""
+
+    def __init__(self, pools, g):
+        s, C = pools, pools.capacity
+        self._set, self.group = s, g
+        self.env, self.lib, self.device = s.env, s.lib, s.device
+        self.capacity, self.pitch, self.words = C, s.pitch, s.words
+        self.toroidal, self.enrich = s.toroidal, s.enrich
+        for k in ("bits", "meta", "algo", "owner", "stamp"):
+            setattr(self, k, getattr(s, k)[g * C:(g + 1) * C])
+        self.errors = s.errors
+
+    @property
+    def _count2(self):
+        return self._set._count2[self.group]
+
+    @property
+    def _cur(self):
+        return self._set._cur
+
+    def record(self, flags=None, stamp=0):
+        raise TypeError("a pool of a MazePoolSet is filled by the set's record()")
+
+
+def add_pool_arguments(ap, what="the run"):
+    """--archive C and --explored-mazes N of the episodic trainers' command lines (mazerl.train's
+    options and defaults: 0 = off, N default every held entry)."""
+    ap.add_argument("--archive", type=int, default=0,
+                    help=f"C > 0: keep the first C mazes {what} trains on (every instance's first "
+                         "maze, then each winner's new one) in a MazePool and report the win rate "
+                         "on them, the reference's test(n, new=False); 0 = off")
+    ap.add_argument("--explored-mazes", type=int, default=None,
+                    help="N: replay the pool's oldest N entries (default: all held; at most held)")
+
+
+def check_pool_arguments(a):
+    """mazerl.train's refusals of the two options, raised before any GPU call."""
+    if a.archive < 0:
+        raise ValueError("--archive must be >= 0")
+    if a.explored_mazes is not None:
+        if a.explored_mazes < 1:
+            raise ValueError("--explored-mazes must be >= 1")
+        if not a.archive:
+            raise ValueError("--explored-mazes replays the pool: it needs --archive")
 
 
 def instance_algorithms(env):

@@ -26,13 +26,21 @@ their mean and spread, and every learner's window settings.
 
 With --learners, --window T is shared by the population (it fixes the layouts and cannot be
 swept); --burn-in and --initial-state are per learner.
+
+--archive C keeps the mazes the run trains on in a MazePool of C entries (with --learners: one
+pool of C entries per learner, all filled by one launch per vector step) and the final line gains
+the greedy win rate on its oldest --explored-mazes entries, the reference's test(n, new=False)
+(per learner, with the spread), and the pool's fill.
 """
 import argparse
 import json
 
 import torch
 
+from .archive import add_pool_arguments, check_pool_arguments
 from .trainers.drqn_trainer import VectorRecurrentDQNTrainer, check_window, evaluate_plain
+from .trainers.episodic import episode_bound
+from .trainers.vector_trainer import evaluate_explored
 from .vector_env import VectorMazeEnv
 
 
@@ -122,7 +130,9 @@ def parse_args(argv=None):
                     help="per-learner values (P or one) of lr, gamma, eps-start, eps-final, "
                          "eps-decay, target-update or seed; repeatable")
     ap.add_argument("--seeds", default=None, metavar="s1,s2,...", help="--sweep seed=...")
+    add_pool_arguments(ap, "the run (with --learners: each learner)")
     a = ap.parse_args(argv)
+    check_pool_arguments(a)  # refused here, before any GPU call
     try:
         check_window(a.window, a.burn_in, a.initial_state)
     except ValueError as e:
@@ -156,7 +166,7 @@ def main_population(a):
     tr = VectorRecurrentDQNPopulation(
         env, dev, learners=a.learners, batch_size=a.batch, memory_size=a.memory,
         explore_actions=a.explore_actions, train_every=a.train_every, bank=not a.no_bank,
-        algorithm=a.algo, window=a.window, **kw)
+        algorithm=a.algo, window=a.window, archive=a.archive or None, **kw)
     if a.resume:
         from .checkpoint import load_checkpoint
         load_checkpoint(a.resume, tr)
@@ -167,6 +177,13 @@ def main_population(a):
         from .checkpoint import save_checkpoint
         save_checkpoint(a.save, tr)
     after = tr.evaluate_all(a.eval_mazes, a.dim, **ev)
+    explored = {}
+    if tr.archive is not None:  # every learner on its own oldest n mazes, n the same for all
+        n = min(a.explored_mazes or tr.archive.capacity, min(tr.archive.held.tolist()))
+        rates = tr.evaluate_explored_all(n)
+        explored = {"win_rate_explored_greedy": rates,
+                    "win_rate_explored_greedy_spread": spread(rates), "explored_mazes": n,
+                    "archive": tr.summary()["archive"]}
     print(json.dumps({"config": "lstm-dqn population " + ("toroidal" if a.toroidal else "euclidean"),
                       "envs": a.envs, "learners": a.learners, "dim": a.dim,
                       "vector_steps": a.steps, "train_seconds": secs,
@@ -176,7 +193,8 @@ def main_population(a):
                       "window": tr._window_settings(),  # T and every learner's K_p, S_p
                       "replay_bytes": tr.memory_bytes()["replay"],
                       "win_rate_greedy_untrained": before, "win_rate_greedy": after,
-                      "win_rate_greedy_spread": spread(after), "eval_mazes": a.eval_mazes}),
+                      "win_rate_greedy_spread": spread(after), "eval_mazes": a.eval_mazes,
+                      **explored}),
           flush=True)
     env.close()
 
@@ -194,7 +212,7 @@ def main(argv=None):
         memory_size=a.memory, target_update_frequency=a.target_update,
         explore_actions=a.explore_actions, train_every=a.train_every, seed=a.seed,
         bank=not a.no_bank, algorithm=a.algo, window=a.window, burn_in=a.burn_in,
-        initial_state=a.initial_state)
+        initial_state=a.initial_state, archive=a.archive or None)
     if a.resume:
         from .checkpoint import load_checkpoint
         load_checkpoint(a.resume, tr)
@@ -205,6 +223,14 @@ def main(argv=None):
         from .checkpoint import save_checkpoint
         save_checkpoint(a.save, tr)
     after, k = evaluate_plain(tr.evaluator(), a.eval_mazes, a.dim, **kw)
+    explored = {}
+    if tr.archive is not None:
+        pool = tr.archive
+        n = min(a.explored_mazes or pool.capacity, int(pool.held))
+        xg, _ = evaluate_explored(tr.evaluator(), pool, n, chunk=min(n, a.envs), seed=0x7E590000,
+                                  max_vector_steps=episode_bound(pool.pitch, pool.toroidal) + 1)
+        explored = {"win_rate_explored_greedy": xg, "explored_mazes": n,
+                    "archive": tr.summary()["archive"]}
     print(json.dumps({"config": "lstm-dqn " + ("toroidal" if a.toroidal else "euclidean"),
                       "envs": a.envs, "dim": a.dim, "vector_steps": a.steps, "train_seconds": secs,
                       "train_env_steps_per_s": a.envs * a.steps / secs, "episodes": tr.episodes,
@@ -212,7 +238,8 @@ def main(argv=None):
                       "seed": a.seed, "window": a.window, "burn_in": a.burn_in,
                       "initial_state": a.initial_state if a.window else None,
                       "win_rate_greedy_untrained": before,
-                      "win_rate_greedy": after, "eval_mazes": a.eval_mazes, "eval_steps": k}),
+                      "win_rate_greedy": after, "eval_mazes": a.eval_mazes, "eval_steps": k,
+                      **explored}),
           flush=True)
     env.close()
 

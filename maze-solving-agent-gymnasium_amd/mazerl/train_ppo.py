@@ -5,18 +5,22 @@
 
 Instance i (global id) gets grid size dims[i % len(dims)]; N = 15 (reference crash Q8) is not in
 the range. Prints one JSON line with training throughput and the greedy win-rate on fresh mazes.
+With --archive C every rank keeps the mazes it trains on in a MazePool of C entries and the line
+gains the win rate on them, the reference's PPOTrainer.test(n, new=False), with the pool's fill.
 """
 import argparse
 import json
 
 import torch
 
+from .archive import add_pool_arguments, check_pool_arguments
 from .distributed import GradAllReduce, allreduce_sum, broadcast_params, init_from_env
+from .trainers.episodic import episode_bound
 from .trainers.ppo_trainer import VectorPPOTrainer
-from .trainers.vector_trainer import best_of_mazes, evaluate, make_env
+from .trainers.vector_trainer import best_of_mazes, evaluate, evaluate_explored, make_env
 
 
-def main(argv=None):
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--dims", default="17-79", help="odd range lo-hi or comma list")
@@ -44,7 +48,14 @@ def main(argv=None):
     ap.add_argument("--resume", default=None, help="checkpoint to continue from (<path>.rank<r> "
                                                     "per rank when world > 1)")
     ap.add_argument("--save", default=None, help="checkpoint written after training")
+    add_pool_arguments(ap, "a rank")
     a = ap.parse_args(argv)
+    check_pool_arguments(a)  # refused here, before any GPU call
+    return a
+
+
+def main(argv=None):
+    a = parse(argv)
     if "-" in a.dims:
         lo, hi = (int(x) for x in a.dims.split("-"))
         dims = [n for n in range(lo, hi + 1, 2)]
@@ -62,7 +73,8 @@ def main(argv=None):
                           pool_size=a.pool, seed=a.seed + 7919 * rank, use_graph=not a.eager_update,
                           bank=not a.no_bank, curriculum=None if a.curriculum == "none" else a.curriculum,
                           growth=growth, algorithm=a.algo, bank_candidates=a.candidates,
-                          allreduce=GradAllReduce() if world > 1 else None)
+                          allreduce=GradAllReduce() if world > 1 else None,
+                          archive=a.archive or None)
     if world > 1:
         broadcast_params(tr.net)
     ck = (lambda p: p if world == 1 else f"{p}.rank{rank}")  # noqa: E731
@@ -75,6 +87,19 @@ def main(argv=None):
         from .checkpoint import save_checkpoint
         save_checkpoint(ck(a.save), tr)
     st = allreduce_sum(torch.tensor([tr.episodes, tr.wins], dtype=torch.float64, device=dev))
+    explored = {}
+    if tr.archive is not None:
+        # every rank replays its own pool; the (won, played) counts and fills are summed over ranks
+        pool = tr.archive
+        n = min(a.explored_mazes or pool.capacity, int(pool.held))
+        xg, _ = evaluate_explored(tr, pool, n, eps=0.0, chunk=min(n, a.envs), seed=0x7E590000,
+                                  max_vector_steps=episode_bound(pool.pitch, pool.toroidal) + 1)
+        fill = tr.summary()["archive"]
+        cnt = allreduce_sum(torch.tensor([round(xg * n), n, fill["recorded"], fill["held"],
+                                          fill["dropped"]], dtype=torch.float64, device=dev)).tolist()
+        explored = {"win_rate_explored_greedy": cnt[0] / cnt[1], "explored_mazes": int(cnt[1]),
+                    "archive": {"capacity": pool.capacity * world, "recorded": int(cnt[2]),
+                                "held": int(cnt[3]), "dropped": int(cnt[4])}}
     if rank == 0:
         rate, k = evaluate(tr, a.eval_mazes, dims, a.algo, seed=0x7E570000, eps=0.0, toroidal=True,
                            device=dev)
@@ -91,7 +116,7 @@ def main(argv=None):
                           "win_rate_greedy": rate, "win_rate_greedy_best_of_6": rate6,
                           "candidates": a.candidates, "stopped_at": tr.stopped_at,
                           "schedule": tr.schedule.summary() if tr.schedule is not None else None,
-                          "eval_mazes": a.eval_mazes, "eval_steps": k}), flush=True)
+                          "eval_mazes": a.eval_mazes, "eval_steps": k, **explored}), flush=True)
     env.close()
 
 

@@ -8,19 +8,23 @@ Every instance starts at the growth's first size (15: SimpleVariableMazeEnv.STAR
 smallest euclidean maze that holds the 15x15 window) and grows by 4 per win (--growth START,MAX);
 --growth none keeps fixed per-instance sizes from --dims. Prints one JSON line with the training
 throughput and the win-rate on fresh mazes, sampled at temperature 2 (the reference's own test())
-and greedy (argmax of the logits).
+and greedy (argmax of the logits). With --archive C the run keeps the mazes it trains on in a
+MazePool of C entries and the line gains both win rates on them, the reference's
+ValueBasedTrainer.test(n, new=False), with the pool's fill.
 """
 import argparse
 import json
 
 import torch
 
+from .archive import add_pool_arguments, check_pool_arguments
+from .trainers.episodic import episode_bound
 from .trainers.reinforce_trainer import VectorReinforceTrainer
 from .trainers.schedule import growth_sizes
-from .trainers.vector_trainer import evaluate, make_env
+from .trainers.vector_trainer import evaluate, evaluate_explored, make_env
 
 
-def main(argv=None):
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--growth", default="15,35",
@@ -48,11 +52,18 @@ def main(argv=None):
                     help="build winners' new mazes inline instead of copying them from a maze bank")
     ap.add_argument("--resume", default=None, help="checkpoint to continue from")
     ap.add_argument("--save", default=None, help="checkpoint written after training")
+    add_pool_arguments(ap)
     a = ap.parse_args(argv)
+    check_pool_arguments(a)  # refused here, before any GPU call
+    if a.dims is None and a.growth in ("none", ""):
+        ap.error("--growth none needs --dims")
+    return a
+
+
+def main(argv=None):
+    a = parse(argv)
     growth = None if a.growth in ("none", "") else tuple(int(x) for x in a.growth.split(","))
     if a.dims is None:
-        if growth is None:
-            ap.error("--growth none needs --dims")
         dims = growth_sizes(*growth)
     elif "-" in a.dims:
         lo, hi = (int(x) for x in a.dims.split("-"))
@@ -68,7 +79,8 @@ def main(argv=None):
                                 batch_size=a.batch, temperature=a.temperature,
                                 entropy_coef=a.entropy_coef, seed=a.seed, bank=not a.no_bank,
                                 curriculum=None if a.curriculum == "none" else a.curriculum,
-                                growth=growth, algorithm=a.algo, bank_candidates=a.candidates)
+                                growth=growth, algorithm=a.algo, bank_candidates=a.candidates,
+                                archive=a.archive or None)
     if a.resume:
         from .checkpoint import load_checkpoint
         load_checkpoint(a.resume, tr)
@@ -80,6 +92,16 @@ def main(argv=None):
     kw = dict(toroidal=a.toroidal, device=dev, eps=0.0)
     sampled, k = evaluate(tr.sampler(), a.eval_mazes, dims, a.algo, seed=0x7E570000, **kw)
     greedy, _ = evaluate(tr, a.eval_mazes, dims, a.algo, seed=0x7E570000, **kw)
+    explored = {}
+    if tr.archive is not None:
+        pool = tr.archive
+        n = min(a.explored_mazes or pool.capacity, int(pool.held))
+        xkw = dict(eps=0.0, chunk=min(n, a.envs), seed=0x7E590000,
+                   max_vector_steps=episode_bound(pool.pitch, pool.toroidal) + 1)
+        xs, _ = evaluate_explored(tr.sampler(), pool, n, **xkw)
+        xg, _ = evaluate_explored(tr, pool, n, **xkw)
+        explored = {"win_rate_explored_sample": xs, "win_rate_explored_greedy": xg,
+                    "explored_mazes": n, "archive": tr.summary()["archive"]}
     print(json.dumps({"config": "reinforce " + ("toroidal" if a.toroidal else "euclidean") +
                       (" variable" if growth else ""), "envs": a.envs, "growth": growth,
                       "dims": [dims[0], dims[-1]], "vector_steps": steps, "train_seconds": secs,
@@ -89,7 +111,7 @@ def main(argv=None):
                       "win_rate_sampled": sampled, "win_rate_greedy": greedy,
                       "stopped_at": tr.stopped_at,
                       "schedule": tr.schedule.summary() if tr.schedule is not None else None,
-                      "eval_mazes": a.eval_mazes, "eval_steps": k}), flush=True)
+                      "eval_mazes": a.eval_mazes, "eval_steps": k, **explored}), flush=True)
     env.close()
 
 

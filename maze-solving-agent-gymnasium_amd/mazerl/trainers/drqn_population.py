@@ -129,7 +129,10 @@ class VectorRecurrentDQNPopulation(RecurrentDQNBase):
                  epsilon_decay=1000.0, discount_factor=0.99, batch_size=32, memory_size=20000,
                  target_update_frequency=10, explore_actions=4, train_every=1, seed=0, bank=True,
                  curriculum=False, growth=None, algorithm="r-prim", bank_candidates=1, window=None,
-                 burn_in=0, initial_state="stored"):
+                 burn_in=0, initial_state="stored", archive=None):
+        """archive (None: off): an int C or a MazePoolSet of this env with one group per learner
+        — every learner's explored mazes in a pool of C entries of its own, all filled by one
+        launch per vector step (evaluate_explored_all)."""
         P = int(learners)
         if P < 1 or env.num_envs % P:
             raise ValueError(f"env.num_envs {env.num_envs} must be a multiple of learners {P} >= 1")
@@ -173,7 +176,8 @@ class VectorRecurrentDQNPopulation(RecurrentDQNBase):
                     f"{need['total'] / 2 ** 30:.2f} GiB in all; {free / 2 ** 30:.2f} GiB are free. "
                     "Lower memory_size or learners.")
         super().__init__(env, device, bank=bank, curriculum=curriculum, growth=growth,
-                         algorithm=algorithm, bank_candidates=bank_candidates)
+                         algorithm=algorithm, bank_candidates=bank_candidates, archive=archive,
+                         archive_groups=P)
         kw = dict(device=self.device)
         i32, i64, f32 = torch.int32, torch.int64, torch.float32
         self.src = torch.zeros(P, PARAMS, dtype=f32, **kw)
@@ -257,6 +261,15 @@ class VectorRecurrentDQNPopulation(RecurrentDQNBase):
             ids = torch.arange(p * n, (p + 1) * n, dtype=torch.int32, device=self.device)
             env.generate(env_ids=ids, algorithm=algorithm, seed=(seed - p * n) & U64)
         env.reset()
+        won = self._greedy_blocks(env, n, episode_bound(dim, toroidal) + 1)
+        rates = won.view(P, n).float().mean(dim=1).tolist()
+        env.close()
+        return rates
+
+    def _greedy_blocks(self, env, n, limit):
+        """One greedy episode per row of `env`, P blocks of n rows, block p played by learner p
+        from zero state through the population act in evaluation mode. Returns the rows that won."""
+        P = self.P
         kw = dict(device=self.device)
         h = torch.zeros(HIDDEN, P * n, dtype=torch.float32, **kw)
         c = torch.zeros_like(h)
@@ -273,10 +286,38 @@ class VectorRecurrentDQNPopulation(RecurrentDQNBase):
             t.fill_(1)
             return acts
 
-        won, _ = self.greedy_rollout(env, act, episode_bound(dim, toroidal) + 1)
-        rates = won.view(P, n).float().mean(dim=1).tolist()
+        won, _ = self.greedy_rollout(env, act, limit)
+        return won
+
+    def evaluate_explored_all(self, n=None):
+        """The reference's test(n, new=False) for every learner at once: the P greedy win-rates
+        on each learner's own oldest n explored mazes (entries 0 .. n - 1 of its pool; n None: the
+        smallest `held` over the learners), from one rollout of P n rows — block p filled from
+        pool p by one load launch — through the population act in evaluation mode. Learner p's
+        rate is evaluate_explored(self.evaluator(p), self.archive.pool(p), n)'s. An entry the load
+        refuses raises a RuntimeError (a corrupt pool: the result is void)."""
+        from ..vector_env import VectorMazeEnv
+        pools = self.archive
+        if pools is None:
+            raise ValueError("this population keeps no explored-maze pools (archive=)")
+        P, C = self.P, pools.capacity
+        low = min(pools.held.tolist())
+        n = low if n is None else int(n)
+        if n < 1 or n > low:
+            raise ValueError(f"n = {n}: the emptiest pool holds {low} entries")
+        env = VectorMazeEnv(P * n, pools.pitch, toroidal=pools.toroidal, enrich=False,
+                            device=self.device, pos=False, done_list=False)
+        k = torch.arange(P * n, dtype=torch.int32, device=self.device)
+        pools.load(env, (k // n) * C + k % n)  # row p n + j <- pool p's entry j
+        env.reset()
+        won = self._greedy_blocks(env, n, episode_bound(pools.pitch, pools.toroidal) + 1)
+        wins = won.view(P, n).sum(dim=1)
+        *wins, refused = torch.cat([wins, pools.errors.to(wins.dtype)]).tolist()
         env.close()
-        return rates
+        if refused:
+            raise RuntimeError(f"{refused} pool entries were refused by mz_archive_load "
+                               f"(errors): a pool is corrupt, the result is void")
+        return [w / n for w in wins]
 
     # ---- a vector step --------------------------------------------------------------------------
     def _act(self):

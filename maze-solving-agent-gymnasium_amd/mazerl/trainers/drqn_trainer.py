@@ -215,14 +215,15 @@ class VectorRecurrentDQNTrainer(RecurrentDQNBase):
                  epsilon_decay=1000.0, discount_factor=0.99, batch_size=32, memory_size=20000,
                  target_update_frequency=10, explore_actions=4, train_every=1, seed=0, bank=True,
                  curriculum=False, growth=None, algorithm="r-prim", bank_candidates=1, window=None,
-                 burn_in=0, initial_state="stored"):
+                 burn_in=0, initial_state="stored", archive=None):
+        """archive: EpisodicTrainer's explored-maze pool (None: off)."""
         check_window(window, burn_in, initial_state)
         if batch_size < 1 or memory_size < batch_size or train_every < 1 or \
                 target_update_frequency < 1 or explore_actions not in (1, 2, 3, 4):
             raise ValueError("batch_size >= 1, memory_size >= batch_size, train_every >= 1, "
                              "target_update_frequency >= 1, explore_actions in 1..4")
         super().__init__(env, device, bank=bank, curriculum=curriculum, growth=growth,
-                         algorithm=algorithm, bank_candidates=bank_candidates)
+                         algorithm=algorithm, bank_candidates=bank_candidates, archive=archive)
         torch.manual_seed(seed)
         self.source_net = DQN(6, 4, HIDDEN, self.device)
         self.target_net = DQN(6, 4, HIDDEN, self.device)

@@ -16,6 +16,7 @@ import time
 import torch
 
 from .. import _native as N
+from ..archive import MazePool, MazePoolSet
 from .schedule import enable_winner_bank, make_schedule, max_shape_stop, reset_winners
 
 
@@ -36,6 +37,27 @@ def episode_bound(max_dim, toroidal):
     return best
 
 
+def attach_pool(env, archive, groups=None):
+    """A trainer's archive= argument -> its explored-maze pool: an int capacity C makes a
+    MazePool(env, C), or with `groups` (a population of learners) a MazePoolSet(env, groups, C), C
+    per learner; a pool or pool set of this env is taken as it is. ValueError for another env's,
+    for a pool where a set is needed (or the reverse) and for a set of another group count."""
+    if isinstance(archive, (MazePool, MazePoolSet)):
+        if archive.env is not env:
+            raise ValueError("the pool was built for another env")
+        if groups is None and type(archive) is not MazePool:
+            raise ValueError("this trainer keeps one MazePool (a population of learners keeps a "
+                             "MazePoolSet)")
+        if groups is not None and not (isinstance(archive, MazePoolSet) and
+                                       archive.groups == groups):
+            raise ValueError(f"a population of {groups} learners keeps a MazePoolSet of {groups} "
+                             "groups")
+        return archive
+    if isinstance(archive, bool) or not isinstance(archive, int):
+        raise ValueError("archive: None, an int capacity, or a MazePool / MazePoolSet of this env")
+    return MazePool(env, archive) if groups is None else MazePoolSet(env, groups, archive)
+
+
 class EpisodicTrainer:
     """A subclass sets _FORMAT (the checkpoint's format string), _SHAPE (the attributes a
     checkpoint must match), _REC (its record buffers, [B, >= L, ...]) and _COUNTERS (its host
@@ -43,10 +65,15 @@ class EpisodicTrainer:
     _SHAPE = ("L",)
 
     def __init__(self, env, device, bank=True, curriculum=False, growth=None, algorithm="r-prim",
-                 bank_candidates=1):
+                 bank_candidates=1, archive=None, archive_groups=None):
         """curriculum (False | True / "global" | "per-instance"), growth ((start, max_dim): the
         variable-size envs' +4 per win and the max-shape stop), algorithm (the initial mazes'),
-        bank_candidates (best-of-C replacement mazes): schedule.py, VectorOffPolicyTrainer."""
+        bank_candidates (best-of-C replacement mazes): schedule.py, VectorOffPolicyTrainer.
+        archive (None: off — no launch, no tensor, no checkpoint key more than before): an int C
+        or a pool of this env (attach_pool) — the explored mazes, `env.mazes`, for
+        evaluate_explored: every instance's first maze now, then each winner's new one
+        (_reset_winners; one more launch and one flag copy per vector step). archive_groups: the
+        learners of a population, each with a pool of its own."""
         self.env = env
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -67,6 +94,10 @@ class EpisodicTrainer:
         # episodes, wins, dropped 1-step episodes, record-buffer overflows (an error at update)
         self.stats = torch.zeros(4, dtype=torch.int64, **kw)
         self.lib = N.load()
+        self.archive = None
+        if archive is not None:
+            self.archive = attach_pool(env, archive, archive_groups)
+            self.archive.record(stamp=0)  # the first mazes (simple_maze_env.py:34)
 
     @property
     def supports_bits(self):
@@ -105,8 +136,37 @@ class EpisodicTrainer:
 
     def _reset_winners(self):
         """change_algorithm for the winners, the reset (winners get new mazes, truncated
-        instances restart theirs), update_maze's sizes and the max-shape retirements."""
-        return reset_winners(self.env, self.schedule)
+        instances restart theirs), update_maze's sizes and the max-shape retirements; with a
+        pool, env.mazes.append(maze) for the winners' new mazes (simple_maze_env.py:91), stamped
+        with the act counter after this step's act."""
+        arch, env = self.archive, self.env
+        if arch is None:
+            return reset_winners(env, self.schedule)
+        # the winners that will receive a new maze (the reset clears the flags): all of them, or
+        # under per-instance sizes those whose next size is not 0 (update_maze past max_shape
+        # appends nothing)
+        rd = env._regen_dims
+        new_maze = env.terminated.clone() if rd is None else \
+            (env.terminated.bool() & (rd > 0)).to(torch.uint8)
+        won = reset_winners(env, self.schedule)
+        arch.record(new_maze, stamp=self.counter)
+        return won
+
+    def summary(self):
+        """Host-side counts (synchronises): the vector steps, the max-shape stop, the win
+        schedule's summary and the pool's fill — capacity, recorded, held, dropped; a population's
+        set reports the last three per learner."""
+        out = {"vector_steps": self.counter, "stopped_at": self.stopped_at,
+               "schedule": None if self.schedule is None else self.schedule.summary(),
+               "archive": None}
+        a = self.archive
+        if a is not None:
+            count, held, dropped = torch.stack([a.count, a.held, a.dropped]).tolist()
+            out["archive"] = {"capacity": a.capacity, "recorded": count, "held": held,
+                              "dropped": dropped}
+            if isinstance(a, MazePoolSet):
+                out["archive"]["learners"] = a.groups
+        return out
 
     def _train_step(self, k, n):
         self.vector_step()
@@ -136,13 +196,25 @@ class EpisodicTrainer:
         [B, L] buffers), the counters and the env."""
         torch.cuda.synchronize(self.device)
         live = self._live()
-        return {"format": self._FORMAT, **{k: getattr(self, k) for k in self._SHAPE},
-                "schedule": None if self.schedule is None else self.schedule.state_dict(),
-                "t": self.t.clone(),
-                "records": {k: getattr(self, k)[:, :self.L][live] for k in self._REC},
-                "stats": self.stats.clone(),
-                "counters": {k: getattr(self, k) for k in self._COUNTERS},
-                "env": self.env.state_dict()}
+        sd = {"format": self._FORMAT, **{k: getattr(self, k) for k in self._SHAPE},
+              "schedule": None if self.schedule is None else self.schedule.state_dict(),
+              "t": self.t.clone(),
+              "records": {k: getattr(self, k)[:, :self.L][live] for k in self._REC},
+              "stats": self.stats.clone(),
+              "counters": {k: getattr(self, k) for k in self._COUNTERS},
+              "env": self.env.state_dict()}
+        if self.archive is not None:  # (a trainer without a pool writes the keys it always wrote)
+            sd["archive"] = self.archive.state_dict()
+        return sd
+
+    def _check_archive(self, sd):
+        """ValueError unless `sd` and this trainer agree in having a pool, and in its kind,
+        geometry, capacity and group count (nothing is changed)."""
+        if ("archive" in sd) != (self.archive is not None):
+            raise ValueError("the saved trainer and this one differ in having an explored-maze "
+                             "pool (archive=)")
+        if self.archive is not None:
+            self.archive.check_state_dict(sd["archive"])
 
     def _load_common(self, sd):
         name = type(self).__name__
@@ -150,6 +222,7 @@ class EpisodicTrainer:
             raise ValueError(f"not a {name} state_dict of this shape")
         if (sd["schedule"] is None) != (self.schedule is None):
             raise ValueError("curriculum / growth differ from the saved trainer's")
+        self._check_archive(sd)  # (before anything changes)
         self.env.load_state_dict(sd["env"])
         if self.schedule is not None:
             self.schedule.load_state_dict(sd["schedule"])
@@ -160,6 +233,8 @@ class EpisodicTrainer:
         self.stats.copy_(sd["stats"])
         for k, v in sd["counters"].items():
             setattr(self, k, int(v))
+        if self.archive is not None:
+            self.archive.load_state_dict(sd["archive"])
 
 
 class PooledEpisodicTrainer(EpisodicTrainer):

@@ -67,11 +67,12 @@ class VectorPPOTrainer(PooledEpisodicTrainer):
     def __init__(self, env, device, actor_lr=3e-4, critic_lr=1e-4, gamma=0.9, batch_size=2048,
                  ppo_steps=4, pool_size=65536, hidden_dim=1024, h_channels=32, seed=0,
                  allreduce=None, use_graph=True, bank=True, pool_capacity=None, curriculum=False,
-                 growth=None, algorithm="r-prim", bank_candidates=1):
-        """curriculum / growth / algorithm / bank_candidates: EpisodicTrainer's (schedule.py)."""
+                 growth=None, algorithm="r-prim", bank_candidates=1, archive=None):
+        """curriculum / growth / algorithm / bank_candidates: EpisodicTrainer's (schedule.py);
+        archive: its explored-maze pool (None: off). A data-parallel run keeps one per rank."""
         super().__init__(env, device, pool_size, pool_capacity, allreduce, bank=bank,
                          curriculum=curriculum, growth=growth, algorithm=algorithm,
-                         bank_candidates=bank_candidates)
+                         bank_candidates=bank_candidates, archive=archive)
         torch.manual_seed(seed)
         self.net = ActorCriticNet(3, 6, 4, h_channels, hidden_dim).to(self.device)
         # the update reads the pool's packed windows through the HIP stem and replays a captured

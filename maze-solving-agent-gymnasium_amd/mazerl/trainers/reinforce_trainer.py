@@ -56,11 +56,13 @@ class VectorReinforceTrainer(PooledEpisodicTrainer):
     def __init__(self, env, device, lr=1e-3, gamma=0.99, update_rows=16384, batch_size=2048,
                  temperature=2.0, entropy_coef=0.01, hidden_dim=1024, h_channels=32, seed=0,
                  bank=True, curriculum=False, growth=None, algorithm="r-prim", bank_candidates=1,
-                 pool_capacity=None):
+                 pool_capacity=None, archive=None):
         """update_rows: pool rows that make an update due (1: after every finished episode);
-        curriculum / growth / algorithm / bank_candidates: EpisodicTrainer's (schedule.py)."""
+        curriculum / growth / algorithm / bank_candidates: EpisodicTrainer's (schedule.py);
+        archive: its explored-maze pool (None: off)."""
         super().__init__(env, device, update_rows, pool_capacity, bank=bank, curriculum=curriculum,
-                         growth=growth, algorithm=algorithm, bank_candidates=bank_candidates)
+                         growth=growth, algorithm=algorithm, bank_candidates=bank_candidates,
+                         archive=archive)
         torch.manual_seed(seed)
         self.net = PolicyNetwork(3, 6, 4, h_channels, hidden_dim).to(self.device)
         self.opt = FlatAdamWGroups(self.net, [(self.net.parameters(), lr)], max_norm=1.0)

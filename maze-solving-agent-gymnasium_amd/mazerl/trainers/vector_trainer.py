@@ -437,9 +437,12 @@ def evaluate_explored(learner, pool, n=None, eps=0.0, chunk=None, seed=0x7E57,
     """The reference's test(n, new=False) (off_policy_trainer.py:228-263) over a MazePool: its
     entries 0 .. n - 1 — the oldest n mazes the run trained on (n None: every held one) — one
     episode each, win = terminated. Dense: the entries are played `chunk` at a time (None: all at
-    once), each chunk in an eval env of its own — the pool's pitch and geometry, enrich
-    observations and evaluate()'s window options — that pool.load() fills without a host copy, so
-    every instance of it plays. `eps` is a number or a callable k -> epsilon of each of the n
+    once), each chunk in an eval env of its own — the pool's pitch, geometry and enrich setting
+    (an Enrich pool: evaluate()'s window options; a plain one, the recurrent DQN's: obs6 alone) —
+    that pool.load() fills without a host copy, so every instance of it plays. A learner with a
+    reset() (drqn_trainer's evaluator: a per-row recurrent state) is reset before each chunk. The
+    default max_vector_steps, (P - 1)^2 + 2, is no bound on the torus: pass
+    episode_bound(pool.pitch, pool.toroidal) + 1 there (trainers/episodic.py). `eps` is a number or a callable k -> epsilon of each of the n
     entries for the k-th action; steps_done_epsilon(learner, n, instances=pool.owner[:n]) is the
     reference's protocol, every maze continuing its owner's epsilon. An entry the load refuses
     would leave a generated maze in its place: pool.errors is read with the result and a
@@ -460,10 +463,16 @@ def evaluate_explored(learner, pool, n=None, eps=0.0, chunk=None, seed=0x7E57,
     steps = 0
     for first in range(0, n, chunk):
         m = min(chunk, n - first)
-        env = make_env(m, P, toroidal=pool.toroidal, seed=seed, device=pool.device,
-                       done_list=False, pos=False, window=not bits, window_bits=True)
+        if pool.enrich:
+            env = make_env(m, P, toroidal=pool.toroidal, seed=seed, device=pool.device,
+                           done_list=False, pos=False, window=not bits, window_bits=True)
+        else:  # a plain env's pool (the recurrent DQN's: obs6 alone, mazes from 9 x 9 up)
+            env = VectorMazeEnv(m, P, toroidal=pool.toroidal, enrich=False, device=pool.device,
+                                seed=seed, done_list=False, pos=False)
         pool.load(env, torch.arange(first, first + m, dtype=torch.int32, device=pool.device))
         env.reset()
+        if hasattr(learner, "reset"):  # a recurrent learner starts every chunk from zero state
+            learner.reset()
         e = (lambda k, a=first, b=first + m: eps(k)[a:b]) if callable(eps) else eps
         w, k = _play_episodes(learner, env, e, seed, limit)
         won[first:first + m] = w
