@@ -853,6 +853,61 @@ int mz_drqn_window_backward(const float* const* params_dev, int32_t hidden, int3
                             const float* d_dev, const double* ep_loss_dev, float* gpart_dev,
                             float* const* grads_dev, float* loss_dev, void* stream);
 
+/* ---- Prioritized replay windows (VectorRecurrentDQNTrainer(window=T, priority_alpha=a)) --------
+ * Every window (slot, j) of the replay ring carries a mass: an unsigned 32-bit fixed-point priority
+ * with 20 fractional bits, 0 = no such window. mem_prio_dev is uint32 [capacity][W], W =
+ * ceil(L / T); mem_psum_dev uint64 [capacity] holds each slot's sum of masses; prio_max_dev uint32
+ * [1] the largest mass an update has written (the caller starts it at 2^20, priority 1). Every sum
+ * over masses is an exact 64-bit integer, so no result below depends on a reduction's order and the
+ * sampler equals a host model bit for bit; no float atomics are used. Every entry point refuses a
+ * null pointer, T < 1, hidden != 32, E < 1, B < 1, L < 1, capacity < 1, K < 0, K % T != 0, alpha
+ * < 0, beta < 0, eta outside [0, 1], eps <= 0, a non-finite parameter, and capacity W E 2^30 >= 2^63
+ * (the bound under which every product fits 64 bits; a store counts E = 1) with MZ_EINVAL before
+ * any GPU call, as far as it has the argument. */
+
+/* After mz_ppo_scan and BEFORE mz_drqn_store (it reads the head the store advances), by
+ * mz_drqn_store's slot rule and validity tests: the k-th listed episode (n steps) gives entries
+ * 0 .. ceil(n / T) - 1 of mem_prio_dev[(head + k) mod capacity] the mass prio_max_dev[0], the
+ * slot's other entries 0, and mem_psum_dev[slot] = ceil(n / T) prio_max; with more listed episodes
+ * than slots the last `capacity` stay. One workgroup per listed episode. */
+int mz_drqn_prio_store(int32_t hidden, int32_t B, int32_t L, int32_t T, const int32_t* fin_id_dev,
+                       const int32_t* fin_len_dev, const int32_t* fin_count_dev, int64_t capacity,
+                       uint32_t* mem_prio_dev, uint64_t* mem_psum_dev, const uint32_t* prio_max_dev,
+                       const int64_t* ring_dev, void* stream);
+
+/* In mz_drqn_window_sample's place: E windows with replacement, in proportion to their mass,
+ * stratified. S = the sum of mem_psum_dev over slots 0 .. capacity - 1; batch position e draws
+ * t = lo + mulhi64(r, hi - lo), lo = floor(e S / E), hi = floor((e + 1) S / E), r = (r0 << 32) | r1
+ * of a Philox stream of its own keyed by (seed, counter, e), and takes the window (slot, j) with
+ * prefix <= t < prefix + mass, the prefix running slot-major, j-minor over all masses. From j:
+ * s = j T, b = max(0, s - K), k = s - b, m = min(T, n - s); wdir_dev, win_off_dev and win_tot_dev
+ * are mz_drqn_window_sample's, so mz_drqn_window_forward / _backward run on them as they are. Two
+ * positions may hold the same window. isw_dev[e] = (float) pow((double) M_min / M_e, beta), M_e the
+ * sampled window's mass and M_min the batch's smallest (1.0f exactly at beta == 0). With S == 0 the
+ * batch has no window (m = 0 throughout). One workgroup per learner; deterministic. */
+int mz_drqn_prio_sample(uint64_t seed, uint64_t counter, int32_t hidden, int32_t E, int32_t L,
+                        int32_t T, int32_t K, int64_t capacity, const int32_t* mem_len_dev,
+                        const uint32_t* mem_prio_dev, const uint64_t* mem_psum_dev,
+                        int32_t* wdir_dev, int64_t* win_off_dev, int64_t* win_tot_dev,
+                        float* isw_dev, double beta, void* stream);
+
+/* After the source net's mz_drqn_window_forward and before mz_drqn_window_backward. For window e
+ * over its m training rows: a_i = |qa_i - y_i| (f32), pr = eta max a_i + (1 - eta) mean a_i
+ * (float64, the mean summed in time order, both products and the sum rounded separately), mass =
+ * clamp(llrint(pow(pr + eps, alpha) 2^20), 1, 2^30) (2^30 where that is not finite; alpha == 0
+ * gives 2^20 exactly), written to mem_prio_dev[slot][(b + k) / T]; prio_max_dev[0] becomes the
+ * maximum of itself and the batch's masses (an integer atomic). Once all E are written, every
+ * touched slot's mem_psum_dev is recomputed from its W entries. Then d_dev[row] *= isw_dev[e] for
+ * the window's training rows and ep_loss_dev[e] *= (double) isw_dev[e], so the unchanged backward
+ * gives the gradient and value of sum_e w_e sum_t (Q_t[a_t] - y_t)^2 / sum m. One workgroup per
+ * learner; a window the directory does not describe validly is skipped. */
+int mz_drqn_prio_update(int32_t hidden, int32_t E, int32_t L, int32_t T, int64_t capacity,
+                        const int32_t* wdir_dev, const int64_t* win_off_dev,
+                        const int64_t* win_tot_dev, const float* qa_dev, const float* y_dev,
+                        float* d_dev, double* ep_loss_dev, const float* isw_dev, double alpha,
+                        double eta, double eps, uint32_t* mem_prio_dev, uint64_t* mem_psum_dev,
+                        uint32_t* prio_max_dev, void* stream);
+
 /* ---- Populations of recurrent DQN learners (VectorRecurrentDQNPopulation) ---------------------
  * P independent learners of agents/lstm_dqn_agent.py (nn.LSTMCell(6, 32) + nn.Linear(32, 4),
  * whole episodes from SequentialExperienceReplayMemory, lib/replay_memory.py:26-43) advanced by

@@ -1962,6 +1962,81 @@ int mz_drqn_pop_window_backward(const float* params_dev, int32_t hidden, int32_t
       ep_loss_dev, drqn_flat_net(grads_dev), loss_dev, stream);
 }
 
+// ---- prioritized replay windows (mz_drqn.hip k_drqn_prio_store / _sample / _update) -------------
+// what the three share: the window, the sizes, and that every integer the kernels form fits 64
+// bits: capacity ceil(L / T) E 2^30 < 2^63 (a store has no batch: E = 1)
+static int drqn_prio_args(const char* who, int32_t hidden, int32_t T, int32_t K, int32_t E,
+                          int32_t L, int64_t capacity) {
+  if (int rc = drqn_win_args(who, hidden, T, K)) return rc;
+  if (E < 1 || L < 1 || capacity < 1)
+    return fail(MZ_EINVAL, "%s: E %d, L %d, capacity %lld", who, E, L, (long long)capacity);
+  const unsigned __int128 prod = (unsigned __int128)capacity * (unsigned)((L - 1) / T + 1) * (unsigned)E;
+  if (prod >= ((unsigned __int128)1 << 33))
+    return fail(MZ_EINVAL, "%s: capacity %lld x %d windows x E %d x 2^30 does not fit 63 bits", who,
+                (long long)capacity, (L - 1) / T + 1, E);
+  return MZ_OK;
+}
+
+int mz_drqn_prio_store(int32_t hidden, int32_t B, int32_t L, int32_t T, const int32_t* fin_id_dev,
+                       const int32_t* fin_len_dev, const int32_t* fin_count_dev, int64_t capacity,
+                       uint32_t* mem_prio_dev, uint64_t* mem_psum_dev, const uint32_t* prio_max_dev,
+                       const int64_t* ring_dev, void* stream) {
+  const char* who = "mz_drqn_prio_store";
+  if (int rc = drqn_pop_args(who, hidden, 1, B, "instances per learner")) return rc;
+  if (int rc = drqn_prio_args(who, hidden, T, 0, 1, L, capacity)) return rc;
+  if (!fin_id_dev || !fin_len_dev || !fin_count_dev || !mem_prio_dev || !mem_psum_dev ||
+      !prio_max_dev || !ring_dev)
+    return fail(MZ_EINVAL, "%s: null pointer", who);
+  StreamGuard g(stream);
+  MzDrqnPrioStore s{B, L, T, fin_id_dev, fin_len_dev, fin_count_dev, capacity, mem_prio_dev,
+                    mem_psum_dev, prio_max_dev, ring_dev};
+  MZ_HIP(mz_launch_drqn_prio_store(MzDrqnPopPrioStore{s, 1, B}, B < 2048 ? B : 2048,
+                                   static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_drqn_prio_sample(uint64_t seed, uint64_t counter, int32_t hidden, int32_t E, int32_t L,
+                        int32_t T, int32_t K, int64_t capacity, const int32_t* mem_len_dev,
+                        const uint32_t* mem_prio_dev, const uint64_t* mem_psum_dev,
+                        int32_t* wdir_dev, int64_t* win_off_dev, int64_t* win_tot_dev,
+                        float* isw_dev, double beta, void* stream) {
+  const char* who = "mz_drqn_prio_sample";
+  if (int rc = drqn_prio_args(who, hidden, T, K, E, L, capacity)) return rc;
+  if (!mem_len_dev || !mem_prio_dev || !mem_psum_dev || !wdir_dev || !win_off_dev ||
+      !win_tot_dev || !isw_dev)
+    return fail(MZ_EINVAL, "%s: null pointer", who);
+  if (!(beta >= 0.0 && std::isfinite(beta))) return fail(MZ_EINVAL, "%s: beta %g (>= 0)", who, beta);
+  StreamGuard g(stream);
+  MzDrqnPrioSample s{seed, counter, E, L, T, K, capacity, mem_len_dev, mem_prio_dev, mem_psum_dev,
+                     wdir_dev, win_off_dev, win_tot_dev, isw_dev, beta};
+  MZ_HIP(mz_launch_drqn_prio_sample(MzDrqnPopPrioSample{s, 1, nullptr, nullptr, nullptr, nullptr},
+                                    static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_drqn_prio_update(int32_t hidden, int32_t E, int32_t L, int32_t T, int64_t capacity,
+                        const int32_t* wdir_dev, const int64_t* win_off_dev,
+                        const int64_t* win_tot_dev, const float* qa_dev, const float* y_dev,
+                        float* d_dev, double* ep_loss_dev, const float* isw_dev, double alpha,
+                        double eta, double eps, uint32_t* mem_prio_dev, uint64_t* mem_psum_dev,
+                        uint32_t* prio_max_dev, void* stream) {
+  const char* who = "mz_drqn_prio_update";
+  if (int rc = drqn_prio_args(who, hidden, T, 0, E, L, capacity)) return rc;
+  if (!wdir_dev || !win_off_dev || !win_tot_dev || !qa_dev || !y_dev || !d_dev || !ep_loss_dev ||
+      !isw_dev || !mem_prio_dev || !mem_psum_dev || !prio_max_dev)
+    return fail(MZ_EINVAL, "%s: null pointer", who);
+  if (!(alpha >= 0.0 && std::isfinite(alpha)) || !(eta >= 0.0 && eta <= 1.0) ||
+      !(eps > 0.0 && std::isfinite(eps)))
+    return fail(MZ_EINVAL, "%s: alpha %g (>= 0), eta %g (0..1), eps %g (> 0)", who, alpha, eta, eps);
+  StreamGuard g(stream);
+  MzDrqnPrioUpdate u{E, L, T, capacity, wdir_dev, win_off_dev, win_tot_dev, qa_dev, y_dev, d_dev,
+                     ep_loss_dev, isw_dev, alpha, eta, eps, mem_prio_dev, mem_psum_dev,
+                     prio_max_dev};
+  MZ_HIP(mz_launch_drqn_prio_update(MzDrqnPopPrioUpdate{u, 1, nullptr},
+                                    static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
 int mz_drqn_pop_sync(const float* src_dev, float* dst_dev, const int32_t* mask_dev, int32_t P,
                      void* stream) {
   if (!src_dev || !dst_dev || !mask_dev) return fail(MZ_EINVAL, "mz_drqn_pop_sync: null pointer");

@@ -169,6 +169,7 @@ __host__ __device__ inline void mz_philox(uint64_t key, uint64_t ctr_hi, uint64_
 #define MZ_DRQN_STREAM 0x6472716Eull  // 'drqn': recurrent DQN exploration draws
 #define MZ_DRQN_SAMPLE_STREAM 0x64727173ull  // 'drqs': recurrent DQN replay episode draws
 #define MZ_DRQN_WINDOW_STREAM 0x64727177ull  // 'drqw': recurrent DQN replay window draws
+#define MZ_DRQN_PRIO_STREAM 0x64727170ull  // 'drqp': recurrent DQN prioritized window draws
 
 // Sequential draw stream (one per maze): draw k = word (k & 3) of philox(key, {GEN, k >> 2}).
 struct MzRng {

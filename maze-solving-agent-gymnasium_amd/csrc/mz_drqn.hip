@@ -48,6 +48,16 @@
 //                      b .. of the episode from the stored state; the burn-in steps only advance the
 //                      state, BPTT covers the m training steps. k_drqn_reduce sums the per-window
 //                      partials.
+// Prioritized windows (priority_alpha; off by default): every window (slot, j) carries an integer
+// mass, so every sum is exact and the sampler equals a host model bit for bit.
+//   k_drqn_prio_store   before k_drqn_store: the finished episodes' windows enter at prio_max.
+//   k_drqn_prio_sample  in k_drqn_win_sample's place, one workgroup per learner: windows in
+//                       proportion to their mass (stratified, with replacement), the same
+//                       directory, and the importance weights.
+//   k_drqn_prio_update  between k_drqn_win_fwd (source) and k_drqn_win_bwd, one workgroup per
+//                       learner: the sampled windows' new masses from the forward's residuals,
+//                       the slots' sums, and d and ep_loss scaled by the weights. The forward
+//                       and backward kernels are not touched.
 // Populations (trainers/drqn_population.py VectorRecurrentDQNPopulation): P independent learners
 // over B = P b instances, learner p owning instances [p b, (p + 1) b), flat [P][5252] parameters.
 // Every kernel above but k_drqn_snapshot (which serves B = P b as it is) moves its single-learner
@@ -990,6 +1000,278 @@ __global__ __launch_bounds__(WAVE) void k_drqn_win_bwd(MzDrqnPopWin q) {
   drqn_unroll_bwd(s.u, e, w);
 }
 
+// ---- prioritized replay windows ------------------------------------------------------------
+// Masses are u32 fixed point (MZ_DRQN_PRIO_FRAC fractional bits), every sum over them an exact
+// u64: whatever order a scan or a reduction below takes, its result is the integer the host model
+// computes. The entry points bound cap W E 2^30 below 2^63, so no sum or product here wraps.
+constexpr int PRIO_T = 1024;             // threads of the sampler and of the write-back
+constexpr int PRIO_WAVES = PRIO_T / WAVE;
+
+// inclusive scan over the wave's 64 lanes
+__device__ __forceinline__ uint64_t drqn_wave_scan(uint64_t v, const int lane) {
+#pragma unroll
+  for (int o = 1; o < WAVE; o <<= 1) {
+    const unsigned long long u = __shfl_up((unsigned long long)v, o);
+    if (lane >= o) v += u;
+  }
+  return v;
+}
+
+// The lane-parallel search both levels of the sampler use: n masses at a[0 .. n) (u64 or u32),
+// 64 per round, taken in index order on top of `base`. Returns the index i with prefix(i) <= t <
+// prefix(i) + a[i] and leaves prefix(i) in base; -1 (base = the whole sum added) where t lies
+// beyond them all. Every lane of the wave gets the same answer.
+template <class M>
+__device__ __forceinline__ int64_t drqn_prio_find(const M* a, const int64_t n, const uint64_t t,
+                                                  uint64_t& base, const int lane) {
+  for (int64_t i0 = 0; i0 < n; i0 += WAVE) {
+    const uint64_t v = i0 + lane < n ? (uint64_t)a[i0 + lane] : 0;
+    const uint64_t inc = drqn_wave_scan(v, lane);
+    const unsigned long long hit = __ballot(t < base + inc);
+    if (hit) {
+      const int l = __ffsll(hit) - 1;
+      base += (uint64_t)__shfl((unsigned long long)(inc - v), l);
+      return i0 + l;
+    }
+    base += (uint64_t)__shfl((unsigned long long)inc, WAVE - 1);
+  }
+  return -1;
+}
+
+// Entry: before k_drqn_store, by its slot rule and its validity tests: the listed episode of n
+// steps gives its ceil(n / T) windows the mass prio_max, zero to the slot's other entries, and the
+// slot its sum.
+__device__ __forceinline__ void drqn_prio_store_body(const MzDrqnPrioStore& q,
+                                                     const int32_t* fin_id, const int32_t* fin_len,
+                                                     const int nfin, const int blk,
+                                                     const int nblk) {
+  const int64_t head = q.ring[0];
+  const int W = drqn_windows(q.L, q.T);
+  const uint32_t pm = q.prio_max[0];
+  const int first = nfin > q.cap ? nfin - (int)q.cap : 0;
+  for (int k = first + blk; k < nfin; k += nblk) {
+    const int i = fin_id[k], n = fin_len[k];
+    if (i < 0 || i >= q.B || n < 1 || n > q.L || head < 0 || head >= q.cap) continue;
+    const int64_t slot = (head + k) % q.cap;
+    const int nw = drqn_windows(n, q.T);
+    for (int j = threadIdx.x; j < W; j += blockDim.x)
+      q.mem_prio[(size_t)slot * W + j] = j < nw ? pm : 0u;
+    if (threadIdx.x == 0) q.mem_psum[slot] = (uint64_t)nw * pm;
+  }
+}
+
+__global__ __launch_bounds__(WAVE) void k_drqn_prio_store(MzDrqnPopPrioStore q) {
+  const int p = blockIdx.y;
+  int lo, hi;
+  drqn_pop_run(q.s.fin_id, q.s.fin_count, q.s.B, q.b, p, &lo, &hi);
+  if (hi <= lo) return;
+  MzDrqnPrioStore s = q.s;
+  s.mem_prio += (size_t)p * s.cap * drqn_windows(s.L, s.T);
+  s.mem_psum += (size_t)p * s.cap;
+  s.prio_max += p;
+  s.ring += 2 * (size_t)p;
+  drqn_prio_store_body(s, q.s.fin_id + lo, q.s.fin_len + lo, hi - lo, blockIdx.x, gridDim.x);
+}
+
+// Sampling, with replacement and stratified: S = the sum of all masses; position e draws t in
+// [floor(e S / E), floor((e + 1) S / E)) and takes the window (slot, j) whose span of the
+// slot-major, j-minor prefix holds t. The slots are cut into at most PRIO_T groups of 64 g
+// consecutive slots: (1) every wave sums whole groups with coalesced loads; (2) one block scan
+// turns the group sums into prefixes in LDS; (3) a wave per position finds its group by binary
+// search, the slot inside the group and the window inside the slot by drqn_prio_find; (4) the
+// smallest sampled mass (an integer atomic min in LDS), the weights, and the row offsets as
+// drqn_win_sample_body lays them out. K < 0 gives the batch no window, as there.
+__device__ __forceinline__ void drqn_prio_sample_body(const MzDrqnPrioSample& q) {
+  __shared__ uint64_t gpre[PRIO_T];    // group sums, then their exclusive prefixes
+  __shared__ uint64_t wsum[PRIO_WAVES];
+  __shared__ uint32_t mmin;
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+  const int E = q.E, W = drqn_windows(q.L, q.T);
+  const int64_t gsz = (int64_t)WAVE * ((q.cap + (int64_t)WAVE * PRIO_T - 1) / ((int64_t)WAVE * PRIO_T));
+  const int ng = (int)((q.cap + gsz - 1) / gsz);  // <= PRIO_T
+  for (int g = wave; g < ng; g += PRIO_WAVES) {
+    uint64_t s = 0;
+    const int64_t end = min((int64_t)(g + 1) * gsz, q.cap);
+    for (int64_t i = (int64_t)g * gsz + lane; i < end; i += WAVE) s += q.mem_psum[i];
+    s = drqn_wave_scan(s, lane);
+    if (lane == WAVE - 1) gpre[g] = s;
+  }
+  if (tid == 0) mmin = 0xffffffffu;
+  __syncthreads();
+  const uint64_t own = tid < ng ? gpre[tid] : 0;
+  const uint64_t inc = drqn_wave_scan(own, lane);
+  if (lane == WAVE - 1) wsum[wave] = inc;
+  __syncthreads();
+  uint64_t before = 0, S = 0;
+  for (int w = 0; w < PRIO_WAVES; ++w) {
+    if (w < wave) before += wsum[w];
+    S += wsum[w];
+  }
+  gpre[tid] = before + inc - own;
+  __syncthreads();
+  int32_t* wd = q.wdir;
+  for (int e = wave; e < E; e += PRIO_WAVES) {
+    int slot = 0, n = 0, b = 0, kb = 0, m = 0;
+    if (S > 0 && q.K >= 0) {
+      const uint64_t lo = (uint64_t)e * S / (uint64_t)E, hi = (uint64_t)(e + 1) * S / (uint64_t)E;
+      uint32_t r[4];
+      mz_philox(q.seed, MZ_DRQN_PRIO_STREAM ^ ((uint64_t)(uint32_t)e << 32), q.counter, r);
+      const uint64_t t = lo + __umul64hi(((uint64_t)r[0] << 32) | r[1], hi - lo);
+      int g = 0;  // the last group whose prefix is <= t: the one whose span holds t
+      for (int step = PRIO_T / 2; step >= 1; step >>= 1)
+        if (g + step < ng && gpre[g + step] <= t) g += step;
+      uint64_t base = gpre[g];
+      const int64_t s0 = (int64_t)g * gsz;
+      const int64_t si = drqn_prio_find(q.mem_psum + s0, min(gsz, q.cap - s0), t, base, lane);
+      if (si >= 0) {
+        const int64_t sl = s0 + si;
+        const int64_t j = drqn_prio_find(q.mem_prio + (size_t)sl * W, W, t, base, lane);
+        const int len = q.mem_len[sl];
+        if (j >= 0 && len >= 1 && len <= q.L && j < drqn_windows(len, q.T)) {
+          const int s = (int)j * q.T;
+          slot = (int)sl;
+          n = len;
+          b = s > q.K ? s - q.K : 0;
+          kb = s - b;
+          m = min(q.T, n - s);
+        }
+      }
+    }
+    if (lane == 0) {
+      wd[MZ_DRQN_WDIR_SLOT * E + e] = slot;
+      wd[MZ_DRQN_WDIR_LEN * E + e] = n;
+      wd[MZ_DRQN_WDIR_B * E + e] = b;
+      wd[MZ_DRQN_WDIR_K * E + e] = kb;
+      wd[MZ_DRQN_WDIR_M * E + e] = m;
+      if (m > 0) atomicMin(&mmin, q.mem_prio[(size_t)slot * W + (b + kb) / q.T]);
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < E; e += PRIO_T) {
+    float w = 1.0f;
+    if (wd[MZ_DRQN_WDIR_M * E + e] > 0 && q.beta != 0.0) {
+      const int j = (wd[MZ_DRQN_WDIR_B * E + e] + wd[MZ_DRQN_WDIR_K * E + e]) / q.T;
+      const uint32_t mass = q.mem_prio[(size_t)wd[MZ_DRQN_WDIR_SLOT * E + e] * W + j];
+      w = (float)pow((double)mmin / (double)mass, q.beta);
+    }
+    q.isw[e] = w;
+  }
+  if (tid == 0) {
+    int64_t rows = 0, steps = 0;
+    for (int e = 0; e < E; ++e) {
+      const int m = wd[MZ_DRQN_WDIR_M * E + e];
+      q.w_off[e] = rows;
+      rows += m > 0 ? m + MZ_DRQN_WIN_PAD : 0;
+      steps += m;
+    }
+    q.w_tot[0] = rows;
+    q.w_tot[1] = steps;
+  }
+}
+
+// one workgroup per learner, on its masses, directory block, seed, update count and burn-in
+__global__ __launch_bounds__(PRIO_T) void k_drqn_prio_sample(MzDrqnPopPrioSample q) {
+  const int p = blockIdx.x;
+  if (q.due && q.due[p] == 0) return;
+  MzDrqnPrioSample s = q.s;
+  const size_t E = (size_t)s.E;
+  if (q.burn_in) s.K = drqn_pop_burn_in(q.burn_in, p, s.T, q.s.K);
+  if (q.seed) s.seed = q.seed[p];
+  if (q.counter) s.counter = q.counter[p];
+  s.mem_len += (size_t)p * s.cap;
+  s.mem_prio += (size_t)p * s.cap * drqn_windows(s.L, s.T);
+  s.mem_psum += (size_t)p * s.cap;
+  s.wdir += (size_t)p * 5 * E;
+  s.w_off += p * E;
+  s.w_tot += 2 * (size_t)p;
+  s.isw += p * E;
+  drqn_prio_sample_body(s);
+}
+
+// the mass of a window whose residuals have the maximum mx and the mean `mean`:
+// clamp(llrint((eta mx + (1 - eta) mean + eps)^alpha 2^20), 1, 2^30), 2^30 where that is not finite
+__device__ __forceinline__ uint32_t drqn_prio_mass(const double mx, const double mean,
+                                                   const double alpha, const double eta,
+                                                   const double eps) {
+  const double pr = __dadd_rn(__dmul_rn(eta, mx), __dmul_rn(1.0 - eta, mean));
+  const double v = (alpha == 0.0 ? 1.0 : pow(pr + eps, alpha)) * (double)(1u << MZ_DRQN_PRIO_FRAC);
+  if (!(v < (double)MZ_DRQN_PRIO_CEIL)) return MZ_DRQN_PRIO_CEIL;
+  const long long r = llrint(v);
+  return r < 1 ? 1u : (uint32_t)r;
+}
+
+// After the source forward, before the backward. A wave per window: lane i holds |qa - y| of
+// training row i (T > 64: of rows i, i + 64, ...; the running maximum and the time-ordered
+// float64 sum go round by round), lane 0 turns them into the mass, writes it to (slot, j) and
+// raises prio_max (an integer atomic max); then the wave scales the window's d rows and its
+// ep_loss by the importance weight. Once every mass of the batch is written, a wave per window
+// recomputes its slot's sum from the slot's W entries (duplicates write the same values).
+__device__ __forceinline__ void drqn_prio_update_body(const MzDrqnPrioUpdate& q) {
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+  const int E = q.E, W = drqn_windows(q.L, q.T);
+  const int64_t rows = (int64_t)E * (min(q.T, q.L) + MZ_DRQN_WIN_PAD);
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int e = wave; e < E; e += PRIO_WAVES) {
+      const int slot = q.wdir[MZ_DRQN_WDIR_SLOT * E + e], m = q.wdir[MZ_DRQN_WDIR_M * E + e];
+      const int s = q.wdir[MZ_DRQN_WDIR_B * E + e] + q.wdir[MZ_DRQN_WDIR_K * E + e];
+      const int64_t off = q.w_off[e];
+      if (!(slot >= 0 && slot < q.cap && m >= 1 && m <= q.T && s >= 0 && s % q.T == 0 &&
+            s / q.T < W && off >= 0 && off + m + MZ_DRQN_WIN_PAD <= rows))
+        continue;
+      uint32_t* pw = q.mem_prio + (size_t)slot * W;
+      if (pass == 1) {
+        uint64_t sum = 0;
+        for (int j = lane; j < W; j += WAVE) sum += pw[j];
+        sum = drqn_wave_scan(sum, lane);
+        if (lane == WAVE - 1) q.mem_psum[slot] = sum;
+        continue;
+      }
+      float mx = 0.0f;
+      double sum = 0.0;
+      for (int i0 = 0; i0 < m; i0 += WAVE) {
+        const int64_t R = off + 1 + i0 + lane;
+        const float a = i0 + lane < m ? fabsf(q.qa[R] - q.y[R]) : 0.0f;
+        float v = a;
+#pragma unroll
+        for (int o = WAVE / 2; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+        mx = fmaxf(mx, v);
+        const int cnt = min(WAVE, m - i0);
+        for (int i = 0; i < cnt; ++i) sum += (double)__shfl(a, i);
+      }
+      if (lane == 0) {
+        const uint32_t mass = drqn_prio_mass((double)mx, sum / (double)m, q.alpha, q.eta, q.eps);
+        pw[s / q.T] = mass;
+        atomicMax(q.prio_max, mass);
+      }
+      const float w = q.isw[e];
+      for (int i = lane; i < m; i += WAVE) q.d[off + 1 + i] *= w;
+      if (lane == 0) q.ep_loss[e] *= (double)w;
+    }
+    __threadfence_block();
+    __syncthreads();
+  }
+}
+
+// one workgroup per learner
+__global__ __launch_bounds__(PRIO_T) void k_drqn_prio_update(MzDrqnPopPrioUpdate q) {
+  const int p = blockIdx.x;
+  if (q.due && q.due[p] == 0) return;
+  MzDrqnPrioUpdate u = q.u;
+  const size_t E = (size_t)u.E, rows = E * (min(u.T, u.L) + MZ_DRQN_WIN_PAD);
+  u.wdir += p * 5 * E;
+  u.w_off += p * E;
+  u.w_tot += 2 * (size_t)p;
+  u.qa += p * rows;
+  u.y += p * rows;
+  u.d += p * rows;
+  u.ep_loss += p * E;
+  u.isw += p * E;
+  u.mem_prio += (size_t)p * u.cap * drqn_windows(u.L, u.T);
+  u.mem_psum += (size_t)p * u.cap;
+  u.prio_max += p;
+  drqn_prio_update_body(u);
+}
+
 }  // namespace
 
 hipError_t mz_launch_drqn_act(const MzDrqnPopAct& q, hipStream_t s) {
@@ -1057,5 +1339,21 @@ hipError_t mz_launch_drqn_window_forward(const MzDrqnPopWin& q, hipStream_t s) {
 
 hipError_t mz_launch_drqn_window_backward(const MzDrqnPopWin& q, hipStream_t s) {
   hipLaunchKernelGGL(k_drqn_win_bwd, dim3((unsigned)q.P * q.q.u.E), dim3(WAVE), 0, s, q);
+  return hipGetLastError();
+}
+
+// ---- prioritized replay windows -------------------------------------------------------------
+hipError_t mz_launch_drqn_prio_store(const MzDrqnPopPrioStore& q, int blocks, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_prio_store, dim3(blocks, q.P), dim3(WAVE), 0, s, q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_prio_sample(const MzDrqnPopPrioSample& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_prio_sample, dim3(q.P), dim3(PRIO_T), 0, s, q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_prio_update(const MzDrqnPopPrioUpdate& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_prio_update, dim3(q.P), dim3(PRIO_T), 0, s, q);
   return hipGetLastError();
 }

@@ -234,6 +234,32 @@ struct MzDrqnWin {
 };
 hipError_t mz_launch_drqn_snapshot(const MzDrqnSnap& q, hipStream_t s);
 
+// Prioritized replay windows. Window (slot, j) carries a mass: u32 fixed point with
+// MZ_DRQN_PRIO_FRAC fractional bits, 0 = no such window. mem_prio [cap][ceil(L / T)], mem_psum
+// [cap] = the slot's sum of masses (u64), prio_max [1] = the largest mass an update has written.
+// Every sum over masses is an exact 64-bit integer, so no result depends on a reduction's order.
+#define MZ_DRQN_PRIO_FRAC 20
+#define MZ_DRQN_PRIO_CEIL (1u << 30)  // the largest mass
+struct MzDrqnPrioStore {
+  int B, L, T;
+  const int32_t* fin_id; const int32_t* fin_len; const int32_t* fin_count;
+  int64_t cap; uint32_t* mem_prio; uint64_t* mem_psum; const uint32_t* prio_max;
+  const int64_t* ring;
+};
+struct MzDrqnPrioSample {
+  uint64_t seed, counter; int E, L, T, K; int64_t cap;
+  const int32_t* mem_len; const uint32_t* mem_prio; const uint64_t* mem_psum;
+  int32_t* wdir; int64_t* w_off; int64_t* w_tot;  // as MzDrqnWinSample writes them
+  float* isw; double beta;                        // [E] importance weights
+};
+struct MzDrqnPrioUpdate {
+  int E, L, T; int64_t cap;
+  const int32_t* wdir; const int64_t* w_off; const int64_t* w_tot;
+  const float* qa; const float* y; float* d; double* ep_loss;  // the source forward's rows
+  const float* isw; double alpha, eta, eps;
+  uint32_t* mem_prio; uint64_t* mem_psum; uint32_t* prio_max;
+};
+
 // Populations: P independent learners over B = P b instances, learner p owning the block
 // [p b, (p + 1) b). Parameters, gradients and moments are flat [P][MZ_DRQN_PARAMS] f32, a row in
 // state_dict order. Every stage has one kernel and one launcher, which take the structs below: each
@@ -289,6 +315,26 @@ struct MzDrqnPopWin {
   const float* gamma; const int32_t* burn_in;  // [P]; null: q.u.gamma, q.K
   const int32_t* stored; const int32_t* due;   // [P]; stored null: q.mem_state as given
 };
+// Prioritized windows in the per-learner row form: mem_prio [P][cap][ceil(L / T)], mem_psum
+// [P][cap], prio_max [P], isw [P][E]; the directory and the row buffers as MzDrqnPopWin's.
+struct MzDrqnPopPrioStore {
+  MzDrqnPrioStore s;                         // s.B = P b
+  int P, b;
+};
+struct MzDrqnPopPrioSample {
+  MzDrqnPrioSample s;                        // s.K = K_max
+  int P;
+  const uint64_t* seed; const uint64_t* counter;  // [P]; null: s.seed, s.counter
+  const int32_t* burn_in; const int32_t* due;     // [P]; burn_in null: s.K
+};
+struct MzDrqnPopPrioUpdate {
+  MzDrqnPrioUpdate u;
+  int P;
+  const int32_t* due;                        // [P]
+};
+hipError_t mz_launch_drqn_prio_store(const MzDrqnPopPrioStore& q, int blocks, hipStream_t s);
+hipError_t mz_launch_drqn_prio_sample(const MzDrqnPopPrioSample& q, hipStream_t s);
+hipError_t mz_launch_drqn_prio_update(const MzDrqnPopPrioUpdate& q, hipStream_t s);
 // blocks: the store's workgroups per learner
 hipError_t mz_launch_drqn_act(const MzDrqnPopAct& q, hipStream_t s);
 hipError_t mz_launch_drqn_store(const MzDrqnPopStore& q, int blocks, hipStream_t s);

@@ -53,6 +53,7 @@ EXPORTS = ["mz_last_error", "mz_device_count", "mz_create", "mz_destroy", "mz_lo
            "mz_rf_head_loss", "mz_drqn_act", "mz_drqn_store", "mz_drqn_sample",
            "mz_drqn_seq_forward", "mz_drqn_seq_backward", "mz_drqn_snapshot", "mz_drqn_snap_store",
            "mz_drqn_window_sample", "mz_drqn_window_forward", "mz_drqn_window_backward",
+           "mz_drqn_prio_store", "mz_drqn_prio_sample", "mz_drqn_prio_update",
            "mz_drqn_pop_act", "mz_drqn_pop_store",
            "mz_drqn_pop_sample", "mz_drqn_pop_seq_forward", "mz_drqn_pop_seq_backward",
            "mz_drqn_pop_sync", "mz_drqn_pop_snap_store", "mz_drqn_pop_window_sample",
@@ -204,6 +205,11 @@ def load(build_if_missing=True):
         [C.c_int64, C.c_int64] + [vp] * 6
     L.mz_drqn_window_forward.argtypes = [vp] + [C.c_int32] * 6 + [C.c_int64, C.c_float] + [vp] * 13
     L.mz_drqn_window_backward.argtypes = [vp] + [C.c_int32] * 5 + [C.c_int64] + [vp] * 11
+    L.mz_drqn_prio_store.argtypes = [C.c_int32] * 4 + [vp] * 3 + [C.c_int64] + [vp] * 5
+    L.mz_drqn_prio_sample.argtypes = [C.c_uint64, C.c_uint64] + [C.c_int32] * 5 + [C.c_int64] + \
+        [vp] * 7 + [C.c_double, vp]
+    L.mz_drqn_prio_update.argtypes = [C.c_int32] * 4 + [C.c_int64] + [vp] * 8 + \
+        [C.c_double] * 3 + [vp] * 4
     L.mz_drqn_pop_act.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, vp, C.c_int32,
                                   vp, C.c_uint64] + [vp] * 8
     L.mz_drqn_pop_store.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32] + [vp] * 6 + \

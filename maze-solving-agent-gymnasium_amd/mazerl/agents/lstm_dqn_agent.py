@@ -103,16 +103,17 @@ def td_loss(source, target, episodes, gamma):
     return total / steps
 
 
-def window_td_loss(source, target, windows, gamma):
+def window_td_loss(source, target, windows, gamma, weights=None):
     """The loss of a batch of replay windows (trainers/drqn_trainer.py, departure 9). A window is
     (x [k + m + 1, 6], a [m] long, r [m], h0 [32], c0 [32], k, term): the observations of steps
     b .. s + m, the actions and rewards of the m training steps s .. s + m - 1, the state both nets
     start from at step b, the k = s - b burn-in steps, and term = the last training step is the
     last step of a terminated episode (its y is r alone). Burn-in steps carry no loss term and no
     gradient flows into them or through the state that enters step s. loss = sum (Q_t[a_t] -
-    y_t)^2 / sum m."""
+    y_t)^2 / sum m. weights (one per window; None: all 1) are the importance weights of prioritized
+    replay (departure 12): loss = sum_e w_e sum_t (Q_t[a_t] - y_t)^2 / sum m."""
     total, steps = 0.0, 0
-    for x, a, r, h0, c0, k, term in windows:
+    for e, (x, a, r, h0, c0, k, term) in enumerate(windows):
         m = a.shape[0]
         h, c = h0[None], c0[None]
         with torch.no_grad():
@@ -122,7 +123,8 @@ def window_td_loss(source, target, windows, gamma):
             if term:
                 y[m - 1] = r[m - 1]
         q = source.unroll_from(x[None, k:k + m], h, c)[0][0]
-        total = total + ((q.gather(1, a[:, None]).squeeze(1) - y) ** 2).sum()
+        sq = ((q.gather(1, a[:, None]).squeeze(1) - y) ** 2).sum()
+        total = total + (sq if weights is None else weights[e] * sq)
         steps += m
     return total / steps
 

@@ -27,6 +27,13 @@ their mean and spread, and every learner's window settings.
 With --learners, --window T is shared by the population (it fixes the layouts and cannot be
 swept); --burn-in and --initial-state are per learner.
 
+--priority-alpha A beside --window samples the windows in proportion to (their TD error)^A over
+the whole memory, with importance weights of exponent --priority-beta B (or B0,B1,N: linear over N
+updates); --priority-eta H and --priority-eps X shape a window's priority (departures 10-12). A = 0
+is uniform over the memory's windows. The population (--learners) does not take these yet.
+
+  python -m mazerl.train_lstm_dqn --dim 41 --window 40 --burn-in 40 --priority-alpha 0.9
+
 --archive C keeps the mazes the run trains on in a MazePool of C entries (with --learners: one
 pool of C entries per learner, all filled by one launch per vector step) and the final line gains
 the greedy win rate on its oldest --explored-mazes entries, the reference's test(n, new=False)
@@ -38,7 +45,8 @@ import json
 import torch
 
 from .archive import add_pool_arguments, check_pool_arguments
-from .trainers.drqn_trainer import VectorRecurrentDQNTrainer, check_window, evaluate_plain
+from .trainers.drqn_trainer import (VectorRecurrentDQNTrainer, check_priority, check_window,
+                                    evaluate_plain)
 from .trainers.episodic import episode_bound
 from .trainers.vector_trainer import evaluate_explored
 from .vector_env import VectorMazeEnv
@@ -49,6 +57,16 @@ def state(v):
     if v not in ("stored", "zero"):
         raise ValueError(v)
     return v
+
+
+def beta(v):
+    """A --priority-beta value: B, or B0,B1,N (linear from B0 to B1 over N updates)."""
+    parts = v.split(",")
+    if len(parts) == 1:
+        return float(v)
+    if len(parts) != 3:
+        raise ValueError(v)
+    return (float(parts[0]), float(parts[1]), int(parts[2]))
 
 
 # --sweep names -> (the constructor's argument, the value type). --window is shared by the
@@ -124,6 +142,14 @@ def parse_args(argv=None):
                     help="burn-in steps before a window, a multiple of --window")
     ap.add_argument("--initial-state", choices=("stored", "zero"), default="stored",
                     help="a window's starting state: the snapshot recorded while acting, or zero")
+    ap.add_argument("--priority-alpha", type=float, default=None, metavar="A",
+                    help="prioritized replay windows with exponent A (needs --window; 0: uniform "
+                         "over the memory's windows)")
+    ap.add_argument("--priority-beta", type=beta, default=0.6, metavar="B | B0,B1,N",
+                    help="importance-weight exponent, or a linear schedule over N updates")
+    ap.add_argument("--priority-eta", type=float, default=0.9, metavar="H",
+                    help="a window's priority: H max + (1 - H) mean of its |TD errors|")
+    ap.add_argument("--priority-eps", type=float, default=1e-3, metavar="X")
     ap.add_argument("--learners", type=int, default=None,
                     help="P independent learners in one run, each on envs / P instances")
     ap.add_argument("--sweep", action="append", default=None, metavar="NAME=v1,v2,...",
@@ -135,8 +161,16 @@ def parse_args(argv=None):
     check_pool_arguments(a)  # refused here, before any GPU call
     try:
         check_window(a.window, a.burn_in, a.initial_state)
+        check_priority(a.window, a.priority_alpha, a.priority_beta, a.priority_eta, a.priority_eps)
     except ValueError as e:
         ap.error(str(e))
+    given = [f for f in ("--priority-beta", "--priority-eta", "--priority-eps")
+             if ap.get_default(f[2:].replace("-", "_")) != getattr(a, f[2:].replace("-", "_"))]
+    if a.priority_alpha is None and given:
+        ap.error(f"{', '.join(given)} need --priority-alpha")
+    if a.learners is not None and a.priority_alpha is not None:
+        ap.error("--priority-alpha: prioritized replay is the single trainer's option; "
+                 "VectorRecurrentDQNPopulation (--learners) does not take it yet")
     if a.learners is None:
         if a.sweep or a.seeds:
             ap.error("--sweep / --seeds need --learners")
@@ -212,7 +246,9 @@ def main(argv=None):
         memory_size=a.memory, target_update_frequency=a.target_update,
         explore_actions=a.explore_actions, train_every=a.train_every, seed=a.seed,
         bank=not a.no_bank, algorithm=a.algo, window=a.window, burn_in=a.burn_in,
-        initial_state=a.initial_state, archive=a.archive or None)
+        initial_state=a.initial_state, archive=a.archive or None,
+        priority_alpha=a.priority_alpha, priority_beta=a.priority_beta,
+        priority_eta=a.priority_eta, priority_eps=a.priority_eps)
     if a.resume:
         from .checkpoint import load_checkpoint
         load_checkpoint(a.resume, tr)
@@ -237,6 +273,7 @@ def main(argv=None):
                       "wins": tr.wins, "updates": tr.updates, "batch_episodes": a.batch,
                       "seed": a.seed, "window": a.window, "burn_in": a.burn_in,
                       "initial_state": a.initial_state if a.window else None,
+                      **({} if a.priority_alpha is None else {"priority": tr._priority_settings()}),
                       "win_rate_greedy_untrained": before,
                       "win_rate_greedy": after, "eval_mazes": a.eval_mazes, "eval_steps": k,
                       **explored}),

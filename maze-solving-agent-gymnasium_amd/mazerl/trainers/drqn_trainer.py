@@ -63,6 +63,36 @@ option window=T, burn_in=K, initial_state="stored" | "zero"; window=None is the 
      training steps, r_t alone only at t = n - 1 of a terminated episode (a window that ends
      before the episode does bootstraps from x_{s+m}); loss = sum (Q_t[a_t] - y_t)^2 / sum m.
 K must be a multiple of T. Overlapping windows (a stride other than T) are out of scope.
+Prioritized windows (the other half of R2D2's replay) are the option priority_alpha=a with
+window=T (priority_beta, priority_eta, priority_eps beside it; R2D2's values are 0.9, 0.6, 0.9);
+priority_alpha=None is the trainer above, and then nothing below is allocated or launched. Every
+window (slot, j) of the ring carries a mass: an unsigned 32-bit fixed-point priority with 20
+fractional bits, 0 = no such window. Masses are integers on purpose: every sum over them is exact
+in 64 bits, so the sampler does not depend on a reduction's order and equals a host model bit for
+bit (tests/drqn_prio_model.py). With W = ceil(L / T):
+ 10. entry: a stored episode of n steps gives its ceil(n / T) windows the mass prio_max, the
+     largest mass any update has written so far (2^20, priority 1, at the start); the slot's other
+     entries are 0 and its sum psum[slot] = ceil(n / T) prio_max. mz_drqn_prio_store follows
+     mz_drqn_store's slot rule and validity tests and runs before it, as mz_drqn_snap_store does;
+ 11. sampling, in departure 8's place: with replacement and stratified, in integers. S = the sum
+     of psum over the slots; batch position e draws t = lo + mulhi64(r, hi - lo), lo =
+     floor(e S / E), hi = floor((e + 1) S / E), r a 64-bit word of a Philox stream of its own keyed
+     by (seed, update count, e), and takes the window (slot, j) with prefix <= t < prefix + mass,
+     the prefix running slot-major, j-minor. Two positions may hold the same window. b, k, m and
+     the directory follow from j as in 8-9. A window's share deviates from mass / S by at most
+     E / S. Its importance weight is w_e = (float) (M_min / M_e)^beta, M_e its mass when sampled
+     and M_min the batch's smallest: (N P)^-beta / max, in which N and S cancel. With alpha = 0
+     every window has mass 2^20: sampling is uniform over the memory's windows, without departure
+     8's bias towards short episodes;
+ 12. after the source forward, before the backward: with a_i = |Q_i[a_i] - y_i| (float32) over the
+     window's m training steps, pr = eta max a_i + (1 - eta) mean a_i (float64, the mean summed in
+     time order), mass = clamp(llrint((pr + eps)^alpha 2^20), 1, 2^30) goes to (slot, j), prio_max
+     becomes the maximum of itself and the batch's masses, and every touched slot's psum is
+     recomputed from its W entries. Then the residuals d and the window's loss term are scaled by
+     w_e, so the unchanged backward gives the gradient and value of loss = sum_e w_e sum_t
+     (Q_t[a_t] - y_t)^2 / sum m.
+VectorRecurrentDQNPopulation does not take the priority arguments yet (the kernels are already in
+the per-learner row form).
 VectorRecurrentDQNPopulation takes the same three arguments (T shared, K and the initial state per
 learner); its learner p is this trainer with (T, K_p, S_p), departures 7-9 included. On the device
 the two are one: every mz_drqn_* entry point here launches the population's kernel with P = 1.
@@ -70,6 +100,7 @@ RecurrentDQNBase holds what the two classes share on the host.
 """
 import copy
 import ctypes as C
+import math
 
 import torch
 
@@ -82,6 +113,7 @@ from .episodic import EpisodicTrainer, episode_bound
 FORMAT = "mazerl.VectorRecurrentDQNTrainer/1"
 EVAL_KEY = 0x4556414C
 ROW, STASH, PARAMS = 8, 192, 5252
+PRIO_ONE = 1 << 20  # the mass of priority 1 (MZ_DRQN_PRIO_FRAC)
 U64 = 0xFFFFFFFFFFFFFFFF
 
 
@@ -104,6 +136,26 @@ def check_window(window, burn_in, initial_state):
                          f"(got {window!r}, {burn_in!r}, {initial_state!r})")
 
 
+def check_priority(window, alpha, beta, eta, eps):
+    """The prioritized-replay arguments' rules (departures 10-12); ValueError otherwise. alpha None
+    is off; beta is a number or (beta0, beta1, updates)."""
+    if alpha is None:
+        return
+
+    def num(v, lo=0.0, hi=float("inf")):
+        return isinstance(v, (int, float)) and not isinstance(v, bool) and \
+            math.isfinite(v) and lo <= v <= hi
+
+    sched = isinstance(beta, (tuple, list)) and len(beta) == 3 and num(beta[0]) and \
+        num(beta[1]) and isinstance(beta[2], int) and not isinstance(beta[2], bool) and beta[2] >= 1
+    if window is None or not num(alpha) or not (num(beta) or sched) or not num(eta, 0.0, 1.0) or \
+            not num(eps) or eps <= 0:
+        raise ValueError("priority_alpha needs window=T; priority_alpha >= 0, priority_beta >= 0 "
+                         "or (beta0, beta1, updates >= 1), priority_eta in [0, 1], priority_eps > "
+                         f"0, all finite (got window {window!r}, {alpha!r}, {beta!r}, {eta!r}, "
+                         f"{eps!r})")
+
+
 class RecurrentDQNBase(EpisodicTrainer):
     """What the trainer and the population (drqn_population.py) share: the buffers, the scan and
     store of a vector step, the overflow look, the window settings and the greedy rollout. The
@@ -111,6 +163,7 @@ class RecurrentDQNBase(EpisodicTrainer):
     (_snap_store_call, _store_call) take (P, b) where the trainer's take B; nothing else differs."""
     _REC = ("rec_x", "rec_a", "rec_r")
     _KIND = "trainer"  # (load_state_dict's error text)
+    priority_alpha = None  # (prioritized windows: the trainer's option; the population has none)
 
     def _alloc(self, P=None, state=False):
         """The per-instance buffers, the replay ring, an update's directory and row buffers
@@ -142,6 +195,13 @@ class RecurrentDQNBase(EpisodicTrainer):
             self.snap_rec = torch.zeros(B, self.snaps, 2 * HIDDEN, dtype=f32, **kw)
             self.mem_state = torch.zeros(*lead, self.capacity, self.snaps, 2 * HIDDEN, dtype=f32,
                                          **kw)
+        if self.priority_alpha is not None:
+            # a window's mass: u32 fixed point, 20 fractional bits (<= 2^30, so int32 holds it);
+            # a slot's sum (< 2^63, so int64 holds it); the largest mass written, from priority 1
+            self.mem_prio = torch.zeros(self.capacity, self.snaps, dtype=i32, **kw)
+            self.mem_psum = torch.zeros(self.capacity, dtype=i64, **kw)
+            self.prio_max = torch.full((1,), PRIO_ONE, dtype=i32, **kw)
+            self.isw = torch.ones(E, dtype=f32, **kw)
         self.d_slot = torch.zeros(*lead, E, dtype=i32, **kw)
         self.d_len = torch.zeros(*lead, E, dtype=i32, **kw)
         self.d_off = torch.zeros(*lead, E, dtype=i64, **kw)
@@ -164,6 +224,11 @@ class RecurrentDQNBase(EpisodicTrainer):
         if self._state:  # (reads the ring's head, which the store advances)
             self._snap_store_call(L, self.window, *fin, self.snap_rec.data_ptr(), self.capacity,
                                   self.mem_state.data_ptr(), self.ring.data_ptr(), st)
+        if self.priority_alpha is not None:  # (reads the head too: new windows enter at prio_max)
+            N.check(self.lib.mz_drqn_prio_store(
+                HIDDEN, env.num_envs, L, self.window, *fin, self.capacity,
+                self.mem_prio.data_ptr(), self.mem_psum.data_ptr(), self.prio_max.data_ptr(),
+                self.ring.data_ptr(), st))
         self._store_call(L, *fin, self.rec_x.data_ptr(), self.rec_a.data_ptr(),
                          self.rec_r.data_ptr(), self.capacity, self.mem.data_ptr(),
                          self.mem_len.data_ptr(), self.mem_term.data_ptr(), self.ring.data_ptr(), st)
@@ -215,9 +280,14 @@ class VectorRecurrentDQNTrainer(RecurrentDQNBase):
                  epsilon_decay=1000.0, discount_factor=0.99, batch_size=32, memory_size=20000,
                  target_update_frequency=10, explore_actions=4, train_every=1, seed=0, bank=True,
                  curriculum=False, growth=None, algorithm="r-prim", bank_candidates=1, window=None,
-                 burn_in=0, initial_state="stored", archive=None):
-        """archive: EpisodicTrainer's explored-maze pool (None: off)."""
+                 burn_in=0, initial_state="stored", archive=None, priority_alpha=None,
+                 priority_beta=0.6, priority_eta=0.9, priority_eps=1e-3):
+        """archive: EpisodicTrainer's explored-maze pool (None: off). priority_alpha: prioritized
+        replay windows (departures 10-12; None: off, nothing of it is allocated or launched);
+        priority_beta: a number, or (beta0, beta1, updates) for a linear schedule over the update
+        count."""
         check_window(window, burn_in, initial_state)
+        check_priority(window, priority_alpha, priority_beta, priority_eta, priority_eps)
         if batch_size < 1 or memory_size < batch_size or train_every < 1 or \
                 target_update_frequency < 1 or explore_actions not in (1, 2, 3, 4):
             raise ValueError("batch_size >= 1, memory_size >= batch_size, train_every >= 1, "
@@ -244,6 +314,11 @@ class VectorRecurrentDQNTrainer(RecurrentDQNBase):
         self.seed = int(seed)
         self.window = None if window is None else int(window)
         self.burn_in, self.initial_state = int(burn_in), initial_state
+        if priority_alpha is not None:
+            self.priority_alpha = float(priority_alpha)
+            self.priority_beta = float(priority_beta) if isinstance(priority_beta, (int, float)) \
+                else (float(priority_beta[0]), float(priority_beta[1]), int(priority_beta[2]))
+            self.priority_eta, self.priority_eps = float(priority_eta), float(priority_eps)
         self.steps_done = 0   # the eps clock
         self.counter = 0      # vector steps (the exploration draws' counter)
         self.updates = 0
@@ -285,7 +360,15 @@ class VectorRecurrentDQNTrainer(RecurrentDQNBase):
     def sample(self):
         """E distinct slots and the directory (d_slot, d_len, d_off, d_tot), keyed by the update
         count; windowed: the same slots, one window each and the window directory (wdir, d_off,
-        d_tot)."""
+        d_tot). Prioritized: E windows in proportion to their mass, the same directory, and the
+        importance weights (isw)."""
+        if self.priority_alpha is not None:
+            N.check(self.lib.mz_drqn_prio_sample(
+                self.seed & U64, self.updates & U64, HIDDEN, self.batch_size, self.L, self.window,
+                self.burn_in, self.capacity, self.mem_len.data_ptr(), self.mem_prio.data_ptr(),
+                self.mem_psum.data_ptr(), self.wdir.data_ptr(), self.d_off.data_ptr(),
+                self.d_tot.data_ptr(), self.isw.data_ptr(), self.beta(), self._stream()))
+            return
         if self.window is not None:
             N.check(self.lib.mz_drqn_window_sample(
                 self.seed & U64, self.updates & U64, HIDDEN, self.batch_size, self.L, self.window,
@@ -335,6 +418,12 @@ class VectorRecurrentDQNTrainer(RecurrentDQNBase):
             self._ps, HIDDEN, 0, E, L, T, K, self.capacity, self.gamma, self.mem.data_ptr(),
             self.mem_term.data_ptr(), state, *dirs, self.qmax.data_ptr(), self.stash.data_ptr(),
             self.qa.data_ptr(), self.y.data_ptr(), self.d.data_ptr(), self.ep_loss.data_ptr(), st))
+        if self.priority_alpha is not None:  # the new masses; d and ep_loss times the weights
+            N.check(self.lib.mz_drqn_prio_update(
+                HIDDEN, E, L, T, self.capacity, *dirs, self.qa.data_ptr(), self.y.data_ptr(),
+                self.d.data_ptr(), self.ep_loss.data_ptr(), self.isw.data_ptr(),
+                self.priority_alpha, self.priority_eta, self.priority_eps,
+                self.mem_prio.data_ptr(), self.mem_psum.data_ptr(), self.prio_max.data_ptr(), st))
         N.check(self.lib.mz_drqn_window_backward(
             self._ps, HIDDEN, E, L, T, K, self.capacity, self.mem.data_ptr(), *dirs,
             self.stash.data_ptr(), self.d.data_ptr(), self.ep_loss.data_ptr(),
@@ -359,8 +448,26 @@ class VectorRecurrentDQNTrainer(RecurrentDQNBase):
         if self.filled >= self.batch_size and self.counter % self.train_every == 0:
             self._update()
 
+    def beta(self):
+        """The importance exponent of the coming update: priority_beta, or its linear schedule
+        over the update count (computed here, on the host)."""
+        b = self.priority_beta
+        if isinstance(b, float):
+            return b
+        return b[0] + (b[1] - b[0]) * min(self.updates / b[2], 1.0)
+
     def _log_fields(self):
-        return {"loss": float(self.loss)}
+        if self.priority_alpha is None:
+            return {"loss": float(self.loss)}
+        return {"loss": float(self.loss), "prio_max": int(self.prio_max) / PRIO_ONE,
+                "mean_weight": float(self.isw.mean())}
+
+    def _priority_settings(self):
+        if self.priority_alpha is None:
+            return None
+        b = self.priority_beta
+        return {"alpha": self.priority_alpha, "beta": b if isinstance(b, float) else list(b),
+                "eta": self.priority_eta, "eps": self.priority_eps}
 
     # ---- evaluation (vector_trainer.evaluate) ---------------------------------------------------
     def evaluator(self):
@@ -396,6 +503,11 @@ class VectorRecurrentDQNTrainer(RecurrentDQNBase):
         if self.stored:
             sd["snap_rec"] = self.snap_rec.clone()
             sd["mem_state"] = self.mem_state[:n].clone()
+        if self.priority_alpha is not None:
+            sd["priority"] = self._priority_settings()
+            sd["mem_prio"] = self.mem_prio[:n].clone()
+            sd["mem_psum"] = self.mem_psum[:n].clone()
+            sd["prio_max"] = self.prio_max.clone()
         sd.update({k: getattr(self, k).clone() for k in self._OWN})
         sd.update({k: getattr(self, k)[:n].clone() for k in ("mem", "mem_len", "mem_term")})
         sd["source"] = {k: v.clone() for k, v in self.source_net.state_dict().items()}
@@ -406,6 +518,10 @@ class VectorRecurrentDQNTrainer(RecurrentDQNBase):
 
     def load_state_dict(self, sd):
         self._check_window_settings(sd)
+        # (a checkpoint of a trainer without priorities has no "priority" key: priority_alpha=None)
+        if sd.get("priority") != self._priority_settings():
+            raise ValueError(f"the checkpoint's prioritized replay {sd.get('priority')} differs "
+                             f"from this trainer's {self._priority_settings()}")
         self._load_common(sd)
         with torch.no_grad():
             self.source_net.load_state_dict(sd["source"])
@@ -423,6 +539,10 @@ class VectorRecurrentDQNTrainer(RecurrentDQNBase):
         if self.stored:
             self.snap_rec.copy_(sd["snap_rec"])
             self.mem_state[:n].copy_(sd["mem_state"])
+        if self.priority_alpha is not None:
+            self.mem_prio[:n].copy_(sd["mem_prio"])
+            self.mem_psum[:n].copy_(sd["mem_psum"])
+            self.prio_max.copy_(sd["prio_max"])
 
 
 def evaluate_plain(learner, num_mazes, dim, algorithm="r-prim", seed=0x7E57, toroidal=False,
