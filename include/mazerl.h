@@ -1038,6 +1038,48 @@ int mz_drqn_pop_window_backward(const float* params_dev, int32_t hidden, int32_t
                                 const double* ep_loss_dev, float* gpart_dev, float* grads_dev,
                                 float* loss_dev, void* stream);
 
+/* ---- Prioritized replay windows per learner (VectorRecurrentDQNPopulation(priority_alpha=...)) --
+ * The three mz_drqn_prio_* kernels over P learners in one launch each, learner p on its own rows:
+ * mem_prio_dev uint32 [P][capacity][W], mem_psum_dev uint64 [P][capacity], prio_max_dev uint32 [P],
+ * isw_dev f32 [P][E]; the directory, win_off_dev, win_tot_dev and the row buffers as the
+ * mz_drqn_pop_window_* entry points lay them out. Learner p's outputs are, bit for bit, what the
+ * single entry point writes on its block with its values. due_dev (int32 [P], may be NULL: all
+ * due): a learner with due_dev[p] == 0 has nothing read or written. Each refuses, before any GPU
+ * call, P < 1, b < 1, any other null pointer, and all the single entry points refuse. The
+ * per-learner values (beta_dev, alpha_dev, eta_dev, eps_dev, burn_in_dev) live on the device and
+ * cannot be refused here: the caller validates them before it uploads them. */
+
+/* mz_drqn_prio_store for every learner, BEFORE mz_drqn_pop_store of the same vector step: learner
+ * p's run of the finished list by mz_drqn_pop_store's rule, its k-th episode's windows into slot
+ * (head_p + k) mod capacity at the mass prio_max_dev[p]. ring_dev is int64 [P][2]. */
+int mz_drqn_pop_prio_store(int32_t hidden, int32_t P, int32_t b, int32_t L, int32_t T,
+                           const int32_t* fin_id_dev, const int32_t* fin_len_dev,
+                           const int32_t* fin_count_dev, int64_t capacity, uint32_t* mem_prio_dev,
+                           uint64_t* mem_psum_dev, const uint32_t* prio_max_dev,
+                           const int64_t* ring_dev, void* stream);
+
+/* mz_drqn_prio_sample per due learner, one workgroup each, keyed by (seed_dev[p], counter_dev[p])
+ * with K = burn_in_dev[p] (<= K_max) and the importance exponent beta_dev[p] (float64 [P], each
+ * finite and >= 0). T is shared. */
+int mz_drqn_pop_prio_sample(const uint64_t* seed_dev, const uint64_t* counter_dev,
+                            const int32_t* burn_in_dev, const double* beta_dev,
+                            const int32_t* due_dev, int32_t hidden, int32_t P, int32_t E, int32_t L,
+                            int32_t T, int32_t K_max, int64_t capacity, const int32_t* mem_len_dev,
+                            const uint32_t* mem_prio_dev, const uint64_t* mem_psum_dev,
+                            int32_t* wdir_dev, int64_t* win_off_dev, int64_t* win_tot_dev,
+                            float* isw_dev, void* stream);
+
+/* mz_drqn_prio_update per due learner, one workgroup each, with alpha_dev[p] (finite, >= 0),
+ * eta_dev[p] (in [0, 1]) and eps_dev[p] (finite, > 0), float64 [P] each: between
+ * mz_drqn_pop_window_forward (source) and mz_drqn_pop_window_backward. */
+int mz_drqn_pop_prio_update(const double* alpha_dev, const double* eta_dev, const double* eps_dev,
+                            const int32_t* due_dev, int32_t hidden, int32_t P, int32_t E, int32_t L,
+                            int32_t T, int64_t capacity, const int32_t* wdir_dev,
+                            const int64_t* win_off_dev, const int64_t* win_tot_dev,
+                            const float* qa_dev, const float* y_dev, float* d_dev,
+                            double* ep_loss_dev, const float* isw_dev, uint32_t* mem_prio_dev,
+                            uint64_t* mem_psum_dev, uint32_t* prio_max_dev, void* stream);
+
 /* The target sync (lstm_dqn_agent.py update_target: target.load_state_dict(source.state_dict()))
  * of the learners with mask_dev[p] != 0: row p of dst_dev <- row p of src_dev ([P][5252]). */
 int mz_drqn_pop_sync(const float* src_dev, float* dst_dev, const int32_t* mask_dev, int32_t P,

@@ -1977,21 +1977,57 @@ static int drqn_prio_args(const char* who, int32_t hidden, int32_t T, int32_t K,
   return MZ_OK;
 }
 
+// One validator per stage, as everywhere above: the single entry point is P = 1 with the per-learner
+// arrays null, the population's has checked that its own are there.
+static int drqn_prio_store(const char* who, int32_t hidden, int32_t P, int32_t b,
+                           int32_t max_blocks, MzDrqnPrioStore s, void* stream) {
+  if (int rc = drqn_pop_args(who, hidden, P, b, "instances per learner")) return rc;
+  if (int rc = drqn_prio_args(who, hidden, s.T, 0, 1, s.L, s.cap)) return rc;
+  if (!s.fin_id || !s.fin_len || !s.fin_count || !s.mem_prio || !s.mem_psum || !s.prio_max ||
+      !s.ring)
+    return fail(MZ_EINVAL, "%s: null pointer", who);
+  s.B = P * b;
+  StreamGuard g(stream);
+  MZ_HIP(mz_launch_drqn_prio_store(MzDrqnPopPrioStore{s, P, b}, b < max_blocks ? b : max_blocks,
+                                   static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
 int mz_drqn_prio_store(int32_t hidden, int32_t B, int32_t L, int32_t T, const int32_t* fin_id_dev,
                        const int32_t* fin_len_dev, const int32_t* fin_count_dev, int64_t capacity,
                        uint32_t* mem_prio_dev, uint64_t* mem_psum_dev, const uint32_t* prio_max_dev,
                        const int64_t* ring_dev, void* stream) {
-  const char* who = "mz_drqn_prio_store";
-  if (int rc = drqn_pop_args(who, hidden, 1, B, "instances per learner")) return rc;
-  if (int rc = drqn_prio_args(who, hidden, T, 0, 1, L, capacity)) return rc;
-  if (!fin_id_dev || !fin_len_dev || !fin_count_dev || !mem_prio_dev || !mem_psum_dev ||
-      !prio_max_dev || !ring_dev)
+  return drqn_prio_store("mz_drqn_prio_store", hidden, 1, B, 2048,
+                         MzDrqnPrioStore{0, L, T, fin_id_dev, fin_len_dev, fin_count_dev, capacity,
+                                         mem_prio_dev, mem_psum_dev, prio_max_dev, ring_dev},
+                         stream);
+}
+
+int mz_drqn_pop_prio_store(int32_t hidden, int32_t P, int32_t b, int32_t L, int32_t T,
+                           const int32_t* fin_id_dev, const int32_t* fin_len_dev,
+                           const int32_t* fin_count_dev, int64_t capacity, uint32_t* mem_prio_dev,
+                           uint64_t* mem_psum_dev, const uint32_t* prio_max_dev,
+                           const int64_t* ring_dev, void* stream) {
+  return drqn_prio_store("mz_drqn_pop_prio_store", hidden, P, b, 256,
+                         MzDrqnPrioStore{0, L, T, fin_id_dev, fin_len_dev, fin_count_dev, capacity,
+                                         mem_prio_dev, mem_psum_dev, prio_max_dev, ring_dev},
+                         stream);
+}
+
+static int drqn_prio_sample(const char* who, int32_t hidden, int32_t P, const uint64_t* seed_dev,
+                            const uint64_t* counter_dev, const int32_t* burn_in_dev,
+                            const double* beta_dev, const int32_t* due_dev,
+                            const MzDrqnPrioSample& s, void* stream) {
+  if (int rc = drqn_pop_args(who, hidden, P, s.E, "E")) return rc;
+  if (int rc = drqn_prio_args(who, hidden, s.T, s.K, s.E, s.L, s.cap)) return rc;
+  if (!s.mem_len || !s.mem_prio || !s.mem_psum || !s.wdir || !s.w_off || !s.w_tot || !s.isw)
     return fail(MZ_EINVAL, "%s: null pointer", who);
+  if (!(s.beta >= 0.0 && std::isfinite(s.beta)))
+    return fail(MZ_EINVAL, "%s: beta %g (>= 0)", who, s.beta);
   StreamGuard g(stream);
-  MzDrqnPrioStore s{B, L, T, fin_id_dev, fin_len_dev, fin_count_dev, capacity, mem_prio_dev,
-                    mem_psum_dev, prio_max_dev, ring_dev};
-  MZ_HIP(mz_launch_drqn_prio_store(MzDrqnPopPrioStore{s, 1, B}, B < 2048 ? B : 2048,
-                                   static_cast<hipStream_t>(stream)));
+  MZ_HIP(mz_launch_drqn_prio_sample(
+      MzDrqnPopPrioSample{s, P, seed_dev, counter_dev, burn_in_dev, due_dev, beta_dev},
+      static_cast<hipStream_t>(stream)));
   return MZ_OK;
 }
 
@@ -2000,16 +2036,41 @@ int mz_drqn_prio_sample(uint64_t seed, uint64_t counter, int32_t hidden, int32_t
                         const uint32_t* mem_prio_dev, const uint64_t* mem_psum_dev,
                         int32_t* wdir_dev, int64_t* win_off_dev, int64_t* win_tot_dev,
                         float* isw_dev, double beta, void* stream) {
-  const char* who = "mz_drqn_prio_sample";
-  if (int rc = drqn_prio_args(who, hidden, T, K, E, L, capacity)) return rc;
-  if (!mem_len_dev || !mem_prio_dev || !mem_psum_dev || !wdir_dev || !win_off_dev ||
-      !win_tot_dev || !isw_dev)
+  return drqn_prio_sample(
+      "mz_drqn_prio_sample", hidden, 1, nullptr, nullptr, nullptr, nullptr, nullptr,
+      MzDrqnPrioSample{seed, counter, E, L, T, K, capacity, mem_len_dev, mem_prio_dev,
+                       mem_psum_dev, wdir_dev, win_off_dev, win_tot_dev, isw_dev, beta}, stream);
+}
+
+int mz_drqn_pop_prio_sample(const uint64_t* seed_dev, const uint64_t* counter_dev,
+                            const int32_t* burn_in_dev, const double* beta_dev,
+                            const int32_t* due_dev, int32_t hidden, int32_t P, int32_t E, int32_t L,
+                            int32_t T, int32_t K_max, int64_t capacity, const int32_t* mem_len_dev,
+                            const uint32_t* mem_prio_dev, const uint64_t* mem_psum_dev,
+                            int32_t* wdir_dev, int64_t* win_off_dev, int64_t* win_tot_dev,
+                            float* isw_dev, void* stream) {
+  if (!seed_dev || !counter_dev || !burn_in_dev || !beta_dev)
+    return fail(MZ_EINVAL, "mz_drqn_pop_prio_sample: null pointer");
+  return drqn_prio_sample(
+      "mz_drqn_pop_prio_sample", hidden, P, seed_dev, counter_dev, burn_in_dev, beta_dev, due_dev,
+      MzDrqnPrioSample{0, 0, E, L, T, K_max, capacity, mem_len_dev, mem_prio_dev, mem_psum_dev,
+                       wdir_dev, win_off_dev, win_tot_dev, isw_dev, 0.0}, stream);
+}
+
+static int drqn_prio_update(const char* who, int32_t hidden, int32_t P, const double* alpha_dev,
+                            const double* eta_dev, const double* eps_dev, const int32_t* due_dev,
+                            const MzDrqnPrioUpdate& u, void* stream) {
+  if (int rc = drqn_pop_args(who, hidden, P, u.E, "E")) return rc;
+  if (int rc = drqn_prio_args(who, hidden, u.T, 0, u.E, u.L, u.cap)) return rc;
+  if (!u.wdir || !u.w_off || !u.w_tot || !u.qa || !u.y || !u.d || !u.ep_loss || !u.isw ||
+      !u.mem_prio || !u.mem_psum || !u.prio_max)
     return fail(MZ_EINVAL, "%s: null pointer", who);
-  if (!(beta >= 0.0 && std::isfinite(beta))) return fail(MZ_EINVAL, "%s: beta %g (>= 0)", who, beta);
+  if (!(u.alpha >= 0.0 && std::isfinite(u.alpha)) || !(u.eta >= 0.0 && u.eta <= 1.0) ||
+      !(u.eps > 0.0 && std::isfinite(u.eps)))
+    return fail(MZ_EINVAL, "%s: alpha %g (>= 0), eta %g (0..1), eps %g (> 0)", who, u.alpha, u.eta,
+                u.eps);
   StreamGuard g(stream);
-  MzDrqnPrioSample s{seed, counter, E, L, T, K, capacity, mem_len_dev, mem_prio_dev, mem_psum_dev,
-                     wdir_dev, win_off_dev, win_tot_dev, isw_dev, beta};
-  MZ_HIP(mz_launch_drqn_prio_sample(MzDrqnPopPrioSample{s, 1, nullptr, nullptr, nullptr, nullptr},
+  MZ_HIP(mz_launch_drqn_prio_update(MzDrqnPopPrioUpdate{u, P, due_dev, alpha_dev, eta_dev, eps_dev},
                                     static_cast<hipStream_t>(stream)));
   return MZ_OK;
 }
@@ -2020,21 +2081,28 @@ int mz_drqn_prio_update(int32_t hidden, int32_t E, int32_t L, int32_t T, int64_t
                         float* d_dev, double* ep_loss_dev, const float* isw_dev, double alpha,
                         double eta, double eps, uint32_t* mem_prio_dev, uint64_t* mem_psum_dev,
                         uint32_t* prio_max_dev, void* stream) {
-  const char* who = "mz_drqn_prio_update";
-  if (int rc = drqn_prio_args(who, hidden, T, 0, E, L, capacity)) return rc;
-  if (!wdir_dev || !win_off_dev || !win_tot_dev || !qa_dev || !y_dev || !d_dev || !ep_loss_dev ||
-      !isw_dev || !mem_prio_dev || !mem_psum_dev || !prio_max_dev)
-    return fail(MZ_EINVAL, "%s: null pointer", who);
-  if (!(alpha >= 0.0 && std::isfinite(alpha)) || !(eta >= 0.0 && eta <= 1.0) ||
-      !(eps > 0.0 && std::isfinite(eps)))
-    return fail(MZ_EINVAL, "%s: alpha %g (>= 0), eta %g (0..1), eps %g (> 0)", who, alpha, eta, eps);
-  StreamGuard g(stream);
-  MzDrqnPrioUpdate u{E, L, T, capacity, wdir_dev, win_off_dev, win_tot_dev, qa_dev, y_dev, d_dev,
-                     ep_loss_dev, isw_dev, alpha, eta, eps, mem_prio_dev, mem_psum_dev,
-                     prio_max_dev};
-  MZ_HIP(mz_launch_drqn_prio_update(MzDrqnPopPrioUpdate{u, 1, nullptr},
-                                    static_cast<hipStream_t>(stream)));
-  return MZ_OK;
+  return drqn_prio_update(
+      "mz_drqn_prio_update", hidden, 1, nullptr, nullptr, nullptr, nullptr,
+      MzDrqnPrioUpdate{E, L, T, capacity, wdir_dev, win_off_dev, win_tot_dev, qa_dev, y_dev, d_dev,
+                       ep_loss_dev, isw_dev, alpha, eta, eps, mem_prio_dev, mem_psum_dev,
+                       prio_max_dev}, stream);
+}
+
+int mz_drqn_pop_prio_update(const double* alpha_dev, const double* eta_dev, const double* eps_dev,
+                            const int32_t* due_dev, int32_t hidden, int32_t P, int32_t E, int32_t L,
+                            int32_t T, int64_t capacity, const int32_t* wdir_dev,
+                            const int64_t* win_off_dev, const int64_t* win_tot_dev,
+                            const float* qa_dev, const float* y_dev, float* d_dev,
+                            double* ep_loss_dev, const float* isw_dev, uint32_t* mem_prio_dev,
+                            uint64_t* mem_psum_dev, uint32_t* prio_max_dev, void* stream) {
+  if (!alpha_dev || !eta_dev || !eps_dev)
+    return fail(MZ_EINVAL, "mz_drqn_pop_prio_update: null pointer");
+  // the scalar fallbacks are never read (the arrays are there): any value in range
+  return drqn_prio_update(
+      "mz_drqn_pop_prio_update", hidden, P, alpha_dev, eta_dev, eps_dev, due_dev,
+      MzDrqnPrioUpdate{E, L, T, capacity, wdir_dev, win_off_dev, win_tot_dev, qa_dev, y_dev, d_dev,
+                       ep_loss_dev, isw_dev, 0.0, 0.0, 1.0, mem_prio_dev, mem_psum_dev,
+                       prio_max_dev}, stream);
 }
 
 int mz_drqn_pop_sync(const float* src_dev, float* dst_dev, const int32_t* mask_dev, int32_t P,

@@ -1169,7 +1169,7 @@ __device__ __forceinline__ void drqn_prio_sample_body(const MzDrqnPrioSample& q)
   }
 }
 
-// one workgroup per learner, on its masses, directory block, seed, update count and burn-in
+// one workgroup per learner, on its masses, directory block, seed, update count, burn-in and beta
 __global__ __launch_bounds__(PRIO_T) void k_drqn_prio_sample(MzDrqnPopPrioSample q) {
   const int p = blockIdx.x;
   if (q.due && q.due[p] == 0) return;
@@ -1178,6 +1178,7 @@ __global__ __launch_bounds__(PRIO_T) void k_drqn_prio_sample(MzDrqnPopPrioSample
   if (q.burn_in) s.K = drqn_pop_burn_in(q.burn_in, p, s.T, q.s.K);
   if (q.seed) s.seed = q.seed[p];
   if (q.counter) s.counter = q.counter[p];
+  if (q.beta) s.beta = q.beta[p];
   s.mem_len += (size_t)p * s.cap;
   s.mem_prio += (size_t)p * s.cap * drqn_windows(s.L, s.T);
   s.mem_psum += (size_t)p * s.cap;
@@ -1252,12 +1253,15 @@ __device__ __forceinline__ void drqn_prio_update_body(const MzDrqnPrioUpdate& q)
   }
 }
 
-// one workgroup per learner
+// one workgroup per learner, with its alpha, eta and eps
 __global__ __launch_bounds__(PRIO_T) void k_drqn_prio_update(MzDrqnPopPrioUpdate q) {
   const int p = blockIdx.x;
   if (q.due && q.due[p] == 0) return;
   MzDrqnPrioUpdate u = q.u;
   const size_t E = (size_t)u.E, rows = E * (min(u.T, u.L) + MZ_DRQN_WIN_PAD);
+  if (q.alpha) u.alpha = q.alpha[p];
+  if (q.eta) u.eta = q.eta[p];
+  if (q.eps) u.eps = q.eps[p];
   u.wdir += p * 5 * E;
   u.w_off += p * E;
   u.w_tot += 2 * (size_t)p;

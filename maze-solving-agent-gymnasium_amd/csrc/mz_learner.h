@@ -326,11 +326,13 @@ struct MzDrqnPopPrioSample {
   int P;
   const uint64_t* seed; const uint64_t* counter;  // [P]; null: s.seed, s.counter
   const int32_t* burn_in; const int32_t* due;     // [P]; burn_in null: s.K
+  const double* beta;                             // [P]; null: s.beta
 };
 struct MzDrqnPopPrioUpdate {
   MzDrqnPrioUpdate u;
   int P;
   const int32_t* due;                        // [P]
+  const double* alpha; const double* eta; const double* eps;  // [P]; null: u.alpha, u.eta, u.eps
 };
 hipError_t mz_launch_drqn_prio_store(const MzDrqnPopPrioStore& q, int blocks, hipStream_t s);
 hipError_t mz_launch_drqn_prio_sample(const MzDrqnPopPrioSample& q, hipStream_t s);

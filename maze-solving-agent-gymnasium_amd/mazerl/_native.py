@@ -58,6 +58,7 @@ EXPORTS = ["mz_last_error", "mz_device_count", "mz_create", "mz_destroy", "mz_lo
            "mz_drqn_pop_sample", "mz_drqn_pop_seq_forward", "mz_drqn_pop_seq_backward",
            "mz_drqn_pop_sync", "mz_drqn_pop_snap_store", "mz_drqn_pop_window_sample",
            "mz_drqn_pop_window_forward", "mz_drqn_pop_window_backward",
+           "mz_drqn_pop_prio_store", "mz_drqn_pop_prio_sample", "mz_drqn_pop_prio_update",
            "mz_adamw_pop", "mz_qact_prepare", "mz_qact",
            "mz_qact_workspace_floats", "mz_qtab_states", "mz_qtab_act", "mz_qtab_update",
            "mz_qtab_hash_act", "mz_qtab_hash_update", "mz_qtab_hash_rehash", "mz_qtab_hash_lookup",
@@ -226,6 +227,9 @@ def load(build_if_missing=True):
         [vp] * 6
     L.mz_drqn_pop_window_forward.argtypes = [vp] + [C.c_int32] * 7 + [C.c_int64] + [vp] * 17
     L.mz_drqn_pop_window_backward.argtypes = [vp] + [C.c_int32] * 6 + [C.c_int64] + [vp] * 13
+    L.mz_drqn_pop_prio_store.argtypes = [C.c_int32] * 5 + [vp] * 3 + [C.c_int64] + [vp] * 5
+    L.mz_drqn_pop_prio_sample.argtypes = [vp] * 5 + [C.c_int32] * 6 + [C.c_int64] + [vp] * 8
+    L.mz_drqn_pop_prio_update.argtypes = [vp] * 4 + [C.c_int32] * 5 + [C.c_int64] + [vp] * 12
     L.mz_adamw_pop.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int64, vp, vp, vp, C.c_double,
                                C.c_double, C.c_double, C.c_double, C.c_float, C.c_float,
                                C.c_int32, vp]

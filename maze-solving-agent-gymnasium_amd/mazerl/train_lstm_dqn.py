@@ -17,9 +17,10 @@ stored | zero starts from the recurrent state recorded while acting or from zero
 
 --learners P trains P independent learners in one run (trainers/drqn_population.py), each on
 envs / P instances; --seeds and --sweep NAME=v1,v2,... (repeatable; NAME one of lr, gamma,
-eps-start, eps-final, eps-decay, target-update, seed, burn-in, initial-state; P values or one) set
-them apart. The final line then reports every learner's trained greedy win-rate on the same mazes,
-their mean and spread, and every learner's window settings.
+eps-start, eps-final, eps-decay, target-update, seed, burn-in, initial-state, priority-alpha,
+priority-beta, priority-eta, priority-eps; P values or one) set them apart. The final line then
+reports every learner's trained greedy win-rate on the same mazes, their mean and spread, and every
+learner's window and priority settings.
 
   python -m mazerl.train_lstm_dqn --dim 41 --learners 16 --window 40 --burn-in 40 \\
       --sweep initial-state=stored,stored,...,zero,zero --seeds 0,1,...
@@ -30,9 +31,19 @@ swept); --burn-in and --initial-state are per learner.
 --priority-alpha A beside --window samples the windows in proportion to (their TD error)^A over
 the whole memory, with importance weights of exponent --priority-beta B (or B0,B1,N: linear over N
 updates); --priority-eta H and --priority-eps X shape a window's priority (departures 10-12). A = 0
-is uniform over the memory's windows. The population (--learners) does not take these yet.
+is uniform over the memory's windows.
 
   python -m mazerl.train_lstm_dqn --dim 41 --window 40 --burn-in 40 --priority-alpha 0.9
+
+With --learners the exponent is per learner and comes through --sweep priority-alpha=A or
+=A1,A2,... (a value may be none: that learner keeps the uniform-per-episode window sampler);
+--priority-beta, --priority-eta and --priority-eps then apply to every prioritized learner unless
+swept too (a schedule inside a sweep is written B0:B1:N). The final line lists every learner's
+settings beside its greedy win rate (by_learner).
+
+  python -m mazerl.train_lstm_dqn --dim 41 --learners 12 --window 40 --burn-in 40 \\
+      --sweep priority-alpha=none,none,none,none,0,0,0,0,0.9,0.9,0.9,0.9 \\
+      --sweep priority-beta=0.6,0.6,0.6,0.6,0,0,0,0,0.6,0.6,0.6,0.6 --seeds 0,1,2,3,0,1,2,3,0,1,2,3
 
 --archive C keeps the mazes the run trains on in a MazePool of C entries (with --learners: one
 pool of C entries per learner, all filled by one launch per vector step) and the final line gains
@@ -59,9 +70,15 @@ def state(v):
     return v
 
 
+def alpha(v):
+    """A priority-alpha value of a sweep: a number, or none (that learner is not prioritized)."""
+    return None if v.strip().lower() == "none" else float(v)
+
+
 def beta(v):
-    """A --priority-beta value: B, or B0,B1,N (linear from B0 to B1 over N updates)."""
-    parts = v.split(",")
+    """A --priority-beta value: B, or B0,B1,N (linear from B0 to B1 over N updates; inside a
+    --sweep, whose values the commas separate, B0:B1:N)."""
+    parts = v.replace(":", ",").split(",")
     if len(parts) == 1:
         return float(v)
     if len(parts) != 3:
@@ -74,7 +91,9 @@ def beta(v):
 SWEEPABLE = {"lr": ("lr", float), "gamma": ("discount_factor", float),
              "eps-start": ("starting_epsilon", float), "eps-final": ("final_epsilon", float),
              "eps-decay": ("epsilon_decay", float), "target-update": ("target_update_frequency", int),
-             "seed": ("seed", int), "burn-in": ("burn_in", int), "initial-state": ("initial_state", state)}
+             "seed": ("seed", int), "burn-in": ("burn_in", int), "initial-state": ("initial_state", state),
+             "priority-alpha": ("priority_alpha", alpha), "priority-beta": ("priority_beta", beta),
+             "priority-eta": ("priority_eta", float), "priority-eps": ("priority_eps", float)}
 
 
 def parse_sweeps(sweeps, seeds, P):
@@ -154,7 +173,8 @@ def parse_args(argv=None):
                     help="P independent learners in one run, each on envs / P instances")
     ap.add_argument("--sweep", action="append", default=None, metavar="NAME=v1,v2,...",
                     help="per-learner values (P or one) of lr, gamma, eps-start, eps-final, "
-                         "eps-decay, target-update or seed; repeatable")
+                         "eps-decay, target-update, seed, burn-in, initial-state or "
+                         "priority-alpha / -beta / -eta / -eps; repeatable")
     ap.add_argument("--seeds", default=None, metavar="s1,s2,...", help="--sweep seed=...")
     add_pool_arguments(ap, "the run (with --learners: each learner)")
     a = ap.parse_args(argv)
@@ -166,11 +186,11 @@ def parse_args(argv=None):
         ap.error(str(e))
     given = [f for f in ("--priority-beta", "--priority-eta", "--priority-eps")
              if ap.get_default(f[2:].replace("-", "_")) != getattr(a, f[2:].replace("-", "_"))]
-    if a.priority_alpha is None and given:
+    if a.learners is None and a.priority_alpha is None and given:
         ap.error(f"{', '.join(given)} need --priority-alpha")
     if a.learners is not None and a.priority_alpha is not None:
-        ap.error("--priority-alpha: prioritized replay is the single trainer's option; "
-                 "VectorRecurrentDQNPopulation (--learners) does not take it yet")
+        ap.error("--priority-alpha is the single trainer's flag; with --learners the exponent is "
+                 "per learner: --sweep priority-alpha=A (or A1,A2,..., a value may be none)")
     if a.learners is None:
         if a.sweep or a.seeds:
             ap.error("--sweep / --seeds need --learners")
@@ -182,9 +202,30 @@ def parse_args(argv=None):
         a.per_learner = parse_sweeps(a.sweep, a.seeds, a.learners)
         for K in a.per_learner.get("burn_in", ()):  # every learner's K_p against the shared T
             check_window(a.window, K, a.initial_state)
+        per = a.per_learner
+        alphas = per.get("priority_alpha", [None] * a.learners)
+        for p, al in enumerate(alphas):  # every learner's priority settings against the shared T
+            check_priority(a.window, al, *(per[k][p] if k in per else getattr(a, k) for k in
+                                           ("priority_beta", "priority_eta", "priority_eps")))
     except ValueError as e:
         ap.error(str(e))
+    swept = ["--sweep " + k.replace("_", "-") for k in per
+             if k in ("priority_beta", "priority_eta", "priority_eps")]
+    if all(al is None for al in alphas) and (given or swept):
+        ap.error(f"{', '.join(given + swept)} need --sweep priority-alpha=... with a value that "
+                 "is not none")
     return a
+
+
+def by_learner(tr, rates):
+    """A prioritized population's report: the per-learner priority settings and, learner by
+    learner, its seed and settings beside its greedy win rate. Empty without priorities."""
+    pr = tr._priority_settings()
+    if pr is None:
+        return {}
+    rows = [{"learner": p, "seed": tr.seed[p], **{"priority_" + k: pr[k][p] for k in pr},
+             "win_rate_greedy": rates[p]} for p in range(tr.P)]
+    return {"priority": pr, "by_learner": rows}
 
 
 def main_population(a):
@@ -195,7 +236,8 @@ def main_population(a):
     kw = dict(lr=a.lr, starting_epsilon=a.eps_start, final_epsilon=a.eps_final,
               epsilon_decay=a.eps_decay, discount_factor=a.gamma,
               target_update_frequency=a.target_update, seed=a.seed, burn_in=a.burn_in,
-              initial_state=a.initial_state)
+              initial_state=a.initial_state, priority_beta=a.priority_beta,
+              priority_eta=a.priority_eta, priority_eps=a.priority_eps)
     kw.update(a.per_learner)
     tr = VectorRecurrentDQNPopulation(
         env, dev, learners=a.learners, batch_size=a.batch, memory_size=a.memory,
@@ -225,6 +267,7 @@ def main_population(a):
                       "wins": tr.wins, "updates": tr.updates, "batch_episodes": a.batch,
                       "per_learner": {k: v for k, v in a.per_learner.items()},
                       "window": tr._window_settings(),  # T and every learner's K_p, S_p
+                      **by_learner(tr, after),
                       "replay_bytes": tr.memory_bytes()["replay"],
                       "win_rate_greedy_untrained": before, "win_rate_greedy": after,
                       "win_rate_greedy_spread": spread(after), "eval_mazes": a.eval_mazes,

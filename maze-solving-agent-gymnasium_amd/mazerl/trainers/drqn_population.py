@@ -43,6 +43,25 @@ learner never reads it. A checkpoint then also holds T and the two per-learner l
 stored, snap_rec and each ring's filled slots of mem_state; it loads only into a population with
 the same window settings.
 
+Prioritized windows (priority_alpha, priority_beta, priority_eta, priority_eps: each a value or a
+list of P; with every alpha None, the default, this is the population above: nothing of it is
+allocated or launched, the same bits, the same checkpoint keys). An entry of priority_alpha may be
+None: that learner keeps the uniform-per-episode window sampler. priority_beta is a number, a tuple
+(beta0, beta1, updates) - one schedule for every learner - or a list of P numbers or such triples;
+a learner's schedule runs over its own update count and is evaluated on the host, as the single
+trainer's beta(), and goes up with the per-update scalars. Learner p with an alpha is
+VectorRecurrentDQNTrainer(window=T, priority_alpha=a_p, priority_beta=b_p, priority_eta=h_p,
+priority_eps=x_p) on its block, bit for bit (its departures 10-12). Then mem_prio
+[P][capacity][ceil(L / T)], mem_psum [P][capacity], prio_max [P] and isw [P][E] exist for all
+learners (a uniform learner's masses are kept by the store launch and never read). Per update:
+mz_drqn_pop_prio_sample under the mask due-and-prioritized, mz_drqn_pop_window_sample under
+due-and-uniform (each launched only where its mask has an entry; the uniform sampler's smallest
+fill is taken over its own mask), and mz_drqn_pop_prio_update under the first mask between the
+source forward and the backward. The forward, backward, reduce, AdamW and sync launches run under
+the one due mask, unchanged. A checkpoint then also holds the per-learner settings, each ring's
+filled slots of mem_prio and mem_psum, and prio_max; it loads only into a population with the same
+settings, and a checkpoint without them only into a population without priorities.
+
 curriculum="global" counts wins across all instances and would couple the learners: it is refused.
 With bank=False a learner's whole run is independent of the other learners, bit for bit. With the
 winner bank the maze a winner receives depends on how many instances of other learners won before
@@ -56,8 +75,8 @@ import torch
 from .. import _native as N
 from ..agents.lstm_dqn_agent import DQN, ETA_MIN, HIDDEN, T_MAX, epsilon_at
 from ..agents.rf_agent import cosine_lr
-from .drqn_trainer import (EVAL_KEY, PARAMS, ROW, STASH, U64, RecurrentDQNBase, _Evaluator,
-                           check_window)
+from .drqn_trainer import (EVAL_KEY, PARAMS, PRIO_ONE, ROW, STASH, U64, RecurrentDQNBase,
+                           _Evaluator, check_priority, check_window)
 from .episodic import episode_bound
 
 FORMAT = "mazerl.VectorRecurrentDQNPopulation/1"
@@ -87,10 +106,12 @@ def _signed(u):
     return u - (1 << 64) if u >> 63 else u
 
 
-def footprint(P, B, L, E, capacity, window=None, stored=False):
+def footprint(P, B, L, E, capacity, window=None, stored=False, prio=False):
     """Bytes of the replay rings, the in-flight records, and an update's stash and row buffers;
     windowed: the row buffers hold E (min(T, L) + 2) rows, and with stored state the state memory
-    (P capacity ceil(L / T) snapshots of 256 B) and the in-flight snapshots are added."""
+    (P capacity ceil(L / T) snapshots of 256 B) and the in-flight snapshots are added; prioritized:
+    the masses (P capacity ceil(L / T) words and a 64-bit sum per slot), prio_max, the importance
+    weights and the three float64 settings per learner."""
     rows = E * (L + 1) if window is None else E * (min(window, L) + 2)
     ring = P * capacity * ((L + 1) * ROW * 4 + 8)
     records = B * ((L + 1) * 6 * 4 + L * 4 + L * 8)
@@ -102,6 +123,9 @@ def footprint(P, B, L, E, capacity, window=None, stored=False):
         out["state"], out["snap_rec"] = P * capacity * snaps, B * snaps
         out["update"] += P * 5 * E * 4
         out["total"] = ring + records + out["update"] + out["state"] + out["snap_rec"]
+    if prio:
+        out["prio"] = P * (capacity * (((L - 1) // window + 1) * 4 + 8) + 4 + E * 4 + 3 * 8)
+        out["total"] += out["prio"]
     return out
 
 
@@ -129,10 +153,12 @@ class VectorRecurrentDQNPopulation(RecurrentDQNBase):
                  epsilon_decay=1000.0, discount_factor=0.99, batch_size=32, memory_size=20000,
                  target_update_frequency=10, explore_actions=4, train_every=1, seed=0, bank=True,
                  curriculum=False, growth=None, algorithm="r-prim", bank_candidates=1, window=None,
-                 burn_in=0, initial_state="stored", archive=None):
+                 burn_in=0, initial_state="stored", archive=None, priority_alpha=None,
+                 priority_beta=0.6, priority_eta=0.9, priority_eps=1e-3):
         """archive (None: off): an int C or a MazePoolSet of this env with one group per learner
         — every learner's explored mazes in a pool of C entries of its own, all filled by one
-        launch per vector step (evaluate_explored_all)."""
+        launch per vector step (evaluate_explored_all). priority_alpha .. priority_eps: prioritized
+        replay windows per learner (the module's docstring; every alpha None: off)."""
         P = int(learners)
         if P < 1 or env.num_envs % P:
             raise ValueError(f"env.num_envs {env.num_envs} must be a multiple of learners {P} >= 1")
@@ -146,6 +172,7 @@ class VectorRecurrentDQNPopulation(RecurrentDQNBase):
             check_window(window, K, S)
         self.window = None if window is None else int(window)
         self.stored = [self.window is not None and S == "stored" for S in self.initial_state]
+        self._priority(P, window, priority_alpha, priority_beta, priority_eta, priority_eps)
         self.tuf = per_learner(target_update_frequency, P, "target_update_frequency", int)
         if batch_size < 1 or memory_size < batch_size or train_every < 1 or min(self.tuf) < 1 or \
                 explore_actions not in (1, 2, 3, 4):
@@ -162,7 +189,7 @@ class VectorRecurrentDQNPopulation(RecurrentDQNBase):
         self.explore_actions, self.train_every = int(explore_actions), int(train_every)
         B, E = env.num_envs, self.batch_size
         L = episode_bound(env.max_dim, env.toroidal)
-        need = footprint(P, B, L, E, self.capacity, self.window, any(self.stored))
+        need = footprint(P, B, L, E, self.capacity, self.window, any(self.stored), any(self.prio))
         dev = torch.device(device)
         if dev.type == "cuda":
             free, _ = torch.cuda.mem_get_info(dev)
@@ -173,6 +200,8 @@ class VectorRecurrentDQNPopulation(RecurrentDQNBase):
                     + (f"{need['state'] / 2 ** 30:.2f} GiB of state memory (mem_state) with "
                        f"{need['snap_rec'] / 2 ** 30:.2f} GiB of in-flight snapshots (snap_rec) and "
                        if any(self.stored) else "") +
+                    (f"{need['prio'] / 2 ** 30:.2f} GiB of window priorities (mem_prio, mem_psum) "
+                     "and " if any(self.prio) else "") +
                     f"{need['total'] / 2 ** 30:.2f} GiB in all; {free / 2 ** 30:.2f} GiB are free. "
                     "Lower memory_size or learners.")
         super().__init__(env, device, bank=bank, curriculum=curriculum, growth=growth,
@@ -199,23 +228,67 @@ class VectorRecurrentDQNPopulation(RecurrentDQNBase):
         self.gamma_dev = torch.tensor(self.gamma, dtype=f32, **kw)
         self.seed_dev = torch.tensor([_signed(s) for s in self.seed], dtype=i64, **kw)
         self.eps_dev = torch.zeros(P, dtype=f32, **kw)
-        # the per-update scalars, one upload: sample counters (int64), due, sync, lr (f32 bits)
-        self.upd = torch.zeros(5 * P, dtype=i32, **kw)
+        # the per-update scalars, one upload: sample counters (int64), due, sync, lr (f32 bits);
+        # prioritized: then the two samplers' masks and every learner's beta (float64)
+        self.upd = torch.zeros((9 * P + P % 2) if any(self.prio) else 5 * P, dtype=i32, **kw)
         self.cnt_dev = self.upd[:2 * P].view(i64)
         self.due_dev, self.sync_dev = self.upd[2 * P:3 * P], self.upd[3 * P:4 * P]
-        self.lr_dev = self.upd[4 * P:].view(f32)
+        self.lr_dev = self.upd[4 * P:5 * P].view(f32)
         self._alloc(P, any(self.stored))
+        if any(self.prio):
+            self.due_prio_dev, self.due_uni_dev = self.upd[5 * P:6 * P], self.upd[6 * P:7 * P]
+            self.beta_dev = self.upd[7 * P + P % 2:].view(torch.float64)  # (8-byte aligned)
+            f64 = lambda vs, ph: torch.tensor(  # noqa: E731 (a uniform learner: a valid placeholder)
+                [ph if v is None else v for v in vs], dtype=torch.float64, **kw)
+            self.prio_alpha_dev = f64(self.priority_alpha, 0.0)
+            self.prio_eta_dev = f64(self.priority_eta, 0.0)
+            self.prio_eps_dev = f64(self.priority_eps, 1.0)
+        self._prio_due = False  # whether the update under way has a due prioritized learner
         if self.window is not None:
             self.burn_in_dev = torch.tensor(self.burn_in, dtype=i32, **kw)
             self.stored_dev = torch.tensor([int(s) for s in self.stored], dtype=i32, **kw)
         self.last_lr = [None] * P
         self.last_due = [False] * P  # the learners the last vector step updated
 
+    def _priority(self, P, window, alpha, beta, eta, eps):
+        """The per-learner priority settings, checked learner by learner before anything touches
+        the GPU: prio[p] (whether learner p is prioritized) and, when any is, priority_alpha / _beta
+        / _eta / _eps as lists of P (None throughout for a uniform learner)."""
+        same = lambda v: v  # noqa: E731 (check_priority wants the values as they were given)
+        alpha = per_learner(alpha, P, "priority_alpha", same)
+        beta = [beta] * P if isinstance(beta, tuple) else per_learner(beta, P, "priority_beta", same)
+        eta = per_learner(eta, P, "priority_eta", same)
+        eps = per_learner(eps, P, "priority_eps", same)
+        for a, b, h, x in zip(alpha, beta, eta, eps):
+            check_priority(window, a, b, h, x)
+        self.prio = [a is not None for a in alpha]
+        if not any(self.prio):
+            return
+        on = lambda vs, f: [f(v) if q else None for v, q in zip(vs, self.prio)]  # noqa: E731
+        self.priority_alpha = on(alpha, float)
+        self.priority_beta = on(beta, lambda b: float(b) if isinstance(b, (int, float)) else
+                                (float(b[0]), float(b[1]), int(b[2])))
+        self.priority_eta, self.priority_eps = on(eta, float), on(eps, float)
+
+    def beta(self, p):
+        """Learner p's importance exponent at its coming update (the single trainer's beta())."""
+        b = self.priority_beta[p]
+        if isinstance(b, float):
+            return b
+        return b[0] + (b[1] - b[0]) * min(self.updates[p] / b[2], 1.0)
+
+    def _priority_settings(self):
+        if self.priority_alpha is None:
+            return None
+        return {"alpha": list(self.priority_alpha),
+                "beta": [list(b) if isinstance(b, tuple) else b for b in self.priority_beta],
+                "eta": list(self.priority_eta), "eps": list(self.priority_eps)}
+
     # ---- per-learner access -------------------------------------------------------------------
     def memory_bytes(self):
         """The replay, record, stash and row-buffer footprint in bytes (footprint())."""
         return footprint(self.P, self.env.num_envs, self.L, self.batch_size, self.capacity,
-                         self.window, any(self.stored))
+                         self.window, any(self.stored), any(self.prio))
 
     def epsilon(self, p):
         return epsilon_at(self.steps_done[p], self.starting_epsilon[p], self.final_epsilon[p],
@@ -341,6 +414,9 @@ class VectorRecurrentDQNPopulation(RecurrentDQNBase):
     def _snap_store_call(self, *tail):
         N.check(self.lib.mz_drqn_pop_snap_store(HIDDEN, self.P, self.b, *tail))
 
+    def _prio_store_call(self, *tail):
+        N.check(self.lib.mz_drqn_pop_prio_store(HIDDEN, self.P, self.b, *tail))
+
     def _store_call(self, *tail):
         env = self.env
         N.check(self.lib.mz_drqn_pop_store(env.obs6.data_ptr(), env.terminated.data_ptr(), self.P,
@@ -348,21 +424,42 @@ class VectorRecurrentDQNPopulation(RecurrentDQNBase):
 
     def _upload(self, due, sync, lr):
         P = self.P
-        buf = np.zeros(5 * P, np.int32)
+        buf = np.zeros(self.upd.numel(), np.int32)
         buf[:2 * P].view(np.int64)[:] = self.updates
         buf[2 * P:3 * P] = due
         buf[3 * P:4 * P] = sync
-        buf[4 * P:].view(np.float32)[:] = lr
+        buf[4 * P:5 * P].view(np.float32)[:] = lr
+        if any(self.prio):  # the two samplers' masks; beta_p at learner p's own update count
+            buf[5 * P:6 * P] = [d and q for d, q in zip(due, self.prio)]
+            buf[6 * P:7 * P] = [d and not q for d, q in zip(due, self.prio)]
+            buf[7 * P + P % 2:].view(np.float64)[:] = [self.beta(p) if q else 0.0
+                                                       for p, q in enumerate(self.prio)]
+            self._prio_due = bool(buf[5 * P:6 * P].any())
         self.upd.copy_(torch.from_numpy(buf))
 
     def sample(self, due):
         """E distinct slots and the directory of every due learner, keyed by its update count;
-        windowed: the same slots, one window each and the learner's window directory."""
+        windowed: the same slots, one window each and the learner's window directory; a prioritized
+        learner: E windows in proportion to their mass and its importance weights."""
+        mask = self.due_dev
+        if any(self.prio):
+            if self._prio_due:
+                N.check(self.lib.mz_drqn_pop_prio_sample(
+                    self.seed_dev.data_ptr(), self.cnt_dev.data_ptr(), self.burn_in_dev.data_ptr(),
+                    self.beta_dev.data_ptr(), self.due_prio_dev.data_ptr(), HIDDEN, self.P,
+                    self.batch_size, self.L, self.window, max(self.burn_in), self.capacity,
+                    self.mem_len.data_ptr(), self.mem_prio.data_ptr(), self.mem_psum.data_ptr(),
+                    self.wdir.data_ptr(), self.d_off.data_ptr(), self.d_tot.data_ptr(),
+                    self.isw.data_ptr(), self._stream()))
+            due = [d and not q for d, q in zip(due, self.prio)]
+            if not any(due):
+                return
+            mask = self.due_uni_dev
         filled = min(f for f, d in zip(self.filled, due) if d)
         if self.window is not None:
             N.check(self.lib.mz_drqn_pop_window_sample(
                 self.seed_dev.data_ptr(), self.cnt_dev.data_ptr(), self.burn_in_dev.data_ptr(),
-                self.due_dev.data_ptr(), HIDDEN, self.P, self.batch_size, self.L, self.window,
+                mask.data_ptr(), HIDDEN, self.P, self.batch_size, self.L, self.window,
                 max(self.burn_in), self.capacity, filled, self.ring.data_ptr(),
                 self.mem_len.data_ptr(), self.wdir.data_ptr(), self.d_off.data_ptr(),
                 self.d_tot.data_ptr(), self._stream()))
@@ -418,6 +515,13 @@ class VectorRecurrentDQNPopulation(RecurrentDQNBase):
             self.mem.data_ptr(), self.mem_term.data_ptr(), state, *dirs, self.qmax.data_ptr(),
             self.stash.data_ptr(), self.qa.data_ptr(), self.y.data_ptr(), self.d.data_ptr(),
             self.ep_loss.data_ptr(), st))
+        if self._prio_due:  # the new masses; d and ep_loss times the weights
+            N.check(self.lib.mz_drqn_pop_prio_update(
+                self.prio_alpha_dev.data_ptr(), self.prio_eta_dev.data_ptr(),
+                self.prio_eps_dev.data_ptr(), self.due_prio_dev.data_ptr(), HIDDEN, P, E, L, T,
+                self.capacity, *dirs, self.qa.data_ptr(), self.y.data_ptr(), self.d.data_ptr(),
+                self.ep_loss.data_ptr(), self.isw.data_ptr(), self.mem_prio.data_ptr(),
+                self.mem_psum.data_ptr(), self.prio_max.data_ptr(), st))
         N.check(self.lib.mz_drqn_pop_window_backward(
             self.src.data_ptr(), HIDDEN, P, E, L, T, K, self.capacity, burn, due,
             self.mem.data_ptr(), *dirs, self.stash.data_ptr(), self.d.data_ptr(),
@@ -458,8 +562,13 @@ class VectorRecurrentDQNPopulation(RecurrentDQNBase):
             self._update(due)
 
     def _log_fields(self):
-        return {"loss": [round(v, 6) for v in self.loss.tolist()],
-                "epsilon": [round(self.epsilon(p), 4) for p in range(self.P)]}
+        out = {"loss": [round(v, 6) for v in self.loss.tolist()],
+               "epsilon": [round(self.epsilon(p), 4) for p in range(self.P)]}
+        if any(self.prio):  # (None for a uniform learner)
+            on = lambda vs: [v if q else None for v, q in zip(vs, self.prio)]  # noqa: E731
+            out["prio_max"] = on([v / PRIO_ONE for v in self.prio_max.tolist()])
+            out["mean_weight"] = on(self.isw.mean(dim=1).tolist())
+        return out
 
     # ---- checkpoint / resume (mazerl/checkpoint.py) -------------------------------------------
     _OWN = ("h", "c", "ring", "pool", "loss", "src", "tgt", "exp_avg", "exp_avg_sq", "step")
@@ -480,11 +589,25 @@ class VectorRecurrentDQNPopulation(RecurrentDQNBase):
         if any(self.stored):
             sd["snap_rec"] = self.snap_rec.clone()
             sd["mem_state"] = [self.mem_state[p, :n].clone() for p, n in enumerate(counts)]
+        if any(self.prio):
+            sd["priority"] = self._priority_settings()
+            for k in ("mem_prio", "mem_psum"):
+                sd[k] = [getattr(self, k)[p, :n].clone() for p, n in enumerate(counts)]
+            sd["prio_max"] = self.prio_max.clone()
         return sd
 
     def load_state_dict(self, sd):
         self._check_window_settings(sd)
+        # (a checkpoint of a population without priorities has no "priority" key)
+        if sd.get("priority") != self._priority_settings():
+            raise ValueError(f"the checkpoint's prioritized replay {sd.get('priority')} differs "
+                             f"from this population's {self._priority_settings()}")
         self._load_common(sd)
+        if any(self.prio):
+            for k in ("mem_prio", "mem_psum"):
+                for p, part in enumerate(sd[k]):
+                    getattr(self, k)[p, :part.shape[0]].copy_(part)
+            self.prio_max.copy_(sd["prio_max"])
         if any(self.stored):
             self.snap_rec.copy_(sd["snap_rec"])
             for p, part in enumerate(sd["mem_state"]):

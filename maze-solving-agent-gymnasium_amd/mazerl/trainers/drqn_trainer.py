@@ -91,8 +91,9 @@ bit (tests/drqn_prio_model.py). With W = ceil(L / T):
      recomputed from its W entries. Then the residuals d and the window's loss term are scaled by
      w_e, so the unchanged backward gives the gradient and value of loss = sum_e w_e sum_t
      (Q_t[a_t] - y_t)^2 / sum m.
-VectorRecurrentDQNPopulation does not take the priority arguments yet (the kernels are already in
-the per-learner row form).
+VectorRecurrentDQNPopulation takes the four priority arguments per learner (an alpha of None keeps
+that learner on departure 8's sampler); its learner p is this trainer with learner p's values,
+departures 10-12 included, and the three kernels serve all prioritized learners in one launch each.
 VectorRecurrentDQNPopulation takes the same three arguments (T shared, K and the initial state per
 learner); its learner p is this trainer with (T, K_p, S_p), departures 7-9 included. On the device
 the two are one: every mz_drqn_* entry point here launches the population's kernel with P = 1.
@@ -160,10 +161,13 @@ class RecurrentDQNBase(EpisodicTrainer):
     """What the trainer and the population (drqn_population.py) share: the buffers, the scan and
     store of a vector step, the overflow look, the window settings and the greedy rollout. The
     population's ring, directory and row buffers carry a leading P dimension and its store calls
-    (_snap_store_call, _store_call) take (P, b) where the trainer's take B; nothing else differs."""
+    (_snap_store_call, _prio_store_call, _store_call) take (P, b) where the trainer's take B;
+    nothing else differs."""
     _REC = ("rec_x", "rec_a", "rec_r")
     _KIND = "trainer"  # (load_state_dict's error text)
-    priority_alpha = None  # (prioritized windows: the trainer's option; the population has none)
+    # prioritized windows: None is off. The trainer holds its alpha; the population None when every
+    # learner's is None and the list of its learners' alphas otherwise.
+    priority_alpha = None
 
     def _alloc(self, P=None, state=False):
         """The per-instance buffers, the replay ring, an update's directory and row buffers
@@ -198,10 +202,10 @@ class RecurrentDQNBase(EpisodicTrainer):
         if self.priority_alpha is not None:
             # a window's mass: u32 fixed point, 20 fractional bits (<= 2^30, so int32 holds it);
             # a slot's sum (< 2^63, so int64 holds it); the largest mass written, from priority 1
-            self.mem_prio = torch.zeros(self.capacity, self.snaps, dtype=i32, **kw)
-            self.mem_psum = torch.zeros(self.capacity, dtype=i64, **kw)
-            self.prio_max = torch.full((1,), PRIO_ONE, dtype=i32, **kw)
-            self.isw = torch.ones(E, dtype=f32, **kw)
+            self.mem_prio = torch.zeros(*lead, self.capacity, self.snaps, dtype=i32, **kw)
+            self.mem_psum = torch.zeros(*lead, self.capacity, dtype=i64, **kw)
+            self.prio_max = torch.full(lead or (1,), PRIO_ONE, dtype=i32, **kw)
+            self.isw = torch.ones(*lead, E, dtype=f32, **kw)
         self.d_slot = torch.zeros(*lead, E, dtype=i32, **kw)
         self.d_len = torch.zeros(*lead, E, dtype=i32, **kw)
         self.d_off = torch.zeros(*lead, E, dtype=i64, **kw)
@@ -225,10 +229,9 @@ class RecurrentDQNBase(EpisodicTrainer):
             self._snap_store_call(L, self.window, *fin, self.snap_rec.data_ptr(), self.capacity,
                                   self.mem_state.data_ptr(), self.ring.data_ptr(), st)
         if self.priority_alpha is not None:  # (reads the head too: new windows enter at prio_max)
-            N.check(self.lib.mz_drqn_prio_store(
-                HIDDEN, env.num_envs, L, self.window, *fin, self.capacity,
-                self.mem_prio.data_ptr(), self.mem_psum.data_ptr(), self.prio_max.data_ptr(),
-                self.ring.data_ptr(), st))
+            self._prio_store_call(L, self.window, *fin, self.capacity, self.mem_prio.data_ptr(),
+                                  self.mem_psum.data_ptr(), self.prio_max.data_ptr(),
+                                  self.ring.data_ptr(), st)
         self._store_call(L, *fin, self.rec_x.data_ptr(), self.rec_a.data_ptr(),
                          self.rec_r.data_ptr(), self.capacity, self.mem.data_ptr(),
                          self.mem_len.data_ptr(), self.mem_term.data_ptr(), self.ring.data_ptr(), st)
@@ -351,6 +354,9 @@ class VectorRecurrentDQNTrainer(RecurrentDQNBase):
 
     def _snap_store_call(self, *tail):
         N.check(self.lib.mz_drqn_snap_store(HIDDEN, self.env.num_envs, *tail))
+
+    def _prio_store_call(self, *tail):
+        N.check(self.lib.mz_drqn_prio_store(HIDDEN, self.env.num_envs, *tail))
 
     def _store_call(self, *tail):
         env = self.env
