@@ -3,23 +3,25 @@ nn.LSTMCell(6, 32) + nn.Linear(32, 4) Q-network over obs6, whole episodes in
 SequentialExperienceReplayMemory, lib/replay_memory.py:26-43) over B instances at once, on plain
 (enrich=False) or Enrich envs, euclidean or toroidal. Only obs6 is read.
 
-Per vector step, with no host round trip once the memory holds a batch (csrc/mz_drqn.hip):
-  act      mz_drqn_act: the cell and the head from each instance's (h, c) ([32][B] in HBM), the
+Per vector step, with no device-to-host read once the memory holds a batch (csrc/mz_drqn.hip; every
+launch but the snapshot is a population entry point, mz_drqn_pop_*, with P = 1; the host sends
+eps per step and a block of scalars per update, two small host-to-device copies):
+  act      mz_drqn_pop_act: the cell and the head from each instance's (h, c) ([32][B] in HBM), the
            eps-greedy draw, the record of (x_t, a_t) at t[i];
   step     the env step;
   scan     mz_ppo_scan, unchanged (the f32 reward widened to its float64 record; t[i] += 1; the
            finished episodes' list in instance order). It drops 1-step episodes, so none reaches
            the memory;
-  store    mz_drqn_store: x_n and each finished episode into ring slot (head + k) mod capacity;
+  store    mz_drqn_pop_store: x_n and each finished episode into ring slot (head + k) mod capacity;
   reset    winners get new mazes, truncated instances restart theirs (schedule.py as REINFORCE);
-  update   when due: mz_drqn_sample (E distinct slots + the batch directory), the target net's
+  update   when due: mz_drqn_pop_sample (E distinct slots + the batch directory), the target net's
            sequence forward (max_a Q'_t), the source net's (Q_t[a_t], y_t, residuals, the stash),
-           mz_drqn_seq_backward (BPTT, gradients reduced in a fixed order into the flat gradient
+           mz_drqn_pop_seq_backward (BPTT, gradients reduced in a fixed order into the flat gradient
            segments), then FlatAdamW (the reference's clamp_(-1, 1) + AdamW in one launch).
 With window=T the update trains on one window of T steps per sampled episode (departures 7-9):
-mz_drqn_snapshot runs before act, mz_drqn_snap_store before store, and the update is
-mz_drqn_window_sample / _forward / _backward; its row buffers hold E (T + 2) rows whatever the maze
-size and the burn-in are. With window=None (the default) none of these is launched.
+mz_drqn_snapshot runs before act, mz_drqn_pop_snap_store before store, and the update is
+mz_drqn_pop_window_sample / _forward / _backward; its row buffers hold E (T + 2) rows whatever the
+maze size and the burn-in are. With window=None (the default) none of these is launched.
 
 The reference defines the net, the gate order, eps = final + (start - final) exp(-steps / decay),
 episodes as the unit of replay sampled without replacement, the MSE loss, the clamp, AdamW at
@@ -51,7 +53,7 @@ option window=T, burn_in=K, initial_state="stored" | "zero"; window=None is the 
      values, computed with the parameters of that moment: they go stale as the net trains, which
      is what the burn-in is for. With initial_state="zero" none is recorded or stored;
   8. the unit of a batch: the memory stays the ring of whole episodes. A batch is E distinct
-     episodes chosen with exactly mz_drqn_sample's draws for the same (seed, update count), then
+     episodes chosen with exactly mz_drqn_pop_sample's draws for the same (seed, update count), then
      one window j per chosen episode, uniform over its ceil(n / T) windows, from a Philox stream of
      its own keyed by (seed, update count, position in the batch). Windows are therefore uniform
      within an episode, not over the memory: a step of a short episode is trained on more often;
@@ -72,8 +74,9 @@ in 64 bits, so the sampler does not depend on a reduction's order and equals a h
 bit (tests/drqn_prio_model.py). With W = ceil(L / T):
  10. entry: a stored episode of n steps gives its ceil(n / T) windows the mass prio_max, the
      largest mass any update has written so far (2^20, priority 1, at the start); the slot's other
-     entries are 0 and its sum psum[slot] = ceil(n / T) prio_max. mz_drqn_prio_store follows
-     mz_drqn_store's slot rule and validity tests and runs before it, as mz_drqn_snap_store does;
+     entries are 0 and its sum psum[slot] = ceil(n / T) prio_max. mz_drqn_pop_prio_store follows
+     mz_drqn_pop_store's slot rule and validity tests and runs before it, as
+     mz_drqn_pop_snap_store does;
  11. sampling, in departure 8's place: with replacement and stratified, in integers. S = the sum
      of psum over the slots; batch position e draws t = lo + mulhi64(r, hi - lo), lo =
      floor(e S / E), hi = floor((e + 1) S / E), r a 64-bit word of a Philox stream of its own keyed
@@ -91,18 +94,23 @@ bit (tests/drqn_prio_model.py). With W = ceil(L / T):
      recomputed from its W entries. Then the residuals d and the window's loss term are scaled by
      w_e, so the unchanged backward gives the gradient and value of loss = sum_e w_e sum_t
      (Q_t[a_t] - y_t)^2 / sum m.
-VectorRecurrentDQNPopulation takes the four priority arguments per learner (an alpha of None keeps
-that learner on departure 8's sampler); its learner p is this trainer with learner p's values,
-departures 10-12 included, and the three kernels serve all prioritized learners in one launch each.
-VectorRecurrentDQNPopulation takes the same three arguments (T shared, K and the initial state per
-learner); its learner p is this trainer with (T, K_p, S_p), departures 7-9 included. On the device
-the two are one: every mz_drqn_* entry point here launches the population's kernel with P = 1.
-RecurrentDQNBase holds what the two classes share on the host.
+The vector step and the update above are written once, for P learners over the mz_drqn_pop_* entry
+points: RecurrentDQNBase below. VectorRecurrentDQNPopulation (drqn_population.py) is that driver
+with P learners, each with its own values of the per-learner arguments (T shared; K, the initial
+state and the four priority arguments per learner, an alpha of None keeping that learner on
+departure 8's sampler); this trainer is the same driver with P = 1. Its ring, directory and row
+buffers without a leading dimension are the [1, ...] layout, its nets' flat parameter and gradient
+buffers begin with a population row, and eps, seed, gamma, the counters and the window and priority
+settings go up as one-element arrays. A class adds its optimizer step and target sync (FlatAdamW and
+copy_flat here, mz_adamw_pop and mz_drqn_pop_sync there), its public surface (scalars here, lists of
+P there) and its checkpoint format. The single-learner mz_drqn_* entry points stay exported
+(include/mazerl.h); of them only mz_drqn_act (the evaluator) and mz_drqn_snapshot are called here.
 """
 import copy
 import ctypes as C
 import math
 
+import numpy as np
 import torch
 
 from .. import _native as N
@@ -114,6 +122,7 @@ from .episodic import EpisodicTrainer, episode_bound
 FORMAT = "mazerl.VectorRecurrentDQNTrainer/1"
 EVAL_KEY = 0x4556414C
 ROW, STASH, PARAMS = 8, 192, 5252
+SHAPES = ((128, 6), (128, 32), (128,), (128,), (4, 32), (4,))  # a net, in state_dict order
 PRIO_ONE = 1 << 20  # the mass of priority 1 (MZ_DRQN_PRIO_FRAC)
 U64 = 0xFFFFFFFFFFFFFFFF
 
@@ -121,7 +130,7 @@ U64 = 0xFFFFFFFFFFFFFFFF
 def param_ptrs(net):
     """The host array of six device pointers the mz_drqn_* entry points take (state_dict order)."""
     ps = list(net.parameters())
-    assert [tuple(p.shape) for p in ps] == [(128, 6), (128, 32), (128,), (128,), (4, 32), (4,)]
+    assert tuple(tuple(p.shape) for p in ps) == SHAPES
     return (C.c_void_p * 6)(*[p.data_ptr() for p in ps])
 
 
@@ -157,23 +166,182 @@ def check_priority(window, alpha, beta, eta, eps):
                          f"{eps!r})")
 
 
-class RecurrentDQNBase(EpisodicTrainer):
-    """What the trainer and the population (drqn_population.py) share: the buffers, the scan and
-    store of a vector step, the overflow look, the window settings and the greedy rollout. The
-    population's ring, directory and row buffers carry a leading P dimension and its store calls
-    (_snap_store_call, _prio_store_call, _store_call) take (P, b) where the trainer's take B;
-    nothing else differs."""
-    _REC = ("rec_x", "rec_a", "rec_r")
-    _KIND = "trainer"  # (load_state_dict's error text)
-    # prioritized windows: None is off. The trainer holds its alpha; the population None when every
-    # learner's is None and the list of its learners' alphas otherwise.
-    priority_alpha = None
+def per_learner(value, P, name, kind=float):
+    """A scalar for all learners or one value per learner -> a list of P."""
+    if isinstance(value, (list, tuple, np.ndarray)):
+        vals = [kind(v) for v in value]
+        if len(vals) == 1:
+            vals = vals * P
+        if len(vals) != P:
+            raise ValueError(f"{name}: {len(vals)} values for {P} learners")
+        return vals
+    return [kind(value)] * P
 
-    def _alloc(self, P=None, state=False):
+
+def _signed(u):
+    """A 64-bit key as the int64 torch stores."""
+    u &= U64
+    return u - (1 << 64) if u >> 63 else u
+
+
+class _PerLearner:
+    """A per-learner host value of the driver. The list of P lives at `_<name>`, which is what
+    RecurrentDQNBase reads and writes; the public attribute is that list for a population and its
+    one entry for the single trainer (_ONE). Assigning gamma, seed, burn_in, priority_eta or
+    priority_eps (the whole value, not an entry of the list) also renews the copy the kernels read
+    (_mirror). initial_state, stored and priority_alpha fix the buffers and are not to be assigned
+    after construction."""
+    MIRRORED = ("gamma", "seed", "burn_in", "priority_eta", "priority_eps")
+
+    def __init__(self, name):
+        self.key, self.mirrored = "_" + name, name in self.MIRRORED
+
+    def __get__(self, obj, cls=None):
+        if obj is None:
+            return self
+        v = getattr(obj, self.key)
+        return v[0] if obj._ONE else v
+
+    def __set__(self, obj, value):
+        setattr(obj, self.key, [value] if obj._ONE else value)
+        if self.mirrored and hasattr(obj, "upd"):  # (the device arrays exist)
+            obj._mirror()
+
+
+class RecurrentDQNBase(EpisodicTrainer):
+    """The host driver of P recurrent DQN learners over B = P b instances, learner p on the block
+    [p b, (p + 1) b): the arguments' checks, the buffers, the vector step (act, scan and store, the
+    cadence), an update (the per-update scalars, the three samplers, the whole-episode and the
+    window chains with the priority update between the source forward and the backward), the
+    greedy rollout and the replay half of a checkpoint. Every launch is an mz_drqn_pop_* entry
+    point. A subclass sets src, tgt and grad (flat [P][5252] rows), _learn() (sample, update, its
+    optimizer step and target sync) and its public surface and checkpoint format; with _ONE it is
+    the single trainer, P = 1, whose buffers carry no leading dimension."""
+    _REC = ("rec_x", "rec_a", "rec_r")
+    _ONE = False
+    _PER = ("lr", "gamma", "starting_epsilon", "final_epsilon", "epsilon_decay", "seed", "tuf",
+            "burn_in", "initial_state", "stored", "priority_beta", "priority_eta", "priority_eps",
+            "steps_done", "updates", "filled", "last_lr")
+
+    def _configure(self, P, B, lr, starting_epsilon, final_epsilon, epsilon_decay, discount_factor,
+                   batch_size, memory_size, target_update_frequency, explore_actions, train_every,
+                   seed, window, burn_in, initial_state, priority_alpha, priority_beta,
+                   priority_eta, priority_eps):
+        """The arguments' checks and the per-learner host values (each argument from lr to seed
+        and from burn_in on: a scalar or a length-P sequence). Touches no GPU."""
+        same = lambda v: v  # noqa: E731 (the checks want the values as they were given)
+        self._burn_in = per_learner(burn_in, P, "burn_in", same)
+        self._initial_state = per_learner(initial_state, P, "initial_state", same)
+        for K, S in zip(self._burn_in, self._initial_state):
+            check_window(window, K, S)
+        self.window = None if window is None else int(window)
+        self._stored = [self.window is not None and S == "stored" for S in self._initial_state]
+        alpha = per_learner(priority_alpha, P, "priority_alpha", same)
+        beta = [priority_beta] * P if isinstance(priority_beta, tuple) else \
+            per_learner(priority_beta, P, "priority_beta", same)
+        eta = per_learner(priority_eta, P, "priority_eta", same)
+        eps = per_learner(priority_eps, P, "priority_eps", same)
+        for a, b, h, x in zip(alpha, beta, eta, eps):
+            check_priority(window, a, b, h, x)
+        # prio[p]: whether learner p is prioritized; its four settings (None for a uniform learner)
+        self.prio = [a is not None for a in alpha]
+        on = lambda vs, f: [f(v) if q else None for v, q in zip(vs, self.prio)]  # noqa: E731
+        self._priority_alpha = on(alpha, float)
+        self._priority_beta = on(beta, lambda b: float(b) if isinstance(b, (int, float)) else
+                                 (float(b[0]), float(b[1]), int(b[2])))
+        self._priority_eta, self._priority_eps = on(eta, float), on(eps, float)
+        self._tuf = per_learner(target_update_frequency, P, "target_update_frequency", int)
+        if batch_size < 1 or memory_size < batch_size or train_every < 1 or min(self._tuf) < 1 or \
+                explore_actions not in (1, 2, 3, 4):
+            raise ValueError("batch_size >= 1, memory_size >= batch_size, train_every >= 1, "
+                             "target_update_frequency >= 1, explore_actions in 1..4")
+        self.P, self.b = P, B // P
+        self._lr = per_learner(lr, P, "lr")
+        self._gamma = per_learner(discount_factor, P, "discount_factor")
+        self._starting_epsilon = per_learner(starting_epsilon, P, "starting_epsilon")
+        self._final_epsilon = per_learner(final_epsilon, P, "final_epsilon")
+        self._epsilon_decay = per_learner(epsilon_decay, P, "epsilon_decay")
+        self._seed = per_learner(seed, P, "seed", int)
+        self.batch_size, self.capacity = int(batch_size), int(memory_size)
+        self.explore_actions, self.train_every = int(explore_actions), int(train_every)
+        self._steps_done = [0] * P  # the eps clocks
+        self.counter = 0            # vector steps (the exploration draws' counter)
+        self.launches = 0           # update launches (the overflow look's clock)
+        self._updates = [0] * P
+        self._filled = [0] * P      # the host's lower bounds of the rings' counts
+        self._last_lr = [None] * P
+        self.last_due = [False] * P  # the learners the last vector step updated
+
+    @property
+    def priority_alpha(self):
+        """None when no learner is prioritized, else the learners' alphas (None: uniform)."""
+        if not any(self.prio):
+            return None
+        return self._priority_alpha[0] if self._ONE else self._priority_alpha
+
+    def _alloc_scalars(self):
+        """The per-learner scalars on the device, uploaded once, and the per-update block."""
+        P, kw = self.P, dict(device=self.device)
+        i32, i64, f32 = torch.int32, torch.int64, torch.float32
+        self.gamma_dev = torch.tensor(self._gamma, dtype=f32, **kw)
+        self.seed_dev = torch.tensor([_signed(s) for s in self._seed], dtype=i64, **kw)
+        self.eps_dev = torch.zeros(P, dtype=f32, **kw)
+        # the per-update scalars, one upload: sample counters (int64), due, sync, lr (f32 bits);
+        # prioritized: then the two samplers' masks and every learner's beta (float64)
+        self.upd = torch.zeros((9 * P + P % 2) if any(self.prio) else 5 * P, dtype=i32, **kw)
+        self.cnt_dev = self.upd[:2 * P].view(i64)
+        self.due_dev, self.sync_dev = self.upd[2 * P:3 * P], self.upd[3 * P:4 * P]
+        self.lr_dev = self.upd[4 * P:5 * P].view(f32)
+        if any(self.prio):
+            self.due_prio_dev, self.due_uni_dev = self.upd[5 * P:6 * P], self.upd[6 * P:7 * P]
+            self.beta_dev = self.upd[7 * P + P % 2:].view(torch.float64)  # (8-byte aligned)
+            f64 = lambda vs, ph: torch.tensor(  # noqa: E731 (a uniform learner: a valid placeholder)
+                [ph if v is None else v for v in vs], dtype=torch.float64, **kw)
+            self.prio_alpha_dev = f64(self._priority_alpha, 0.0)
+            self.prio_eta_dev = f64(self._priority_eta, 0.0)
+            self.prio_eps_dev = f64(self._priority_eps, 1.0)
+        self._prio_due = False  # whether the update under way has a due prioritized learner
+        self._stage = {}  # (_send's pinned rows)
+        if self.window is not None:
+            self.burn_in_dev = torch.tensor(self._burn_in, dtype=i32, **kw)
+            self.stored_dev = torch.tensor([int(s) for s in self._stored], dtype=i32, **kw)
+
+    def _send(self, dev, values):
+        """values (a numpy array of dev's shape and width) -> dev on the launch stream, without
+        draining it: through a ring of pinned host rows, each reused only after the event of its
+        last copy (a wait that only a host more than SLOTS copies ahead of the device meets)."""
+        SLOTS = 8
+        st = self._stage.get(dev.data_ptr())
+        if st is None:
+            rows = torch.zeros(SLOTS, dev.numel(), dtype=dev.dtype).pin_memory()
+            st = self._stage[dev.data_ptr()] = [rows, rows.numpy(), [None] * SLOTS, 0]
+        rows, host, events, k = st
+        if events[k] is not None:
+            events[k].synchronize()
+        host[k] = values
+        dev.copy_(rows[k], non_blocking=True)
+        events[k] = torch.cuda.Event()
+        events[k].record(torch.cuda.current_stream(self.device))
+        st[3] = (k + 1) % SLOTS
+
+    def _mirror(self):
+        """The once-uploaded values that may be assigned later (_PerLearner.MIRRORED, a loaded
+        checkpoint's seeds among them) go up again, in place."""
+        pairs = [(self.gamma_dev, self._gamma), (self.seed_dev, [_signed(s) for s in self._seed])]
+        if self.window is not None:
+            pairs.append((self.burn_in_dev, self._burn_in))
+        if any(self.prio):
+            pairs += [(self.prio_eta_dev, [v or 0.0 for v in self._priority_eta]),
+                      (self.prio_eps_dev, [1.0 if v is None else v for v in self._priority_eps])]
+        for dev, host in pairs:
+            dev.copy_(torch.tensor(host, dtype=dev.dtype))
+
+    def _alloc(self):
         """The per-instance buffers, the replay ring, an update's directory and row buffers
-        (population: a leading P dimension) and, with `state`, the snapshots' two buffers."""
+        (population: a leading P dimension) and, when a learner stores state, the snapshots' two
+        buffers; then _alloc_scalars."""
         B, E, L = self.env.num_envs, self.batch_size, self.L
-        lead = () if P is None else (P,)
+        lead = () if self._ONE else (self.P,)
         kw = dict(device=self.device)
         i32, i64, f32 = torch.int32, torch.int64, torch.float32
         self.h = torch.zeros(HIDDEN, B, dtype=f32, **kw)
@@ -194,12 +362,12 @@ class RecurrentDQNBase(EpisodicTrainer):
         if self.window is not None:
             self.wdir = torch.zeros(*lead, 5, E, dtype=i32, **kw)  # slot, n, b, k, m
             self.snaps = (L - 1) // self.window + 1
-        self._state = bool(state)
+        self._state = any(self._stored)
         if self._state:
             self.snap_rec = torch.zeros(B, self.snaps, 2 * HIDDEN, dtype=f32, **kw)
             self.mem_state = torch.zeros(*lead, self.capacity, self.snaps, 2 * HIDDEN, dtype=f32,
                                          **kw)
-        if self.priority_alpha is not None:
+        if any(self.prio):
             # a window's mass: u32 fixed point, 20 fractional bits (<= 2^30, so int32 holds it);
             # a slot's sum (< 2^63, so int64 holds it); the largest mass written, from priority 1
             self.mem_prio = torch.zeros(*lead, self.capacity, self.snaps, dtype=i32, **kw)
@@ -218,29 +386,184 @@ class RecurrentDQNBase(EpisodicTrainer):
         self.ep_loss = torch.zeros(*lead, E, dtype=torch.float64, **kw)
         self.gpart = torch.zeros(*lead, E, PARAMS, dtype=f32, **kw)
         self.loss = torch.zeros(*(lead or (1,)), dtype=f32, **kw)
+        self._alloc_scalars()
+
+    def epsilon(self, p=0):
+        return epsilon_at(self._steps_done[p], self._starting_epsilon[p], self._final_epsilon[p],
+                          self._epsilon_decay[p])
+
+    def update_steps_done(self, p=None):
+        for k in range(self.P) if p is None else (int(p),):
+            self._steps_done[k] = self._steps_done[k] // 2
+
+    def beta(self, p=0):
+        """Learner p's importance exponent at its coming update: its priority_beta, or its linear
+        schedule over its own update count (computed here, on the host)."""
+        b = self._priority_beta[p]
+        if isinstance(b, float):
+            return b
+        return b[0] + (b[1] - b[0]) * min(self._updates[p] / b[2], 1.0)
+
+    # ---- a vector step --------------------------------------------------------------------------
+    def _act(self):
+        env = self.env
+        eps = [min(max(self.epsilon(p), 0.0), 1.0) for p in range(self.P)]
+        for p in range(self.P):
+            self._steps_done[p] += 1
+        self._send(self.eps_dev, np.asarray(eps, np.float32))
+        if self._state:  # (all P b instances: a zero-state learner's snapshots are never read)
+            N.check(self.lib.mz_drqn_snapshot(
+                HIDDEN, env.num_envs, self.L, self.window, self.t.data_ptr(), self.h.data_ptr(),
+                self.c.data_ptr(), self.snap_rec.data_ptr(), self._stream()))
+        N.check(self.lib.mz_drqn_pop_act(
+            self.src.data_ptr(), HIDDEN, self.P, self.b, env.obs6.data_ptr(), self.L,
+            self.eps_dev.data_ptr(), self.explore_actions, self.seed_dev.data_ptr(),
+            self.counter & U64, self.t.data_ptr(), self.h.data_ptr(), self.c.data_ptr(),
+            self.rec_x.data_ptr(), self.rec_a.data_ptr(), self.act_out.data_ptr(), None,
+            self._stream()))
+        self.counter += 1
 
     def _scan_store(self):
-        env, L, st = self.env, self.L, self._stream()
+        env, L, P, b, st = self.env, self.L, self.P, self.b, self._stream()
         self.r64.copy_(env.reward)
         self._scan(self.r64, env.terminated, env.truncated, self.rec_r,
                    self.pool[0:].data_ptr(), self.pool[1:].data_ptr())
         fin = (self.fin_id.data_ptr(), self.fin_len.data_ptr(), self.fin_count.data_ptr())
         if self._state:  # (reads the ring's head, which the store advances)
-            self._snap_store_call(L, self.window, *fin, self.snap_rec.data_ptr(), self.capacity,
-                                  self.mem_state.data_ptr(), self.ring.data_ptr(), st)
-        if self.priority_alpha is not None:  # (reads the head too: new windows enter at prio_max)
-            self._prio_store_call(L, self.window, *fin, self.capacity, self.mem_prio.data_ptr(),
-                                  self.mem_psum.data_ptr(), self.prio_max.data_ptr(),
-                                  self.ring.data_ptr(), st)
-        self._store_call(L, *fin, self.rec_x.data_ptr(), self.rec_a.data_ptr(),
-                         self.rec_r.data_ptr(), self.capacity, self.mem.data_ptr(),
-                         self.mem_len.data_ptr(), self.mem_term.data_ptr(), self.ring.data_ptr(), st)
+            N.check(self.lib.mz_drqn_pop_snap_store(
+                HIDDEN, P, b, L, self.window, *fin, self.snap_rec.data_ptr(), self.capacity,
+                self.mem_state.data_ptr(), self.ring.data_ptr(), st))
+        if any(self.prio):  # (reads the head too: new windows enter at prio_max)
+            N.check(self.lib.mz_drqn_pop_prio_store(
+                HIDDEN, P, b, L, self.window, *fin, self.capacity, self.mem_prio.data_ptr(),
+                self.mem_psum.data_ptr(), self.prio_max.data_ptr(), self.ring.data_ptr(), st))
+        N.check(self.lib.mz_drqn_pop_store(
+            env.obs6.data_ptr(), env.terminated.data_ptr(), P, b, L, *fin, self.rec_x.data_ptr(),
+            self.rec_a.data_ptr(), self.rec_r.data_ptr(), self.capacity, self.mem.data_ptr(),
+            self.mem_len.data_ptr(), self.mem_term.data_ptr(), self.ring.data_ptr(), st))
 
-    def _overflow_look(self, clock):
-        if clock % 256 == 0 and int(self.stats[3]):  # (one look every 256 updates)
+    def vector_step(self):
+        self._act()
+        self.env.step(self.act_out)
+        self._scan_store()
+        self._reset_winners()
+        E = self.batch_size
+        if min(self._filled) < E:  # (only until every learner has its first batch: one sync a step)
+            counts = self.ring.view(-1, 2)[:, 1].tolist()
+            self._filled = [f if f >= E else int(n) for f, n in zip(self._filled, counts)]
+        due = [False] * self.P
+        if self.counter % self.train_every == 0:
+            due = [f >= E for f in self._filled]
+        self.last_due = due
+        if any(due):
+            self._update(due)
+
+    # ---- an update ------------------------------------------------------------------------------
+    def _update(self, due):
+        if self.launches % 256 == 0 and int(self.stats[3]):  # (one look every 256 updates)
             raise RuntimeError(f"recurrent DQN episode records overflowed L = {self.L} steps "
                                "(mz_ppo_scan stats[3])")
+        self.launches += 1
+        lr, sync = [0.0] * self.P, [0] * self.P
+        for p in range(self.P):
+            if due[p]:
+                lr[p] = self._last_lr[p] = cosine_lr(self._updates[p], self._lr[p], T_MAX, ETA_MIN)
+                sync[p] = int((self._updates[p] + 1) % self._tuf[p] == 0)
+        self._learn(due, sync, lr)
+        for p in range(self.P):
+            self._updates[p] += int(due[p])
 
+    def _upload(self, due, sync, lr):
+        """The per-update scalars of the coming update, one host-to-device copy (_send)."""
+        P = self.P
+        buf = np.zeros(self.upd.numel(), np.int32)
+        buf[:2 * P].view(np.int64)[:] = self._updates
+        buf[2 * P:3 * P] = due
+        buf[3 * P:4 * P] = sync
+        buf[4 * P:5 * P].view(np.float32)[:] = lr
+        if any(self.prio):  # the two samplers' masks; beta_p at learner p's own update count
+            buf[5 * P:6 * P] = [d and q for d, q in zip(due, self.prio)]
+            buf[6 * P:7 * P] = [d and not q for d, q in zip(due, self.prio)]
+            buf[7 * P + P % 2:].view(np.float64)[:] = [self.beta(p) if q else 0.0
+                                                       for p, q in enumerate(self.prio)]
+            self._prio_due = bool(buf[5 * P:6 * P].any())
+        self._send(self.upd, buf)
+
+    def _draw(self, due):
+        """E distinct slots and the directory (d_slot, d_len, d_off, d_tot) of every due learner,
+        keyed by its update count; windowed: the same slots, one window each and the window
+        directory (wdir, d_off, d_tot); a prioritized learner: E windows in proportion to their
+        mass, the same directory, and its importance weights (isw)."""
+        mask = self.due_dev
+        if any(self.prio):
+            if self._prio_due:
+                N.check(self.lib.mz_drqn_pop_prio_sample(
+                    self.seed_dev.data_ptr(), self.cnt_dev.data_ptr(), self.burn_in_dev.data_ptr(),
+                    self.beta_dev.data_ptr(), self.due_prio_dev.data_ptr(), HIDDEN, self.P,
+                    self.batch_size, self.L, self.window, max(self._burn_in), self.capacity,
+                    self.mem_len.data_ptr(), self.mem_prio.data_ptr(), self.mem_psum.data_ptr(),
+                    self.wdir.data_ptr(), self.d_off.data_ptr(), self.d_tot.data_ptr(),
+                    self.isw.data_ptr(), self._stream()))
+            due = [d and not q for d, q in zip(due, self.prio)]
+            if not any(due):
+                return
+            mask = self.due_uni_dev
+        filled = min(f for f, d in zip(self._filled, due) if d)
+        if self.window is not None:
+            N.check(self.lib.mz_drqn_pop_window_sample(
+                self.seed_dev.data_ptr(), self.cnt_dev.data_ptr(), self.burn_in_dev.data_ptr(),
+                mask.data_ptr(), HIDDEN, self.P, self.batch_size, self.L, self.window,
+                max(self._burn_in), self.capacity, filled, self.ring.data_ptr(),
+                self.mem_len.data_ptr(), self.wdir.data_ptr(), self.d_off.data_ptr(),
+                self.d_tot.data_ptr(), self._stream()))
+            return
+        N.check(self.lib.mz_drqn_pop_sample(
+            self.seed_dev.data_ptr(), self.cnt_dev.data_ptr(), self.due_dev.data_ptr(), self.P,
+            self.batch_size, self.L, self.capacity, filled, self.ring.data_ptr(),
+            self.mem_len.data_ptr(), self.d_slot.data_ptr(), self.d_len.data_ptr(),
+            self.d_off.data_ptr(), self.d_tot.data_ptr(), self._stream()))
+
+    def _gradients(self):
+        """Every due learner's loss (self.loss, on the device) and gradient (self.grad) on its
+        directory's episodes or windows: the target net's forward, the source net's, a prioritized
+        learner's new masses and weighted residuals, the backward and its reduction."""
+        P, E, L, cap, st = self.P, self.batch_size, self.L, self.capacity, self._stream()
+        due, gam = self.due_dev.data_ptr(), self.gamma_dev.data_ptr()
+        rows = (self.stash.data_ptr(), self.qa.data_ptr(), self.y.data_ptr(), self.d.data_ptr(),
+                self.ep_loss.data_ptr())
+        back = (self.stash.data_ptr(), self.d.data_ptr(), self.ep_loss.data_ptr(),
+                self.gpart.data_ptr(), self.grad.data_ptr(), self.loss.data_ptr(), st)
+        if self.window is None:
+            dirs = (self.d_slot.data_ptr(), self.d_len.data_ptr(), self.d_off.data_ptr(),
+                    self.d_tot.data_ptr())
+            for net, target, out in ((self.tgt, 1, (None,) * 5), (self.src, 0, rows)):
+                N.check(self.lib.mz_drqn_pop_seq_forward(
+                    net.data_ptr(), HIDDEN, target, P, E, L, cap, gam, due, self.mem.data_ptr(),
+                    self.mem_term.data_ptr(), *dirs, self.qmax.data_ptr(), *out, st))
+            N.check(self.lib.mz_drqn_pop_seq_backward(
+                self.src.data_ptr(), HIDDEN, P, E, L, cap, due, self.mem.data_ptr(), *dirs, *back))
+            return
+        T, K = self.window, max(self._burn_in)
+        state = self.mem_state.data_ptr() if self._state else None
+        burn, stored = self.burn_in_dev.data_ptr(), self.stored_dev.data_ptr()
+        dirs = (self.wdir.data_ptr(), self.d_off.data_ptr(), self.d_tot.data_ptr())
+        for net, target, out in ((self.tgt, 1, (None,) * 5), (self.src, 0, rows)):
+            N.check(self.lib.mz_drqn_pop_window_forward(
+                net.data_ptr(), HIDDEN, target, P, E, L, T, K, cap, gam, burn, stored, due,
+                self.mem.data_ptr(), self.mem_term.data_ptr(), state, *dirs, self.qmax.data_ptr(),
+                *out, st))
+        if self._prio_due:  # the new masses; d and ep_loss times the weights
+            N.check(self.lib.mz_drqn_pop_prio_update(
+                self.prio_alpha_dev.data_ptr(), self.prio_eta_dev.data_ptr(),
+                self.prio_eps_dev.data_ptr(), self.due_prio_dev.data_ptr(), HIDDEN, P, E, L, T,
+                cap, *dirs, self.qa.data_ptr(), self.y.data_ptr(), self.d.data_ptr(),
+                self.ep_loss.data_ptr(), self.isw.data_ptr(), self.mem_prio.data_ptr(),
+                self.mem_psum.data_ptr(), self.prio_max.data_ptr(), st))
+        N.check(self.lib.mz_drqn_pop_window_backward(
+            self.src.data_ptr(), HIDDEN, P, E, L, T, K, cap, burn, due, self.mem.data_ptr(), *dirs,
+            *back))
+
+    # ---- the settings and the replay half of a checkpoint ---------------------------------------
     def _window_settings(self):
         """T with the burn-in and the initial state (a population's: the per-learner lists); None
         without windows."""
@@ -249,11 +572,73 @@ class RecurrentDQNBase(EpisodicTrainer):
         return {"window": self.window, "burn_in": copy.copy(self.burn_in),
                 "initial_state": copy.copy(self.initial_state)}
 
-    def _check_window_settings(self, sd):
-        # (a checkpoint from before the window option has no "window" key: window=None)
+    def _priority_settings(self):
+        if not any(self.prio):
+            return None
+        s = {"alpha": list(self._priority_alpha),
+             "beta": [list(b) if isinstance(b, tuple) else b for b in self._priority_beta],
+             "eta": list(self._priority_eta), "eps": list(self._priority_eps)}
+        return {k: v[0] for k, v in s.items()} if self._ONE else s
+
+    def _check_settings(self, sd):
+        """ValueError unless the checkpoint's window and priority settings are this object's. (A
+        checkpoint from before either option has no such key: window=None, priority_alpha=None.)"""
+        kind = "trainer" if self._ONE else "population"
         if sd.get("window") != self._window_settings():
             raise ValueError(f"the checkpoint's replay windows {sd.get('window')} differ from this "
-                             f"{self._KIND}'s {self._window_settings()}")
+                             f"{kind}'s {self._window_settings()}")
+        if sd.get("priority") != self._priority_settings():
+            raise ValueError(f"the checkpoint's prioritized replay {sd.get('priority')} differs "
+                             f"from this {kind}'s {self._priority_settings()}")
+
+    def _slots(self, k):
+        """Buffer k as [P][capacity][...] (the single trainer's has no leading dimension)."""
+        t = getattr(self, k)
+        return t[None] if self._ONE else t
+
+    def _save_slots(self, sd, keys):
+        """Each ring's filled slots of the buffers `keys` (a population: a list of P per key)."""
+        counts = [int(n) for n in self.ring.view(-1, 2)[:, 1].tolist()]
+        for k in keys:
+            parts = [self._slots(k)[p, :n].clone() for p, n in enumerate(counts)]
+            sd[k] = parts[0] if self._ONE else parts
+
+    def _load_slots(self, sd, keys):
+        for k in keys:
+            for p, part in enumerate([sd[k]] if self._ONE else sd[k]):
+                self._slots(k)[p, :part.shape[0]].copy_(part)
+
+    def _save_own(self, sd):
+        """_OWN whole and the ring's filled slots."""
+        sd.update({k: getattr(self, k).clone() for k in self._OWN})
+        self._save_slots(sd, ("mem", "mem_len", "mem_term"))
+
+    def _save_options(self, sd):
+        """What the window and priority options add: the settings, the in-flight and the filled
+        slots' snapshots when a learner stores state, the filled slots' masses and sums and
+        prio_max when one is prioritized."""
+        if self.window is not None:
+            sd["window"] = self._window_settings()
+        if self._state:
+            sd["snap_rec"] = self.snap_rec.clone()
+            self._save_slots(sd, ("mem_state",))
+        if any(self.prio):
+            sd["priority"] = self._priority_settings()
+            self._save_slots(sd, ("mem_prio", "mem_psum"))
+            sd["prio_max"] = self.prio_max.clone()
+
+    def _load_replay(self, sd):
+        """_OWN, the rings' slots and the options' buffers. (The seeds a checkpoint carries went
+        up when they were assigned.)"""
+        for k in self._OWN:
+            getattr(self, k).copy_(sd[k])
+        self._load_slots(sd, ("mem", "mem_len", "mem_term"))
+        if self._state:
+            self.snap_rec.copy_(sd["snap_rec"])
+            self._load_slots(sd, ("mem_state",))
+        if any(self.prio):
+            self._load_slots(sd, ("mem_prio", "mem_psum"))
+            self.prio_max.copy_(sd["prio_max"])
 
     @staticmethod
     def greedy_rollout(env, act, limit):
@@ -274,10 +659,17 @@ class RecurrentDQNBase(EpisodicTrainer):
         return won, k
 
 
+for _name in RecurrentDQNBase._PER:
+    setattr(RecurrentDQNBase, _name, _PerLearner(_name))
+RecurrentDQNBase.target_update_frequency = _PerLearner("tuf")  # (the argument's name)
+
+
 class VectorRecurrentDQNTrainer(RecurrentDQNBase):
     _FORMAT = FORMAT
     _SHAPE = ("L", "capacity")
     _COUNTERS = ("seed", "steps_done", "counter", "updates", "filled")
+    _ONE = True
+    _DUE = (True,)
 
     def __init__(self, env, device, lr=1e-3, starting_epsilon=0.9, final_epsilon=0.05,
                  epsilon_decay=1000.0, discount_factor=0.99, batch_size=32, memory_size=20000,
@@ -289,191 +681,56 @@ class VectorRecurrentDQNTrainer(RecurrentDQNBase):
         replay windows (departures 10-12; None: off, nothing of it is allocated or launched);
         priority_beta: a number, or (beta0, beta1, updates) for a linear schedule over the update
         count."""
-        check_window(window, burn_in, initial_state)
-        check_priority(window, priority_alpha, priority_beta, priority_eta, priority_eps)
-        if batch_size < 1 or memory_size < batch_size or train_every < 1 or \
-                target_update_frequency < 1 or explore_actions not in (1, 2, 3, 4):
-            raise ValueError("batch_size >= 1, memory_size >= batch_size, train_every >= 1, "
-                             "target_update_frequency >= 1, explore_actions in 1..4")
+        one = lambda *vs: ([v] for v in vs)  # noqa: E731 (each value is the one learner's)
+        self._configure(
+            1, getattr(env, "num_envs", 1),
+            *one(lr, starting_epsilon, final_epsilon, epsilon_decay, discount_factor), batch_size,
+            memory_size, [target_update_frequency], explore_actions, train_every, [seed], window,
+            *one(burn_in, initial_state, priority_alpha, priority_beta, priority_eta, priority_eps))
         super().__init__(env, device, bank=bank, curriculum=curriculum, growth=growth,
                          algorithm=algorithm, bank_candidates=bank_candidates, archive=archive)
         torch.manual_seed(seed)
         self.source_net = DQN(6, 4, HIDDEN, self.device)
         self.target_net = DQN(6, 4, HIDDEN, self.device)
-        flatten_params(self.target_net)
-        flatten_grads(self.source_net)
+        self.tgt = flatten_params(self.target_net)
+        self.grad = flatten_grads(self.source_net)
+        self.src = self.source_net._flat_params
+        # the flat buffers begin with a population row: no segment is padded
+        assert self.source_net._flat_sizes == [math.prod(s) for s in SHAPES] and \
+            sum(self.source_net._flat_sizes) == PARAMS
         copy_flat(self.target_net, self.source_net)
         for p in self.source_net.parameters():
             p.grad = grad_segment(p)
         self.opt = FlatAdamW(self.source_net, lr=lr, clamp=1.0)
-        self._ps, self._pt = param_ptrs(self.source_net), param_ptrs(self.target_net)
-        self._pg = (C.c_void_p * 6)(*[p.grad.data_ptr() for p in self.source_net.parameters()])
-        self.lr, self.gamma = float(lr), float(discount_factor)
-        self.starting_epsilon, self.final_epsilon = float(starting_epsilon), float(final_epsilon)
-        self.epsilon_decay = float(epsilon_decay)
-        self.batch_size, self.capacity = int(batch_size), int(memory_size)
-        self.target_update_frequency = int(target_update_frequency)
-        self.explore_actions, self.train_every = int(explore_actions), int(train_every)
-        self.seed = int(seed)
-        self.window = None if window is None else int(window)
-        self.burn_in, self.initial_state = int(burn_in), initial_state
-        if priority_alpha is not None:
-            self.priority_alpha = float(priority_alpha)
-            self.priority_beta = float(priority_beta) if isinstance(priority_beta, (int, float)) \
-                else (float(priority_beta[0]), float(priority_beta[1]), int(priority_beta[2]))
-            self.priority_eta, self.priority_eps = float(priority_eta), float(priority_eps)
-        self.steps_done = 0   # the eps clock
-        self.counter = 0      # vector steps (the exploration draws' counter)
-        self.updates = 0
-        self.filled = 0       # the host's lower bound of the ring's count
-        self.stored = self.window is not None and initial_state == "stored"
-        self._alloc(None, self.stored)
-        self.last_lr = None
-
-    def epsilon(self):
-        return epsilon_at(self.steps_done, self.starting_epsilon, self.final_epsilon,
-                          self.epsilon_decay)
-
-    def update_steps_done(self):
-        self.steps_done = self.steps_done // 2
-
-    def _act(self):
-        env = self.env
-        eps = min(max(self.epsilon(), 0.0), 1.0)
-        self.steps_done += 1
-        if self.stored:
-            N.check(self.lib.mz_drqn_snapshot(
-                HIDDEN, env.num_envs, self.L, self.window, self.t.data_ptr(), self.h.data_ptr(),
-                self.c.data_ptr(), self.snap_rec.data_ptr(), self._stream()))
-        N.check(self.lib.mz_drqn_act(
-            self._ps, HIDDEN, env.obs6.data_ptr(), env.num_envs, self.L, eps, self.explore_actions,
-            self.seed & U64, self.counter & U64, self.t.data_ptr(), self.h.data_ptr(),
-            self.c.data_ptr(), self.rec_x.data_ptr(), self.rec_a.data_ptr(),
-            self.act_out.data_ptr(), None, self._stream()))
-        self.counter += 1
-
-    def _snap_store_call(self, *tail):
-        N.check(self.lib.mz_drqn_snap_store(HIDDEN, self.env.num_envs, *tail))
-
-    def _prio_store_call(self, *tail):
-        N.check(self.lib.mz_drqn_prio_store(HIDDEN, self.env.num_envs, *tail))
-
-    def _store_call(self, *tail):
-        env = self.env
-        N.check(self.lib.mz_drqn_store(env.obs6.data_ptr(), env.terminated.data_ptr(),
-                                       env.num_envs, *tail))
+        self._ps = param_ptrs(self.source_net)  # (_Evaluator's)
+        self._alloc()
 
     def sample(self):
-        """E distinct slots and the directory (d_slot, d_len, d_off, d_tot), keyed by the update
-        count; windowed: the same slots, one window each and the window directory (wdir, d_off,
-        d_tot). Prioritized: E windows in proportion to their mass, the same directory, and the
-        importance weights (isw)."""
-        if self.priority_alpha is not None:
-            N.check(self.lib.mz_drqn_prio_sample(
-                self.seed & U64, self.updates & U64, HIDDEN, self.batch_size, self.L, self.window,
-                self.burn_in, self.capacity, self.mem_len.data_ptr(), self.mem_prio.data_ptr(),
-                self.mem_psum.data_ptr(), self.wdir.data_ptr(), self.d_off.data_ptr(),
-                self.d_tot.data_ptr(), self.isw.data_ptr(), self.beta(), self._stream()))
-            return
-        if self.window is not None:
-            N.check(self.lib.mz_drqn_window_sample(
-                self.seed & U64, self.updates & U64, HIDDEN, self.batch_size, self.L, self.window,
-                self.burn_in, self.capacity, self.filled, self.ring.data_ptr(),
-                self.mem_len.data_ptr(), self.wdir.data_ptr(), self.d_off.data_ptr(),
-                self.d_tot.data_ptr(), self._stream()))
-            return
-        N.check(self.lib.mz_drqn_sample(
-            self.seed & U64, self.updates & U64, self.batch_size, self.L, self.capacity,
-            self.filled, self.ring.data_ptr(), self.mem_len.data_ptr(), self.d_slot.data_ptr(),
-            self.d_len.data_ptr(), self.d_off.data_ptr(), self.d_tot.data_ptr(), self._stream()))
+        """The coming update's scalars go up and its batch is drawn (_draw). Of the block this
+        trainer's kernels read the sample counter, the due mask and beta; its lr is FlatAdamW's
+        and its sync copy_flat's, so both go up as zeros."""
+        self._upload(self._DUE, (0,), (0.0,))
+        self._draw(self._DUE)
 
     def update(self, lr):
         """One optimizer step on the directory's episodes at learning rate `lr`; the loss stays on
         the device (self.loss)."""
-        E, L, st = self.batch_size, self.L, self._stream()
-        dirs = (self.d_slot.data_ptr(), self.d_len.data_ptr(), self.d_off.data_ptr(),
-                self.d_tot.data_ptr())
         self.opt.param_groups[0]["lr"].fill_(float(lr))
-        if self.window is not None:
-            self._window_update(st)
-            self.opt.step()
-            return
-        N.check(self.lib.mz_drqn_seq_forward(
-            self._pt, HIDDEN, 1, E, L, self.capacity, self.gamma, self.mem.data_ptr(),
-            self.mem_term.data_ptr(), *dirs, self.qmax.data_ptr(), None, None, None, None, None,
-            st))
-        N.check(self.lib.mz_drqn_seq_forward(
-            self._ps, HIDDEN, 0, E, L, self.capacity, self.gamma, self.mem.data_ptr(),
-            self.mem_term.data_ptr(), *dirs, self.qmax.data_ptr(), self.stash.data_ptr(),
-            self.qa.data_ptr(), self.y.data_ptr(), self.d.data_ptr(), self.ep_loss.data_ptr(), st))
-        N.check(self.lib.mz_drqn_seq_backward(
-            self._ps, HIDDEN, E, L, self.capacity, self.mem.data_ptr(), *dirs,
-            self.stash.data_ptr(), self.d.data_ptr(), self.ep_loss.data_ptr(),
-            self.gpart.data_ptr(), self._pg, self.loss.data_ptr(), st))
+        self._gradients()
         self.opt.step()
 
-    def _window_update(self, st):
-        E, L, T, K = self.batch_size, self.L, self.window, self.burn_in
-        state = self.mem_state.data_ptr() if self.stored else None
-        dirs = (self.wdir.data_ptr(), self.d_off.data_ptr(), self.d_tot.data_ptr())
-        N.check(self.lib.mz_drqn_window_forward(
-            self._pt, HIDDEN, 1, E, L, T, K, self.capacity, self.gamma, self.mem.data_ptr(),
-            self.mem_term.data_ptr(), state, *dirs, self.qmax.data_ptr(), None, None, None, None,
-            None, st))
-        N.check(self.lib.mz_drqn_window_forward(
-            self._ps, HIDDEN, 0, E, L, T, K, self.capacity, self.gamma, self.mem.data_ptr(),
-            self.mem_term.data_ptr(), state, *dirs, self.qmax.data_ptr(), self.stash.data_ptr(),
-            self.qa.data_ptr(), self.y.data_ptr(), self.d.data_ptr(), self.ep_loss.data_ptr(), st))
-        if self.priority_alpha is not None:  # the new masses; d and ep_loss times the weights
-            N.check(self.lib.mz_drqn_prio_update(
-                HIDDEN, E, L, T, self.capacity, *dirs, self.qa.data_ptr(), self.y.data_ptr(),
-                self.d.data_ptr(), self.ep_loss.data_ptr(), self.isw.data_ptr(),
-                self.priority_alpha, self.priority_eta, self.priority_eps,
-                self.mem_prio.data_ptr(), self.mem_psum.data_ptr(), self.prio_max.data_ptr(), st))
-        N.check(self.lib.mz_drqn_window_backward(
-            self._ps, HIDDEN, E, L, T, K, self.capacity, self.mem.data_ptr(), *dirs,
-            self.stash.data_ptr(), self.d.data_ptr(), self.ep_loss.data_ptr(),
-            self.gpart.data_ptr(), self._pg, self.loss.data_ptr(), st))
-
-    def _update(self):
-        self._overflow_look(self.updates)
-        self.last_lr = cosine_lr(self.updates, self.lr, T_MAX, ETA_MIN)
+    def _learn(self, due, sync, lr):
+        # (one learner, always due: of the three lists only lr[0] and sync[0] are consumed)
         self.sample()
-        self.update(self.last_lr)
-        self.updates += 1
-        if self.updates % self.target_update_frequency == 0:
+        self.update(lr[0])
+        if sync[0]:
             copy_flat(self.target_net, self.source_net)
-
-    def vector_step(self):
-        self._act()
-        self.env.step(self.act_out)
-        self._scan_store()
-        self._reset_winners()
-        if self.filled < self.batch_size:  # (only until the first batch exists: one sync a step)
-            self.filled = int(self.ring[1])
-        if self.filled >= self.batch_size and self.counter % self.train_every == 0:
-            self._update()
-
-    def beta(self):
-        """The importance exponent of the coming update: priority_beta, or its linear schedule
-        over the update count (computed here, on the host)."""
-        b = self.priority_beta
-        if isinstance(b, float):
-            return b
-        return b[0] + (b[1] - b[0]) * min(self.updates / b[2], 1.0)
 
     def _log_fields(self):
         if self.priority_alpha is None:
             return {"loss": float(self.loss)}
         return {"loss": float(self.loss), "prio_max": int(self.prio_max) / PRIO_ONE,
                 "mean_weight": float(self.isw.mean())}
-
-    def _priority_settings(self):
-        if self.priority_alpha is None:
-            return None
-        b = self.priority_beta
-        return {"alpha": self.priority_alpha, "beta": b if isinstance(b, float) else list(b),
-                "eta": self.priority_eta, "eps": self.priority_eps}
 
     # ---- evaluation (vector_trainer.evaluate) ---------------------------------------------------
     def evaluator(self):
@@ -501,21 +758,11 @@ class VectorRecurrentDQNTrainer(RecurrentDQNBase):
         """The run between two vector steps: both nets, the optimizer, (h, c), the in-flight
         records, the filled replay slots with head and count, the counters and the env
         (_save_common); a windowed trainer adds its settings and, when it stores state, the
-        in-flight and the filled slots' snapshots."""
+        in-flight and the filled slots' snapshots; a prioritized one its settings, masses and
+        sums."""
         sd, o = self._save_common(), self.opt
-        n = int(self.ring[1])
-        if self.window is not None:
-            sd["window"] = self._window_settings()
-        if self.stored:
-            sd["snap_rec"] = self.snap_rec.clone()
-            sd["mem_state"] = self.mem_state[:n].clone()
-        if self.priority_alpha is not None:
-            sd["priority"] = self._priority_settings()
-            sd["mem_prio"] = self.mem_prio[:n].clone()
-            sd["mem_psum"] = self.mem_psum[:n].clone()
-            sd["prio_max"] = self.prio_max.clone()
-        sd.update({k: getattr(self, k).clone() for k in self._OWN})
-        sd.update({k: getattr(self, k)[:n].clone() for k in ("mem", "mem_len", "mem_term")})
+        self._save_options(sd)
+        self._save_own(sd)
         sd["source"] = {k: v.clone() for k, v in self.source_net.state_dict().items()}
         sd["target"] = {k: v.clone() for k, v in self.target_net.state_dict().items()}
         sd["opt"] = {"exp_avg": o.exp_avg.clone(), "exp_avg_sq": o.exp_avg_sq.clone(),
@@ -523,12 +770,9 @@ class VectorRecurrentDQNTrainer(RecurrentDQNBase):
         return sd
 
     def load_state_dict(self, sd):
-        self._check_window_settings(sd)
-        # (a checkpoint of a trainer without priorities has no "priority" key: priority_alpha=None)
-        if sd.get("priority") != self._priority_settings():
-            raise ValueError(f"the checkpoint's prioritized replay {sd.get('priority')} differs "
-                             f"from this trainer's {self._priority_settings()}")
+        self._check_settings(sd)
         self._load_common(sd)
+        self.launches = self.updates  # (the overflow look's clock is not in this format)
         with torch.no_grad():
             self.source_net.load_state_dict(sd["source"])
             self.target_net.load_state_dict(sd["target"])
@@ -537,18 +781,7 @@ class VectorRecurrentDQNTrainer(RecurrentDQNBase):
         o.exp_avg_sq.copy_(sd["opt"]["exp_avg_sq"])
         o._step_buf.copy_(sd["opt"]["step"])
         o.param_groups[0]["lr"].copy_(sd["opt"]["lr"])
-        for k in self._OWN:
-            getattr(self, k).copy_(sd[k])
-        n = sd["mem"].shape[0]
-        for k in ("mem", "mem_len", "mem_term"):
-            getattr(self, k)[:n].copy_(sd[k])
-        if self.stored:
-            self.snap_rec.copy_(sd["snap_rec"])
-            self.mem_state[:n].copy_(sd["mem_state"])
-        if self.priority_alpha is not None:
-            self.mem_prio[:n].copy_(sd["mem_prio"])
-            self.mem_psum[:n].copy_(sd["mem_psum"])
-            self.prio_max.copy_(sd["prio_max"])
+        self._load_replay(sd)
 
 
 def evaluate_plain(learner, num_mazes, dim, algorithm="r-prim", seed=0x7E57, toroidal=False,

@@ -15,6 +15,7 @@ snapshots cost beside the whole-episode trainer, and one training run per settin
         --steps 30000 --eps-decay 5000 --seed 0; MODE whole | stored | zero ((40, 40) windows)
 HIP events in one process, 10 warm-up calls, then REPS windows per figure: median (min-max) in
 microseconds. One JSON line per figure, appended to OUT (default directory: profiles/lstm_dqn_window)."""
+import ctypes
 import json
 import os
 import statistics
@@ -59,7 +60,7 @@ def case_update(dim, out):
     sys.path.insert(0, PKG)
     import mazerl
     from mazerl import _native as N
-    from mazerl.trainers.drqn_trainer import VectorRecurrentDQNTrainer
+    from mazerl.trainers.drqn_trainer import VectorRecurrentDQNTrainer, param_ptrs
     env = mazerl.VectorMazeEnv(4096, dim, enrich=False, device="cuda", pos=False, done_list=False)
     tr = VectorRecurrentDQNTrainer(env, "cuda", batch_size=E, memory_size=4096,
                                    train_every=10 ** 9, bank=False, window=40)
@@ -68,6 +69,8 @@ def case_update(dim, out):
     tr.filled = int(tr.ring[1])
     assert tr.filled >= E, tr.filled
     L, cap, st = tr.L, tr.capacity, tr._stream()
+    pt = param_ptrs(tr.target_net)  # (the single-learner entry points' pointer arrays)
+    pg = (ctypes.c_void_p * 6)(*[p.grad.data_ptr() for p in tr.source_net.parameters()])
     lens = tr.mem_len[:tr.filled].float()
     kw = dict(device=tr.device)
     rows = E * (L + 1)
@@ -80,7 +83,7 @@ def case_update(dim, out):
     def whole():  # the whole-episode update of window=None, on this memory
         N.check(tr.lib.mz_drqn_sample(tr.seed, tr.updates, E, L, cap, tr.filled, tr.ring.data_ptr(),
                                       tr.mem_len.data_ptr(), *dirs, st))
-        N.check(tr.lib.mz_drqn_seq_forward(tr._pt, H, 1, E, L, cap, tr.gamma, tr.mem.data_ptr(),
+        N.check(tr.lib.mz_drqn_seq_forward(pt, H, 1, E, L, cap, tr.gamma, tr.mem.data_ptr(),
                                            tr.mem_term.data_ptr(), *dirs, qmax.data_ptr(), None,
                                            None, None, None, None, st))
         N.check(tr.lib.mz_drqn_seq_forward(tr._ps, H, 0, E, L, cap, tr.gamma, tr.mem.data_ptr(),
@@ -89,7 +92,7 @@ def case_update(dim, out):
                                            d.data_ptr(), tr.ep_loss.data_ptr(), st))
         N.check(tr.lib.mz_drqn_seq_backward(tr._ps, H, E, L, cap, tr.mem.data_ptr(), *dirs,
                                             stash.data_ptr(), d.data_ptr(), tr.ep_loss.data_ptr(),
-                                            tr.gpart.data_ptr(), tr._pg, tr.loss.data_ptr(), st))
+                                            tr.gpart.data_ptr(), pg, tr.loss.data_ptr(), st))
         tr.opt.step()
         tr.updates += 1
 
