@@ -1038,6 +1038,70 @@ int mz_drqn_pop_window_backward(const float* params_dev, int32_t hidden, int32_t
                                 const double* ep_loss_dev, float* gpart_dev, float* grads_dev,
                                 float* loss_dev, void* stream);
 
+/* ---- Double-Q targets and n-step returns (double_q=..., n_step=...) -------------------------------
+ * The update's chain when a learner leaves the defaults (population entry points only; the single
+ * trainer is P = 1): the target net's forward and the source net's in the forms below, then the
+ * returns kernel, which forms y, d and ep_loss; mz_drqn_pop_prio_update and the backwards follow as
+ * they are. The old forwards are not part of the chain and keep their bits. Two more row buffers:
+ * q4_dev f32 [P][rows][4], the target net's four Q' of a row (16-byte aligned), and sel_dev int32
+ * [P][rows], the first argmax of the source net's own Q (the acting kernel's rule: the first maximum
+ * in action order, 0 for a NaN row); rows as the old forwards' row buffers. With a span of training
+ * steps s .. s + m - 1 in rows row .. row + m - 1 (a whole episode: s = 0, m = n; a window: after
+ * its burn-in), both cover rows row .. row + m: row + m is the step after the last training step,
+ * the guard row of a window, row off + n of an episode.
+ *
+ * The forwards take the old forwards' arguments without gamma_dev and mem_term_dev, which only y
+ * read, and with q4_dev / sel_dev in place of qmax_dev / y_dev / d_dev / ep_loss_dev. target != 0:
+ * the target net writes q4_dev for rows row .. row + m (stash_dev, qa_dev, sel_dev may be NULL).
+ * target == 0: the source net unrolls one step further than the old forward, x_{s+m} from its own
+ * state; it writes the stash and qa_dev for the training rows as the old forward does (the same
+ * bits) and sel_dev for rows row .. row + m; the extra step has no stash row, no loss term and no
+ * gradient (q4_dev may be NULL). Refusals as the old forwards'. */
+int mz_drqn_pop_seq_forward_q(const float* params_dev, int32_t hidden, int32_t target, int32_t P,
+                              int32_t E, int32_t L, int64_t capacity, const int32_t* due_dev,
+                              const uint32_t* mem_dev, const int32_t* dir_slot_dev,
+                              const int32_t* dir_len_dev, const int64_t* dir_off_dev,
+                              const int64_t* dir_tot_dev, float* q4_dev, float* stash_dev,
+                              float* qa_dev, int32_t* sel_dev, void* stream);
+int mz_drqn_pop_window_forward_q(const float* params_dev, int32_t hidden, int32_t target, int32_t P,
+                                 int32_t E, int32_t L, int32_t T, int32_t K_max, int64_t capacity,
+                                 const int32_t* burn_in_dev, const int32_t* stored_dev,
+                                 const int32_t* due_dev, const uint32_t* mem_dev,
+                                 const float* mem_state_dev, const int32_t* wdir_dev,
+                                 const int64_t* win_off_dev, const int64_t* win_tot_dev,
+                                 float* q4_dev, float* stash_dev, float* qa_dev, int32_t* sel_dev,
+                                 void* stream);
+
+/* After both forwards, one wave per (learner, span), with N = n_step_dev[p] (int32 [P]) and
+ * gamma_dev[p]. For training step t of the span: k = min(N, s + m - t), u = t + k (the return is cut
+ * at the span's end: no reward past it is read), boot = q4[u][sel[u]] where learner p is double,
+ * else max_a q4[u][a]; no bootstrap where u == n and the episode terminated. In float32, in this
+ * order: acc = no_boot ? r_{u-1} : fmaf(gamma, boot, r_{u-1}); acc = fmaf(gamma, acc, r_i) for
+ * i = u - 2 down to t; y_t = acc; d_t = 2 (qa_t - y_t) (float)(1.0 / tot[1]); ep_loss_dev[p][e] =
+ * the float64 sum of the squared residuals in time order. N = 1 without sel_dev gives the old source
+ * forward's y, d and ep_loss bit for bit. sel_dev NULL: every learner bootstraps from the max;
+ * otherwise learner p reads it where double_dev[p] != 0 (int32 [P]; NULL: every learner does). No
+ * atomics; rows outside the directory's spans are not touched. Refused: null pointers (but
+ * sel_dev, double_dev, due_dev), the old forwards' sizes, n_step_max < 1. n_step_dev lives on the
+ * device and cannot be refused: a value outside 1 .. n_step_max counts as the nearer bound. */
+int mz_drqn_pop_seq_returns(const int32_t* n_step_dev, int32_t n_step_max,
+                            const int32_t* double_dev, const float* gamma_dev,
+                            const int32_t* due_dev, int32_t P, int32_t E, int32_t L,
+                            int64_t capacity, const uint32_t* mem_dev, const int32_t* mem_term_dev,
+                            const int32_t* dir_slot_dev, const int32_t* dir_len_dev,
+                            const int64_t* dir_off_dev, const int64_t* dir_tot_dev,
+                            const float* qa_dev, const float* q4_dev, const int32_t* sel_dev,
+                            float* y_dev, float* d_dev, double* ep_loss_dev, void* stream);
+int mz_drqn_pop_window_returns(const int32_t* n_step_dev, int32_t n_step_max,
+                               const int32_t* double_dev, const float* gamma_dev,
+                               const int32_t* burn_in_dev, const int32_t* due_dev, int32_t P,
+                               int32_t E, int32_t L, int32_t T, int32_t K_max, int64_t capacity,
+                               const uint32_t* mem_dev, const int32_t* mem_term_dev,
+                               const int32_t* wdir_dev, const int64_t* win_off_dev,
+                               const int64_t* win_tot_dev, const float* qa_dev,
+                               const float* q4_dev, const int32_t* sel_dev, float* y_dev,
+                               float* d_dev, double* ep_loss_dev, void* stream);
+
 /* ---- Prioritized replay windows per learner (VectorRecurrentDQNPopulation(priority_alpha=...)) --
  * The three mz_drqn_prio_* kernels over P learners in one launch each, learner p on its own rows:
  * mem_prio_dev uint32 [P][capacity][W], mem_psum_dev uint64 [P][capacity], prio_max_dev uint32 [P],

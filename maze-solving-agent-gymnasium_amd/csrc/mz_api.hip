@@ -1962,6 +1962,123 @@ int mz_drqn_pop_window_backward(const float* params_dev, int32_t hidden, int32_t
       ep_loss_dev, drqn_flat_net(grads_dev), loss_dev, stream);
 }
 
+// ---- double-Q targets and n-step returns (mz_drqn.hip k_drqn_*_fwd_q, k_drqn_*_ret) -------------
+// what the two forwards check of the shared fields: target form q4, source form stash, qa and sel
+static int drqn_forward_q_args(const char* who, int32_t hidden, int32_t P, const MzDrqnUnroll& u,
+                               const MzDrqnQRows& x) {
+  if (!u.p.w_ih || !u.mem || (u.target ? !x.q4 : (!u.stash || !u.qa || !x.sel)))
+    return fail(MZ_EINVAL, "%s: null pointer", who);
+  if (int rc = drqn_pop_args(who, hidden, P, u.E, "E")) return rc;
+  return drqn_seq_args(who, u.E, u.L, u.cap);
+}
+static MzDrqnUnroll drqn_forward_q(const float* params_dev, int32_t target, int32_t E, int32_t L,
+                                   int64_t capacity, const uint32_t* mem_dev, float* stash_dev,
+                                   float* qa_dev) {
+  return MzDrqnUnroll{drqn_flat_net(params_dev), target ? 1 : 0, E, L, capacity, 0.0f, mem_dev,
+                      nullptr, nullptr, stash_dev, qa_dev, nullptr, nullptr, nullptr, nullptr};
+}
+// the returns': the shared fields (no net) and the per-learner arrays
+static int drqn_returns_args(const char* who, int32_t P, const MzDrqnUnroll& u,
+                             const float* gamma_dev, const MzDrqnReturns& r) {
+  if (!u.mem || !u.mem_term || !u.qa || !u.y || !u.d || !u.ep_loss || !gamma_dev || !r.n_step ||
+      !r.q4)
+    return fail(MZ_EINVAL, "%s: null pointer", who);
+  if (r.n_max < 1) return fail(MZ_EINVAL, "%s: n_step %d (>= 1)", who, r.n_max);
+  if (int rc = drqn_pop_args(who, MZ_DRQN_HIDDEN, P, u.E, "E")) return rc;
+  return drqn_seq_args(who, u.E, u.L, u.cap);
+}
+static MzDrqnUnroll drqn_returns(int32_t E, int32_t L, int64_t capacity, const uint32_t* mem_dev,
+                                 const int32_t* mem_term_dev, const float* qa_dev, float* y_dev,
+                                 float* d_dev, double* ep_loss_dev) {
+  return MzDrqnUnroll{MzDrqnNet{}, 0, E, L, capacity, 0.0f, mem_dev, mem_term_dev, nullptr, nullptr,
+                      const_cast<float*>(qa_dev), y_dev, d_dev, ep_loss_dev, nullptr};
+}
+
+int mz_drqn_pop_seq_forward_q(const float* params_dev, int32_t hidden, int32_t target, int32_t P,
+                              int32_t E, int32_t L, int64_t capacity, const int32_t* due_dev,
+                              const uint32_t* mem_dev, const int32_t* dir_slot_dev,
+                              const int32_t* dir_len_dev, const int64_t* dir_off_dev,
+                              const int64_t* dir_tot_dev, float* q4_dev, float* stash_dev,
+                              float* qa_dev, int32_t* sel_dev, void* stream) {
+  const char* who = "mz_drqn_pop_seq_forward_q";
+  const MzDrqnSeq q{drqn_forward_q(params_dev, target, E, L, capacity, mem_dev, stash_dev, qa_dev),
+                    dir_slot_dev, dir_len_dev, dir_off_dev, dir_tot_dev};
+  const MzDrqnQRows x{q4_dev, sel_dev};
+  if (!q.d_slot || !q.d_len || !q.d_off || !q.d_tot) return fail(MZ_EINVAL, "%s: null pointer", who);
+  if (int rc = drqn_forward_q_args(who, hidden, P, q.u, x)) return rc;
+  StreamGuard g(stream);
+  MZ_HIP(mz_launch_drqn_seq_forward_q(MzDrqnPopSeqQ{MzDrqnPopSeq{q, P, nullptr, due_dev}, x},
+                                      static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_drqn_pop_window_forward_q(const float* params_dev, int32_t hidden, int32_t target, int32_t P,
+                                 int32_t E, int32_t L, int32_t T, int32_t K_max, int64_t capacity,
+                                 const int32_t* burn_in_dev, const int32_t* stored_dev,
+                                 const int32_t* due_dev, const uint32_t* mem_dev,
+                                 const float* mem_state_dev, const int32_t* wdir_dev,
+                                 const int64_t* win_off_dev, const int64_t* win_tot_dev,
+                                 float* q4_dev, float* stash_dev, float* qa_dev, int32_t* sel_dev,
+                                 void* stream) {
+  const char* who = "mz_drqn_pop_window_forward_q";
+  const MzDrqnWin q{drqn_forward_q(params_dev, target, E, L, capacity, mem_dev, stash_dev, qa_dev),
+                    T, K_max, mem_state_dev, wdir_dev, win_off_dev, win_tot_dev};
+  const MzDrqnQRows x{q4_dev, sel_dev};
+  if (!burn_in_dev || (mem_state_dev && !stored_dev) || !q.wdir || !q.w_off || !q.w_tot)
+    return fail(MZ_EINVAL, "%s: null pointer", who);
+  if (int rc = drqn_win_args(who, hidden, T, K_max)) return rc;
+  if (int rc = drqn_forward_q_args(who, hidden, P, q.u, x)) return rc;
+  StreamGuard g(stream);
+  MZ_HIP(mz_launch_drqn_window_forward_q(
+      MzDrqnPopWinQ{MzDrqnPopWin{q, P, nullptr, burn_in_dev, stored_dev, due_dev}, x},
+      static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_drqn_pop_seq_returns(const int32_t* n_step_dev, int32_t n_step_max,
+                            const int32_t* double_dev, const float* gamma_dev,
+                            const int32_t* due_dev, int32_t P, int32_t E, int32_t L,
+                            int64_t capacity, const uint32_t* mem_dev, const int32_t* mem_term_dev,
+                            const int32_t* dir_slot_dev, const int32_t* dir_len_dev,
+                            const int64_t* dir_off_dev, const int64_t* dir_tot_dev,
+                            const float* qa_dev, const float* q4_dev, const int32_t* sel_dev,
+                            float* y_dev, float* d_dev, double* ep_loss_dev, void* stream) {
+  const char* who = "mz_drqn_pop_seq_returns";
+  const MzDrqnSeq q{drqn_returns(E, L, capacity, mem_dev, mem_term_dev, qa_dev, y_dev, d_dev,
+                                 ep_loss_dev), dir_slot_dev, dir_len_dev, dir_off_dev, dir_tot_dev};
+  const MzDrqnReturns r{n_step_dev, n_step_max, double_dev, q4_dev, sel_dev};
+  if (!q.d_slot || !q.d_len || !q.d_off || !q.d_tot) return fail(MZ_EINVAL, "%s: null pointer", who);
+  if (int rc = drqn_returns_args(who, P, q.u, gamma_dev, r)) return rc;
+  StreamGuard g(stream);
+  MZ_HIP(mz_launch_drqn_seq_returns(MzDrqnPopSeqRet{MzDrqnPopSeq{q, P, gamma_dev, due_dev}, r},
+                                    static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
+int mz_drqn_pop_window_returns(const int32_t* n_step_dev, int32_t n_step_max,
+                               const int32_t* double_dev, const float* gamma_dev,
+                               const int32_t* burn_in_dev, const int32_t* due_dev, int32_t P,
+                               int32_t E, int32_t L, int32_t T, int32_t K_max, int64_t capacity,
+                               const uint32_t* mem_dev, const int32_t* mem_term_dev,
+                               const int32_t* wdir_dev, const int64_t* win_off_dev,
+                               const int64_t* win_tot_dev, const float* qa_dev,
+                               const float* q4_dev, const int32_t* sel_dev, float* y_dev,
+                               float* d_dev, double* ep_loss_dev, void* stream) {
+  const char* who = "mz_drqn_pop_window_returns";
+  const MzDrqnWin q{drqn_returns(E, L, capacity, mem_dev, mem_term_dev, qa_dev, y_dev, d_dev,
+                                 ep_loss_dev), T, K_max, nullptr, wdir_dev, win_off_dev, win_tot_dev};
+  const MzDrqnReturns r{n_step_dev, n_step_max, double_dev, q4_dev, sel_dev};
+  if (!burn_in_dev || !q.wdir || !q.w_off || !q.w_tot)
+    return fail(MZ_EINVAL, "%s: null pointer", who);
+  if (int rc = drqn_win_args(who, MZ_DRQN_HIDDEN, T, K_max)) return rc;
+  if (int rc = drqn_returns_args(who, P, q.u, gamma_dev, r)) return rc;
+  StreamGuard g(stream);
+  MZ_HIP(mz_launch_drqn_window_returns(
+      MzDrqnPopWinRet{MzDrqnPopWin{q, P, gamma_dev, burn_in_dev, nullptr, due_dev}, r},
+      static_cast<hipStream_t>(stream)));
+  return MZ_OK;
+}
+
 // ---- prioritized replay windows (mz_drqn.hip k_drqn_prio_store / _sample / _update) -------------
 // what the three share: the window, the sizes, and that every integer the kernels form fits 64
 // bits: capacity ceil(L / T) E 2^30 < 2^63 (a store has no batch: E = 1)

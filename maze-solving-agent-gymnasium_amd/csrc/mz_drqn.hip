@@ -58,6 +58,15 @@
 //                       learner: the sampled windows' new masses from the forward's residuals,
 //                       the slots' sums, and d and ep_loss scaled by the weights. The forward
 //                       and backward kernels are not touched.
+// Double-Q targets and n-step returns (double_q, n_step; off by default, and then none of these is
+// launched): y is formed in a launch of its own between the source forward and the priority update.
+//   k_drqn_seq_fwd_q / k_drqn_win_fwd_q   the forwards' second form (drqn_unroll_fwd<FWD_Q4 /
+//                       FWD_SEL>): the target net writes all four Q'_t of rows row .. row + m, the
+//                       source net its stash, Q_t[a_t] and the first argmax of its own Q_t, one
+//                       step further than the old source mode.
+//   k_drqn_seq_ret / k_drqn_win_ret   one wave per span: the n-step return of every training
+//                       step (float32 fmaf chain, cut at the span's end), bootstrapped from the
+//                       selected or the largest Q', into y; d and ep_loss as the old source mode.
 // Populations (trainers/drqn_population.py VectorRecurrentDQNPopulation): P independent learners
 // over B = P b instances, learner p owning instances [p b, (p + 1) b), flat [P][5252] parameters.
 // Every kernel above but k_drqn_snapshot (which serves B = P b as it is) moves its single-learner
@@ -493,8 +502,22 @@ struct DrqnSpan {
 // The forward time loop of both update kinds. Target mode: max_a Q'_t of the m training steps and
 // of the step after them (rows row .. row + m). Source mode: the stash, Q_t[a_t], y_t, the
 // residual scaled by 2 / tot[1] and the span's sum of squared residuals (float64, time order).
+// FORM is fixed at compile time. FWD_MAX is the two modes above, chosen by q.target. The other two
+// serve double-Q targets and n-step returns, where y is formed afterwards (drqn_returns_body):
+// FWD_Q4 is the target mode writing all four Q'_t of a row to x.q4 instead of their max; FWD_SEL
+// the source mode that unrolls one step further (x_{s+m}, from its own state), writes the first
+// argmax of its own Q_t to x.sel for rows row .. row + m, the stash and Q_t[a_t] for the training
+// rows, and neither y, d nor ep_loss. The extra step has no stash row and no loss term.
+enum { FWD_MAX = 0, FWD_Q4 = 1, FWD_SEL = 2 };
+// whether the form runs the target mode's loop (FWD_MAX: the runtime flag, as before the forms)
+template <int FORM>
+__device__ __forceinline__ int drqn_fwd_target(const MzDrqnUnroll& q) {
+  return FORM == FWD_Q4 ? 1 : (FORM == FWD_MAX ? q.target : 0);
+}
+template <int FORM>
 __device__ __forceinline__ void drqn_unroll_fwd(const MzDrqnUnroll& q, const int e,
-                                                const DrqnSpan& w, const int64_t* tot) {
+                                                const DrqnSpan& w, const int64_t* tot,
+                                                const MzDrqnQRows& x) {
   __shared__ __attribute__((aligned(16))) float hs[H];
   const int lane = threadIdx.x, u = lane & (H - 1), half = lane >> 5;
   const uint32_t* ep = q.mem + ((size_t)w.slot * (q.L + 1) + w.b) * ROW;
@@ -506,12 +529,14 @@ __device__ __forceinline__ void drqn_unroll_fwd(const MzDrqnUnroll& q, const int
   for (int k = 0; k < H; ++k) hb[k] = w.snap ? w.snap[k] : 0.0f;
   float c = w.snap ? w.snap[H + u] : 0.0f;
   float h = w.snap ? w.snap[u] : 0.0f;
-  const int steps = w.kb + w.m + (q.target ? 1 : 0);
-  const float inv = q.target ? 0.0f : (float)(1.0 / (double)tot[1]);
-  const bool term = q.mem_term[w.slot] != 0;
+  // (FWD_SEL runs the target mode's extra step and, as it, needs neither 1 / tot[1] nor term)
+  const int steps = w.kb + w.m + (FORM == FWD_MAX ? (q.target ? 1 : 0) : 1);
+  const float inv = FORM != FWD_MAX ? 0.0f : (q.target ? 0.0f : (float)(1.0 / (double)tot[1]));
+  const bool term = FORM != FWD_MAX ? false : q.mem_term[w.slot] != 0;
   double sq = 0.0;
   for (int i = 0;; ++i) {
-    if (w.entry && !q.target && i == w.kb) {  // the state entering the first training step
+    // the state entering the first training step
+    if (w.entry && !drqn_fwd_target<FORM>(q) && i == w.kb) {
       float* st = q.stash + (size_t)(w.row - 1) * STASH;
       if (!half) st[G4 + u] = c; else st[G4 + H + u] = h;
     }
@@ -523,7 +548,21 @@ __device__ __forceinline__ void drqn_unroll_fwd(const MzDrqnUnroll& q, const int
     if (i < w.kb) continue;  // burn-in: no q, no loss term
     drqn_fwd_head(lw, hb, q0, q1, q2, q3);
     const int64_t R = w.row + (i - w.kb);
-    if (q.target) {
+    if (FORM == FWD_Q4) {
+      if (lane == 0) reinterpret_cast<float4*>(x.q4)[R] = make_float4(q0, q1, q2, q3);
+      continue;
+    }
+    if (FORM == FWD_SEL) {
+      // the acting kernel's greedy rule: the first maximum; a NaN row selects 0
+      const float qv[4] = {q0, q1, q2, q3};
+      int a = 0;
+#pragma unroll
+      for (int k = 1; k < 4; ++k)
+        if (qv[k] > qv[a]) a = k;
+      if (lane == 0) x.sel[R] = a;
+      if (i - w.kb >= w.m) continue;  // the step after the last training step
+    }
+    if (drqn_fwd_target<FORM>(q)) {
       if (lane == 0) q.qmax[R] = fmaxf(fmaxf(q0, q1), fmaxf(q2, q3));
       continue;
     }
@@ -534,6 +573,10 @@ __device__ __forceinline__ void drqn_unroll_fwd(const MzDrqnUnroll& q, const int
     const int a = (int)rb.z & 3;
     const float rew = __uint_as_float(rb.w);
     const float qsel = a == 0 ? q0 : (a == 1 ? q1 : (a == 2 ? q2 : q3));
+    if (FORM == FWD_SEL) {
+      if (lane == 0) q.qa[R] = qsel;
+      continue;
+    }
     const bool last = w.b + i == w.n - 1;
     const float y = (last && term) ? rew : fmaf(q.gamma, q.qmax[R + 1], rew);
     const float d = qsel - y;
@@ -544,7 +587,7 @@ __device__ __forceinline__ void drqn_unroll_fwd(const MzDrqnUnroll& q, const int
       q.d[R] = 2.0f * d * inv;
     }
   }
-  if (!q.target && lane == 0) q.ep_loss[e] = sq;
+  if (FORM == FWD_MAX && !drqn_fwd_target<FORM>(q) && lane == 0) q.ep_loss[e] = sq;
 }
 
 // learner p's view of what both update kinds share: its parameters, ring, discount factor and row
@@ -595,7 +638,7 @@ __global__ __launch_bounds__(WAVE) void k_drqn_seq_fwd(MzDrqnPopSeq q) {
   if (q.due && q.due[p] == 0) return;
   const MzDrqnSeq s = drqn_seq_row(q, p);
   DrqnSpan w;
-  if (drqn_episode(s, e, &w)) drqn_unroll_fwd(s.u, e, w, s.d_tot);
+  if (drqn_episode(s, e, &w)) drqn_unroll_fwd<FWD_MAX>(s.u, e, w, s.d_tot, MzDrqnQRows{});
 }
 
 // ---- back-propagation through time -----------------------------------------------------------
@@ -985,7 +1028,7 @@ __global__ __launch_bounds__(WAVE) void k_drqn_win_fwd(MzDrqnPopWin q) {
   if (q.due && q.due[p] == 0) return;
   const MzDrqnWin s = drqn_win_row(q, p);
   DrqnSpan w;
-  if (drqn_window(s, e, &w)) drqn_unroll_fwd(s.u, e, w, s.w_tot);
+  if (drqn_window(s, e, &w)) drqn_unroll_fwd<FWD_MAX>(s.u, e, w, s.w_tot, MzDrqnQRows{});
 }
 
 __global__ __launch_bounds__(WAVE) void k_drqn_win_bwd(MzDrqnPopWin q) {
@@ -998,6 +1041,116 @@ __global__ __launch_bounds__(WAVE) void k_drqn_win_bwd(MzDrqnPopWin q) {
     return;
   }
   drqn_unroll_bwd(s.u, e, w);
+}
+
+// ---- double-Q targets and n-step returns ---------------------------------------------------
+// The update's chain when a learner leaves the defaults: the target forward in FWD_Q4, the source
+// forward in FWD_SEL, then k_drqn_*_ret, which forms y, d and ep_loss; the priority update and the
+// backward follow unchanged. The old forwards are not part of that chain and keep their code.
+template <int FORM>
+__global__ __launch_bounds__(WAVE) void k_drqn_seq_fwd_q(MzDrqnPopSeqQ q) {
+  const int E = q.q.q.u.E, p = blockIdx.x / E, e = blockIdx.x % E;
+  if (q.q.due && q.q.due[p] == 0) return;
+  const MzDrqnSeq s = drqn_seq_row(q.q, p);
+  const size_t rows = (size_t)E * (s.u.L + 1);
+  const MzDrqnQRows x{q.x.q4 ? q.x.q4 + p * rows * 4 : nullptr, q.x.sel ? q.x.sel + p * rows : nullptr};
+  DrqnSpan w;
+  if (drqn_episode(s, e, &w)) drqn_unroll_fwd<FORM>(s.u, e, w, s.d_tot, x);
+}
+
+template <int FORM>
+__global__ __launch_bounds__(WAVE) void k_drqn_win_fwd_q(MzDrqnPopWinQ q) {
+  const int E = q.q.q.u.E, p = blockIdx.x / E, e = blockIdx.x % E;
+  if (q.q.due && q.q.due[p] == 0) return;
+  const MzDrqnWin s = drqn_win_row(q.q, p);
+  const size_t rows = (size_t)E * (min(s.T, s.u.L) + MZ_DRQN_WIN_PAD);
+  const MzDrqnQRows x{q.x.q4 ? q.x.q4 + p * rows * 4 : nullptr, q.x.sel ? q.x.sel + p * rows : nullptr};
+  DrqnSpan w;
+  if (drqn_window(s, e, &w)) drqn_unroll_fwd<FORM>(s.u, e, w, s.w_tot, x);
+}
+
+// One wave per span, after both forwards. Lane i takes training rows i, i + 64, ...: for training
+// step t = s + i (s = b + kb) the return runs over k = min(N, m - i) rewards, up to step u = t + k,
+// which the span's end cuts: no reward past row m - 1 is read, and the rows of q4 and sel end with
+// the guard row. In float32 and in this order:
+//   acc = no_boot ? r_{u-1} : fmaf(gamma, boot, r_{u-1});  acc = fmaf(gamma, acc, r_j), j = u-2 .. t
+// boot = q4[u][sel[u]] when the learner is double, else max_a q4[u][a] (the old forward's fmaxf
+// tree); no_boot where u is the end of a terminated episode. y = acc, d = 2 (qa - y) / tot[1], and
+// ep_loss[e] the float64 sum of the squared residuals in time order, each round of 64 rows taken
+// lane by lane (drqn_prio_update_body's idiom). N = 1 is the old source forward's arithmetic, op
+// for op. No atomics.
+__device__ __forceinline__ void drqn_returns_body(const MzDrqnUnroll& q, const float* q4,
+                                                  const int32_t* sel, const int N, const int e,
+                                                  const DrqnSpan& w, const int64_t* tot) {
+  const int lane = threadIdx.x;
+  const int s = w.b + w.kb;
+  const uint32_t* ep = q.mem + ((size_t)w.slot * (q.L + 1) + s) * ROW;  // row i: training step i
+  const float inv = (float)(1.0 / (double)tot[1]);
+  const bool term = q.mem_term[w.slot] != 0;
+  double sq = 0.0;
+  for (int i0 = 0; i0 < w.m; i0 += WAVE) {
+    const int i = i0 + lane;
+    float d = 0.0f;
+    if (i < w.m) {
+      const int u = i + min(N, w.m - i);  // 1 .. m, relative to s
+      float acc = __uint_as_float(ep[(size_t)(u - 1) * ROW + 7]);
+      if (!(s + u == w.n && term)) {
+        const int64_t Ru = w.row + u;
+        const float4 v = reinterpret_cast<const float4*>(q4)[Ru];
+        float boot;
+        if (sel) {
+          const int a = sel[Ru] & 3;
+          boot = a == 0 ? v.x : (a == 1 ? v.y : (a == 2 ? v.z : v.w));
+        } else {
+          boot = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
+        }
+        acc = fmaf(q.gamma, boot, acc);
+      }
+      for (int j = u - 2; j >= i; --j)
+        acc = fmaf(q.gamma, acc, __uint_as_float(ep[(size_t)j * ROW + 7]));
+      const int64_t R = w.row + i;
+      d = q.qa[R] - acc;
+      q.y[R] = acc;
+      q.d[R] = 2.0f * d * inv;
+    }
+    const int cnt = min(WAVE, w.m - i0);
+    for (int j = 0; j < cnt; ++j) {
+      const float v = __shfl(d, j);
+      sq += (double)v * (double)v;
+    }
+  }
+  if (lane == 0) q.ep_loss[e] = sq;
+}
+
+// learner p's n, rows of q4 and (where it is double) of sel
+__device__ __forceinline__ int drqn_returns_row(const MzDrqnReturns& r, const int p,
+                                                const size_t rows, const float** q4,
+                                                const int32_t** sel) {
+  *q4 = r.q4 + p * rows * 4;
+  *sel = (r.sel && (!r.dbl || r.dbl[p] != 0)) ? r.sel + p * rows : nullptr;
+  return min(max(r.n_step[p], 1), r.n_max);
+}
+
+__global__ __launch_bounds__(WAVE) void k_drqn_seq_ret(MzDrqnPopSeqRet q) {
+  const int E = q.q.q.u.E, p = blockIdx.x / E, e = blockIdx.x % E;
+  if (q.q.due && q.q.due[p] == 0) return;
+  const MzDrqnSeq s = drqn_seq_row(q.q, p);
+  const float* q4;
+  const int32_t* sel;
+  const int N = drqn_returns_row(q.r, p, (size_t)E * (s.u.L + 1), &q4, &sel);
+  DrqnSpan w;
+  if (drqn_episode(s, e, &w)) drqn_returns_body(s.u, q4, sel, N, e, w, s.d_tot);
+}
+
+__global__ __launch_bounds__(WAVE) void k_drqn_win_ret(MzDrqnPopWinRet q) {
+  const int E = q.q.q.u.E, p = blockIdx.x / E, e = blockIdx.x % E;
+  if (q.q.due && q.q.due[p] == 0) return;
+  const MzDrqnWin s = drqn_win_row(q.q, p);
+  const float* q4;
+  const int32_t* sel;
+  const int N = drqn_returns_row(q.r, p, (size_t)E * (min(s.T, s.u.L) + MZ_DRQN_WIN_PAD), &q4, &sel);
+  DrqnSpan w;
+  if (drqn_window(s, e, &w)) drqn_returns_body(s.u, q4, sel, N, e, w, s.w_tot);
 }
 
 // ---- prioritized replay windows ------------------------------------------------------------
@@ -1343,6 +1496,31 @@ hipError_t mz_launch_drqn_window_forward(const MzDrqnPopWin& q, hipStream_t s) {
 
 hipError_t mz_launch_drqn_window_backward(const MzDrqnPopWin& q, hipStream_t s) {
   hipLaunchKernelGGL(k_drqn_win_bwd, dim3((unsigned)q.P * q.q.u.E), dim3(WAVE), 0, s, q);
+  return hipGetLastError();
+}
+
+// ---- double-Q targets and n-step returns ----------------------------------------------------
+hipError_t mz_launch_drqn_seq_forward_q(const MzDrqnPopSeqQ& q, hipStream_t s) {
+  const dim3 grid((unsigned)q.q.P * q.q.q.u.E);
+  if (q.q.q.u.target) hipLaunchKernelGGL(k_drqn_seq_fwd_q<FWD_Q4>, grid, dim3(WAVE), 0, s, q);
+  else hipLaunchKernelGGL(k_drqn_seq_fwd_q<FWD_SEL>, grid, dim3(WAVE), 0, s, q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_window_forward_q(const MzDrqnPopWinQ& q, hipStream_t s) {
+  const dim3 grid((unsigned)q.q.P * q.q.q.u.E);
+  if (q.q.q.u.target) hipLaunchKernelGGL(k_drqn_win_fwd_q<FWD_Q4>, grid, dim3(WAVE), 0, s, q);
+  else hipLaunchKernelGGL(k_drqn_win_fwd_q<FWD_SEL>, grid, dim3(WAVE), 0, s, q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_seq_returns(const MzDrqnPopSeqRet& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_seq_ret, dim3((unsigned)q.q.P * q.q.q.u.E), dim3(WAVE), 0, s, q);
+  return hipGetLastError();
+}
+
+hipError_t mz_launch_drqn_window_returns(const MzDrqnPopWinRet& q, hipStream_t s) {
+  hipLaunchKernelGGL(k_drqn_win_ret, dim3((unsigned)q.q.P * q.q.q.u.E), dim3(WAVE), 0, s, q);
   return hipGetLastError();
 }
 

@@ -334,6 +334,35 @@ struct MzDrqnPopPrioUpdate {
   const int32_t* due;                        // [P]
   const double* alpha; const double* eta; const double* eps;  // [P]; null: u.alpha, u.eta, u.eps
 };
+// Double-Q targets and n-step returns: the forwards' second form and the kernel that forms y, d and
+// ep_loss from their rows. q4 [P][rows][4]: the target net's four Q' of a row; sel [P][rows]: the
+// first argmax of the source net's own Q. Both cover a span's rows row .. row + m. The embedded
+// forward structs are filled as for the old forwards, with qmax, y, d and ep_loss null there.
+struct MzDrqnQRows {
+  float* q4; int32_t* sel;                   // target form: q4 out; source form: sel out
+};
+struct MzDrqnPopSeqQ {
+  MzDrqnPopSeq q; MzDrqnQRows x;
+};
+struct MzDrqnPopWinQ {
+  MzDrqnPopWin q; MzDrqnQRows x;
+};
+struct MzDrqnReturns {
+  const int32_t* n_step; int n_max;          // [P]; a value outside 1 .. n_max counts as the nearer bound
+  const int32_t* dbl;                        // [P], 0 = bootstrap from max q4 (null: all read sel)
+  const float* q4; const int32_t* sel;       // sel null: every learner bootstraps from max q4
+};
+struct MzDrqnPopSeqRet {
+  MzDrqnPopSeq q; MzDrqnReturns r;           // q.q.u: mem, mem_term, qa (in), y, d, ep_loss (out)
+};
+struct MzDrqnPopWinRet {
+  MzDrqnPopWin q; MzDrqnReturns r;
+};
+// target != 0 in the embedded struct: the target form
+hipError_t mz_launch_drqn_seq_forward_q(const MzDrqnPopSeqQ& q, hipStream_t s);
+hipError_t mz_launch_drqn_window_forward_q(const MzDrqnPopWinQ& q, hipStream_t s);
+hipError_t mz_launch_drqn_seq_returns(const MzDrqnPopSeqRet& q, hipStream_t s);
+hipError_t mz_launch_drqn_window_returns(const MzDrqnPopWinRet& q, hipStream_t s);
 hipError_t mz_launch_drqn_prio_store(const MzDrqnPopPrioStore& q, int blocks, hipStream_t s);
 hipError_t mz_launch_drqn_prio_sample(const MzDrqnPopPrioSample& q, hipStream_t s);
 hipError_t mz_launch_drqn_prio_update(const MzDrqnPopPrioUpdate& q, hipStream_t s);

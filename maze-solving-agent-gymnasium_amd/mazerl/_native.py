@@ -59,6 +59,8 @@ EXPORTS = ["mz_last_error", "mz_device_count", "mz_create", "mz_destroy", "mz_lo
            "mz_drqn_pop_sync", "mz_drqn_pop_snap_store", "mz_drqn_pop_window_sample",
            "mz_drqn_pop_window_forward", "mz_drqn_pop_window_backward",
            "mz_drqn_pop_prio_store", "mz_drqn_pop_prio_sample", "mz_drqn_pop_prio_update",
+           "mz_drqn_pop_seq_forward_q", "mz_drqn_pop_window_forward_q",
+           "mz_drqn_pop_seq_returns", "mz_drqn_pop_window_returns",
            "mz_adamw_pop", "mz_qact_prepare", "mz_qact",
            "mz_qact_workspace_floats", "mz_qtab_states", "mz_qtab_act", "mz_qtab_update",
            "mz_qtab_hash_act", "mz_qtab_hash_update", "mz_qtab_hash_rehash", "mz_qtab_hash_lookup",
@@ -230,6 +232,12 @@ def load(build_if_missing=True):
     L.mz_drqn_pop_prio_store.argtypes = [C.c_int32] * 5 + [vp] * 3 + [C.c_int64] + [vp] * 5
     L.mz_drqn_pop_prio_sample.argtypes = [vp] * 5 + [C.c_int32] * 6 + [C.c_int64] + [vp] * 8
     L.mz_drqn_pop_prio_update.argtypes = [vp] * 4 + [C.c_int32] * 5 + [C.c_int64] + [vp] * 12
+    L.mz_drqn_pop_seq_forward_q.argtypes = [vp] + [C.c_int32] * 5 + [C.c_int64] + [vp] * 11
+    L.mz_drqn_pop_window_forward_q.argtypes = [vp] + [C.c_int32] * 7 + [C.c_int64] + [vp] * 13
+    L.mz_drqn_pop_seq_returns.argtypes = [vp, C.c_int32] + [vp] * 3 + [C.c_int32] * 3 + \
+        [C.c_int64] + [vp] * 13
+    L.mz_drqn_pop_window_returns.argtypes = [vp, C.c_int32] + [vp] * 4 + [C.c_int32] * 5 + \
+        [C.c_int64] + [vp] * 12
     L.mz_adamw_pop.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int64, vp, vp, vp, C.c_double,
                                C.c_double, C.c_double, C.c_double, C.c_float, C.c_float,
                                C.c_int32, vp]

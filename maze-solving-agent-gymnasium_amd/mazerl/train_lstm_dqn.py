@@ -18,7 +18,7 @@ stored | zero starts from the recurrent state recorded while acting or from zero
 --learners P trains P independent learners in one run (trainers/drqn_population.py), each on
 envs / P instances; --seeds and --sweep NAME=v1,v2,... (repeatable; NAME one of lr, gamma,
 eps-start, eps-final, eps-decay, target-update, seed, burn-in, initial-state, priority-alpha,
-priority-beta, priority-eta, priority-eps; P values or one) set them apart. The final line then
+priority-beta, priority-eta, priority-eps, double-q, n-step; P values or one) set them apart. The final line then
 reports every learner's trained greedy win-rate on the same mazes, their mean and spread, and every
 learner's window and priority settings.
 
@@ -45,6 +45,14 @@ settings beside its greedy win rate (by_learner).
       --sweep priority-alpha=none,none,none,none,0,0,0,0,0.9,0.9,0.9,0.9 \\
       --sweep priority-beta=0.6,0.6,0.6,0.6,0,0,0,0,0.6,0.6,0.6,0.6 --seeds 0,1,2,3,0,1,2,3,0,1,2,3
 
+--double-q bootstraps from the target net's value of the source net's own greedy action (double
+Q-learning, departure 13); --n-step N forms N-step returns, cut at the end of an episode or of a
+window (departure 14). Both work with whole episodes and with windows, uniform or prioritized; with
+--learners they apply to every learner unless --sweep double-q=0,1,... or --sweep n-step=1,3,5,...
+sets them per learner. The final line lists both per learner.
+
+  python -m mazerl.train_lstm_dqn --dim 41 --window 40 --burn-in 40 --double-q --n-step 5
+
 --archive C keeps the mazes the run trains on in a MazePool of C entries (with --learners: one
 pool of C entries per learner, all filled by one launch per vector step) and the final line gains
 the greedy win rate on its oldest --explored-mazes entries, the reference's test(n, new=False)
@@ -56,8 +64,8 @@ import json
 import torch
 
 from .archive import add_pool_arguments, check_pool_arguments
-from .trainers.drqn_trainer import (VectorRecurrentDQNTrainer, check_priority, check_window,
-                                    evaluate_plain)
+from .trainers.drqn_trainer import (VectorRecurrentDQNTrainer, check_priority, check_returns,
+                                    check_window, evaluate_plain)
 from .trainers.episodic import episode_bound
 from .trainers.vector_trainer import evaluate_explored
 from .vector_env import VectorMazeEnv
@@ -73,6 +81,13 @@ def state(v):
 def alpha(v):
     """A priority-alpha value of a sweep: a number, or none (that learner is not prioritized)."""
     return None if v.strip().lower() == "none" else float(v)
+
+
+def flag(v):
+    """A double-q value of a sweep: 0 or 1."""
+    if v.strip() not in ("0", "1"):
+        raise ValueError(v)
+    return v.strip() == "1"
 
 
 def beta(v):
@@ -93,7 +108,8 @@ SWEEPABLE = {"lr": ("lr", float), "gamma": ("discount_factor", float),
              "eps-decay": ("epsilon_decay", float), "target-update": ("target_update_frequency", int),
              "seed": ("seed", int), "burn-in": ("burn_in", int), "initial-state": ("initial_state", state),
              "priority-alpha": ("priority_alpha", alpha), "priority-beta": ("priority_beta", beta),
-             "priority-eta": ("priority_eta", float), "priority-eps": ("priority_eps", float)}
+             "priority-eta": ("priority_eta", float), "priority-eps": ("priority_eps", float),
+             "double-q": ("double_q", flag), "n-step": ("n_step", int)}
 
 
 def parse_sweeps(sweeps, seeds, P):
@@ -169,12 +185,16 @@ def parse_args(argv=None):
     ap.add_argument("--priority-eta", type=float, default=0.9, metavar="H",
                     help="a window's priority: H max + (1 - H) mean of its |TD errors|")
     ap.add_argument("--priority-eps", type=float, default=1e-3, metavar="X")
+    ap.add_argument("--double-q", action="store_true",
+                    help="bootstrap from the target net's value of the source net's greedy action")
+    ap.add_argument("--n-step", type=int, default=1, metavar="N",
+                    help="N-step returns, cut at the end of an episode or a window")
     ap.add_argument("--learners", type=int, default=None,
                     help="P independent learners in one run, each on envs / P instances")
     ap.add_argument("--sweep", action="append", default=None, metavar="NAME=v1,v2,...",
                     help="per-learner values (P or one) of lr, gamma, eps-start, eps-final, "
-                         "eps-decay, target-update, seed, burn-in, initial-state or "
-                         "priority-alpha / -beta / -eta / -eps; repeatable")
+                         "eps-decay, target-update, seed, burn-in, initial-state, "
+                         "priority-alpha / -beta / -eta / -eps, double-q or n-step; repeatable")
     ap.add_argument("--seeds", default=None, metavar="s1,s2,...", help="--sweep seed=...")
     add_pool_arguments(ap, "the run (with --learners: each learner)")
     a = ap.parse_args(argv)
@@ -182,6 +202,7 @@ def parse_args(argv=None):
     try:
         check_window(a.window, a.burn_in, a.initial_state)
         check_priority(a.window, a.priority_alpha, a.priority_beta, a.priority_eta, a.priority_eps)
+        check_returns(a.double_q, a.n_step)
     except ValueError as e:
         ap.error(str(e))
     given = [f for f in ("--priority-beta", "--priority-eta", "--priority-eps")
@@ -203,6 +224,8 @@ def parse_args(argv=None):
         for K in a.per_learner.get("burn_in", ()):  # every learner's K_p against the shared T
             check_window(a.window, K, a.initial_state)
         per = a.per_learner
+        for N in per.get("n_step", ()):
+            check_returns(False, N)
         alphas = per.get("priority_alpha", [None] * a.learners)
         for p, al in enumerate(alphas):  # every learner's priority settings against the shared T
             check_priority(a.window, al, *(per[k][p] if k in per else getattr(a, k) for k in
@@ -218,14 +241,16 @@ def parse_args(argv=None):
 
 
 def by_learner(tr, rates):
-    """A prioritized population's report: the per-learner priority settings and, learner by
-    learner, its seed and settings beside its greedy win rate. Empty without priorities."""
-    pr = tr._priority_settings()
-    if pr is None:
+    """The report of a population with prioritized learners or learners off the target's defaults:
+    the per-learner settings and, learner by learner, its seed and settings beside its greedy win
+    rate. Empty without either."""
+    pr, rt = tr._priority_settings(), tr._returns_settings()
+    if pr is None and rt is None:
         return {}
-    rows = [{"learner": p, "seed": tr.seed[p], **{"priority_" + k: pr[k][p] for k in pr},
-             "win_rate_greedy": rates[p]} for p in range(tr.P)]
-    return {"priority": pr, "by_learner": rows}
+    rows = [{"learner": p, "seed": tr.seed[p], **{"priority_" + k: pr[k][p] for k in pr or ()},
+             "double_q": tr.double_q[p], "n_step": tr.n_step[p], "win_rate_greedy": rates[p]}
+            for p in range(tr.P)]
+    return {**({} if pr is None else {"priority": pr}), "by_learner": rows}
 
 
 def main_population(a):
@@ -237,7 +262,8 @@ def main_population(a):
               epsilon_decay=a.eps_decay, discount_factor=a.gamma,
               target_update_frequency=a.target_update, seed=a.seed, burn_in=a.burn_in,
               initial_state=a.initial_state, priority_beta=a.priority_beta,
-              priority_eta=a.priority_eta, priority_eps=a.priority_eps)
+              priority_eta=a.priority_eta, priority_eps=a.priority_eps, double_q=a.double_q,
+              n_step=a.n_step)
     kw.update(a.per_learner)
     tr = VectorRecurrentDQNPopulation(
         env, dev, learners=a.learners, batch_size=a.batch, memory_size=a.memory,
@@ -267,6 +293,7 @@ def main_population(a):
                       "wins": tr.wins, "updates": tr.updates, "batch_episodes": a.batch,
                       "per_learner": {k: v for k, v in a.per_learner.items()},
                       "window": tr._window_settings(),  # T and every learner's K_p, S_p
+                      "double_q": tr.double_q, "n_step": tr.n_step,
                       **by_learner(tr, after),
                       "replay_bytes": tr.memory_bytes()["replay"],
                       "win_rate_greedy_untrained": before, "win_rate_greedy": after,
@@ -291,7 +318,8 @@ def main(argv=None):
         bank=not a.no_bank, algorithm=a.algo, window=a.window, burn_in=a.burn_in,
         initial_state=a.initial_state, archive=a.archive or None,
         priority_alpha=a.priority_alpha, priority_beta=a.priority_beta,
-        priority_eta=a.priority_eta, priority_eps=a.priority_eps)
+        priority_eta=a.priority_eta, priority_eps=a.priority_eps, double_q=a.double_q,
+        n_step=a.n_step)
     if a.resume:
         from .checkpoint import load_checkpoint
         load_checkpoint(a.resume, tr)
@@ -316,6 +344,7 @@ def main(argv=None):
                       "wins": tr.wins, "updates": tr.updates, "batch_episodes": a.batch,
                       "seed": a.seed, "window": a.window, "burn_in": a.burn_in,
                       "initial_state": a.initial_state if a.window else None,
+                      "double_q": tr.double_q, "n_step": tr.n_step,
                       **({} if a.priority_alpha is None else {"priority": tr._priority_settings()}),
                       "win_rate_greedy_untrained": before,
                       "win_rate_greedy": after, "eval_mazes": a.eval_mazes, "eval_steps": k,

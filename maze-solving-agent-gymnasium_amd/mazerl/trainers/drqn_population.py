@@ -11,7 +11,7 @@ Shared: the env, L = episode_bound, batch_size E, memory_size (capacity, in epis
 train_every, explore_actions. Per learner (a scalar or a length-P sequence): lr, discount_factor,
 starting_epsilon, final_epsilon, epsilon_decay, target_update_frequency, seed.
 
-Learner p is what VectorRecurrentDQNTrainer (drqn_trainer.py: its twelve departures, its
+Learner p is what VectorRecurrentDQNTrainer (drqn_trainer.py: its fourteen departures, its
 accumulation order, Philox streams and ring semantics) is on its b instances with learner p's
 hyper-parameters and seed, bit for bit: both are the same driver over the same kernels, which run
 their device code on learner p's rows. The acting draw of instance i is keyed by (seed_p, counter,
@@ -60,6 +60,17 @@ the one due mask, unchanged. A checkpoint then also holds the per-learner settin
 filled slots of mem_prio and mem_psum, and prio_max; it loads only into a population with the same
 settings, and a checkpoint without them only into a population without priorities.
 
+Double-Q targets and n-step returns (double_q, n_step: each a value or a list of P; with every
+learner at False and 1, the default, this is the population above: nothing of it is allocated or
+launched, the same bits, the same checkpoint keys). Otherwise all due learners go through the
+target net's forward in its four-Q' form, the source net's in its argmax form and one returns
+launch (departures 13-14 with learner p's two values; n_step and the double flag live on the
+device as int32 [P], and the argmax rows are read only when a learner is double and only by such a
+learner), then the priority update where one is due and the unchanged backward. A default learner
+in such a population keeps the default trainer's bits: n_step = 1 without the argmax is its
+arithmetic. q4 [P][rows][4] and sel [P][rows] exist for all learners. A checkpoint then also holds
+the two per-learner lists and loads only into a population with the same ones.
+
 curriculum="global" counts wins across all instances and would couple the learners: it is refused.
 With bank=False a learner's whole run is independent of the other learners, bit for bit. With the
 winner bank the maze a winner receives depends on how many instances of other learners won before
@@ -84,16 +95,17 @@ PER_LEARNER = ("lr", "discount_factor", "starting_epsilon", "final_epsilon", "ep
 BETAS, ADAM_EPS, WEIGHT_DECAY, CLAMP = (0.9, 0.999), 1e-8, 1e-2, 1.0
 
 
-def footprint(P, B, L, E, capacity, window=None, stored=False, prio=False):
+def footprint(P, B, L, E, capacity, window=None, stored=False, prio=False, returns=False):
     """Bytes of the replay rings, the in-flight records, and an update's stash and row buffers;
     windowed: the row buffers hold E (min(T, L) + 2) rows, and with stored state the state memory
     (P capacity ceil(L / T) snapshots of 256 B) and the in-flight snapshots are added; prioritized:
     the masses (P capacity ceil(L / T) words and a 64-bit sum per slot), prio_max, the importance
-    weights and the three float64 settings per learner."""
+    weights and the three float64 settings per learner; with double-Q targets or n-step returns:
+    four Q' and an argmax per row."""
     rows = E * (L + 1) if window is None else E * (min(window, L) + 2)
     ring = P * capacity * ((L + 1) * ROW * 4 + 8)
     records = B * ((L + 1) * 6 * 4 + L * 4 + L * 8)
-    update = P * (rows * (STASH + 4) * 4 + E * (PARAMS * 4 + 8 + 16))
+    update = P * (rows * (STASH + 4 + (5 if returns else 0)) * 4 + E * (PARAMS * 4 + 8 + 16))
     out = {"replay": ring, "records": records, "update": update,
            "total": ring + records + update}
     if window is not None:
@@ -131,11 +143,12 @@ class VectorRecurrentDQNPopulation(RecurrentDQNBase):
                  target_update_frequency=10, explore_actions=4, train_every=1, seed=0, bank=True,
                  curriculum=False, growth=None, algorithm="r-prim", bank_candidates=1, window=None,
                  burn_in=0, initial_state="stored", archive=None, priority_alpha=None,
-                 priority_beta=0.6, priority_eta=0.9, priority_eps=1e-3):
+                 priority_beta=0.6, priority_eta=0.9, priority_eps=1e-3, double_q=False, n_step=1):
         """archive (None: off): an int C or a MazePoolSet of this env with one group per learner
         — every learner's explored mazes in a pool of C entries of its own, all filled by one
         launch per vector step (evaluate_explored_all). priority_alpha .. priority_eps: prioritized
-        replay windows per learner (the module's docstring; every alpha None: off)."""
+        replay windows per learner (the module's docstring; every alpha None: off). double_q,
+        n_step: double-Q targets and n-step returns per learner (every learner False and 1: off)."""
         P = int(learners)
         if P < 1 or env.num_envs % P:
             raise ValueError(f"env.num_envs {env.num_envs} must be a multiple of learners {P} >= 1")
@@ -145,10 +158,11 @@ class VectorRecurrentDQNPopulation(RecurrentDQNBase):
         self._configure(P, env.num_envs, lr, starting_epsilon, final_epsilon, epsilon_decay,
                         discount_factor, batch_size, memory_size, target_update_frequency,
                         explore_actions, train_every, seed, window, burn_in, initial_state,
-                        priority_alpha, priority_beta, priority_eta, priority_eps)
+                        priority_alpha, priority_beta, priority_eta, priority_eps, double_q, n_step)
         B, E = env.num_envs, self.batch_size
         L = episode_bound(env.max_dim, env.toroidal)
-        need = footprint(P, B, L, E, self.capacity, self.window, any(self.stored), any(self.prio))
+        need = footprint(P, B, L, E, self.capacity, self.window, any(self.stored), any(self.prio),
+                         self._returns)
         dev = torch.device(device)
         if dev.type == "cuda":
             free, _ = torch.cuda.mem_get_info(dev)
@@ -183,7 +197,7 @@ class VectorRecurrentDQNPopulation(RecurrentDQNBase):
     def memory_bytes(self):
         """The replay, record, stash and row-buffer footprint in bytes (footprint())."""
         return footprint(self.P, self.env.num_envs, self.L, self.batch_size, self.capacity,
-                         self.window, any(self.stored), any(self.prio))
+                         self.window, any(self.stored), any(self.prio), self._returns)
 
     def learner_state_dict(self, p):
         """Learner p's source net as the state_dict agents/lstm_dqn_agent.DQN and the reference's

@@ -94,6 +94,29 @@ bit (tests/drqn_prio_model.py). With W = ceil(L / T):
      recomputed from its W entries. Then the residuals d and the window's loss term are scaled by
      w_e, so the unchanged backward gives the gradient and value of loss = sum_e w_e sum_t
      (Q_t[a_t] - y_t)^2 / sum m.
+Double-Q targets and n-step returns (R2D2's remaining pieces; the feed-forward DDQN's estimator)
+are the options double_q=True and n_step=N, with whole episodes or windows, uniform or prioritized.
+double_q=False, n_step=1 is the trainer above: nothing below is allocated or launched. A span is
+what one wave unrolls: training steps s .. s + m - 1 of an n-step episode (a whole episode: s = 0,
+m = n; a window: s = j T, m = min(T, n - s), after its burn-in). Off the defaults the target net
+writes all four Q'_u of the span's steps s .. s + m, the source net its stash and Q_t[a_t] as
+before, and mz_drqn_pop_seq_returns / mz_drqn_pop_window_returns forms y, d and the loss terms
+between the source forward and the priority update (which then reads the new y) or the backward:
+ 13. double_q: the bootstrap value at step u is Q'_u[a*_u], a*_u = argmax_a Q_u[a] with the source
+     net's Q at the update's own parameters; the first maximum in action order, 0 for a NaN row (the
+     acting kernel's rule). For that the source net unrolls one step further than above, x_{s+m},
+     continuing from its own state; the extra step has no stash row, no loss term and no gradient,
+     and the selection is a constant of the loss. Both nets still start at step b from the same
+     state (9);
+ 14. n_step = N: for training step t of a span, k = min(N, s + m - t) and u = t + k: the return is
+     cut at the span's end, no reward past a window's end is read and only the guard row's Q' is
+     used there. boot = Q'_u[a*_u] when double, else max_a Q'_u[a]; no bootstrap where u = n and
+     the episode terminated (a truncated one bootstraps from x_n as above). In float32, in this
+     order: acc = r_{u-1} without bootstrap, else fmaf(gamma, boot, r_{u-1}); acc = fmaf(gamma, acc,
+     r_i) for i = u - 2 down to t; y_t = acc. N = 1 is departure 5's and 9's expression, op for op,
+     so a default learner beside others in a population keeps the default trainer's bits. The
+     residuals, the loss and a prioritized window's mass follow from y_t as above.
+R2D2's value rescaling h(x) is out of scope.
 The vector step and the update above are written once, for P learners over the mz_drqn_pop_* entry
 points: RecurrentDQNBase below. VectorRecurrentDQNPopulation (drqn_population.py) is that driver
 with P learners, each with its own values of the per-learner arguments (T shared; K, the initial
@@ -166,6 +189,14 @@ def check_priority(window, alpha, beta, eta, eps):
                          f"{eps!r})")
 
 
+def check_returns(double_q, n_step):
+    """The target's arguments' rules (departures 13-14); ValueError otherwise."""
+    if not isinstance(double_q, bool) or not isinstance(n_step, int) or isinstance(n_step, bool) \
+            or n_step < 1:
+        raise ValueError("double_q: a bool; n_step: an int >= 1 "
+                         f"(got {double_q!r}, {n_step!r})")
+
+
 def per_learner(value, P, name, kind=float):
     """A scalar for all learners or one value per learner -> a list of P."""
     if isinstance(value, (list, tuple, np.ndarray)):
@@ -189,9 +220,10 @@ class _PerLearner:
     RecurrentDQNBase reads and writes; the public attribute is that list for a population and its
     one entry for the single trainer (_ONE). Assigning gamma, seed, burn_in, priority_eta or
     priority_eps (the whole value, not an entry of the list) also renews the copy the kernels read
-    (_mirror). initial_state, stored and priority_alpha fix the buffers and are not to be assigned
-    after construction."""
-    MIRRORED = ("gamma", "seed", "burn_in", "priority_eta", "priority_eps")
+    (_mirror); so does n_step, within a trainer that was built with a learner off the target's
+    defaults (the new values are checked first). initial_state, stored, priority_alpha and double_q
+    fix the buffers and are not to be assigned after construction."""
+    MIRRORED = ("gamma", "seed", "burn_in", "priority_eta", "priority_eps", "n_step")
 
     def __init__(self, name):
         self.key, self.mirrored = "_" + name, name in self.MIRRORED
@@ -203,6 +235,8 @@ class _PerLearner:
         return v[0] if obj._ONE else v
 
     def __set__(self, obj, value):
+        if self.key == "_n_step":
+            obj._check_n_step([value] if obj._ONE else value)
         setattr(obj, self.key, [value] if obj._ONE else value)
         if self.mirrored and hasattr(obj, "upd"):  # (the device arrays exist)
             obj._mirror()
@@ -221,15 +255,22 @@ class RecurrentDQNBase(EpisodicTrainer):
     _ONE = False
     _PER = ("lr", "gamma", "starting_epsilon", "final_epsilon", "epsilon_decay", "seed", "tuf",
             "burn_in", "initial_state", "stored", "priority_beta", "priority_eta", "priority_eps",
-            "steps_done", "updates", "filled", "last_lr")
+            "double_q", "n_step", "steps_done", "updates", "filled", "last_lr")
 
     def _configure(self, P, B, lr, starting_epsilon, final_epsilon, epsilon_decay, discount_factor,
                    batch_size, memory_size, target_update_frequency, explore_actions, train_every,
                    seed, window, burn_in, initial_state, priority_alpha, priority_beta,
-                   priority_eta, priority_eps):
+                   priority_eta, priority_eps, double_q=False, n_step=1):
         """The arguments' checks and the per-learner host values (each argument from lr to seed
         and from burn_in on: a scalar or a length-P sequence). Touches no GPU."""
         same = lambda v: v  # noqa: E731 (the checks want the values as they were given)
+        self._double_q = per_learner(double_q, P, "double_q", same)
+        self._n_step = per_learner(n_step, P, "n_step", same)
+        for dq, ns in zip(self._double_q, self._n_step):
+            check_returns(dq, ns)
+        # whether the update forms its targets in a launch of its own (a learner is off the
+        # defaults): fixed here, as it decides which buffers exist
+        self._returns = any(self._double_q) or any(ns != 1 for ns in self._n_step)
         self._burn_in = per_learner(burn_in, P, "burn_in", same)
         self._initial_state = per_learner(initial_state, P, "initial_state", same)
         for K, S in zip(self._burn_in, self._initial_state):
@@ -272,6 +313,15 @@ class RecurrentDQNBase(EpisodicTrainer):
         self._last_lr = [None] * P
         self.last_due = [False] * P  # the learners the last vector step updated
 
+    def _check_n_step(self, values):
+        """ValueError unless `values` may replace the learners' n_step."""
+        values = per_learner(values, self.P, "n_step", lambda v: v)
+        for ns in values:
+            check_returns(False, ns)
+        if not self._returns and any(ns != 1 for ns in values):
+            raise ValueError("n_step above 1 needs a trainer built with double_q or n_step off "
+                             "their defaults: the default update has no launch that reads it")
+
     @property
     def priority_alpha(self):
         """None when no learner is prioritized, else the learners' alphas (None: uniform)."""
@@ -300,6 +350,9 @@ class RecurrentDQNBase(EpisodicTrainer):
             self.prio_alpha_dev = f64(self._priority_alpha, 0.0)
             self.prio_eta_dev = f64(self._priority_eta, 0.0)
             self.prio_eps_dev = f64(self._priority_eps, 1.0)
+        if self._returns:
+            self.n_step_dev = torch.tensor(self._n_step, dtype=i32, **kw)
+            self.double_dev = torch.tensor([int(v) for v in self._double_q], dtype=i32, **kw)
         self._prio_due = False  # whether the update under way has a due prioritized learner
         self._stage = {}  # (_send's pinned rows)
         if self.window is not None:
@@ -330,6 +383,8 @@ class RecurrentDQNBase(EpisodicTrainer):
         pairs = [(self.gamma_dev, self._gamma), (self.seed_dev, [_signed(s) for s in self._seed])]
         if self.window is not None:
             pairs.append((self.burn_in_dev, self._burn_in))
+        if self._returns:
+            pairs.append((self.n_step_dev, self._n_step))
         if any(self.prio):
             pairs += [(self.prio_eta_dev, [v or 0.0 for v in self._priority_eta]),
                       (self.prio_eps_dev, [1.0 if v is None else v for v in self._priority_eps])]
@@ -378,6 +433,9 @@ class RecurrentDQNBase(EpisodicTrainer):
         self.d_len = torch.zeros(*lead, E, dtype=i32, **kw)
         self.d_off = torch.zeros(*lead, E, dtype=i64, **kw)
         self.d_tot = torch.zeros(*lead, 2, dtype=i64, **kw)
+        if self._returns:  # the target's four Q' of a row and the source's argmax, in qmax's place
+            self.q4 = torch.zeros(*lead, rows, 4, dtype=f32, **kw)
+            self.sel = torch.zeros(*lead, rows, dtype=i32, **kw)
         self.qmax = torch.zeros(*lead, rows, dtype=f32, **kw)
         self.stash = torch.zeros(*lead, rows, STASH, dtype=f32, **kw)
         self.qa = torch.zeros(*lead, rows, dtype=f32, **kw)
@@ -527,6 +585,8 @@ class RecurrentDQNBase(EpisodicTrainer):
         """Every due learner's loss (self.loss, on the device) and gradient (self.grad) on its
         directory's episodes or windows: the target net's forward, the source net's, a prioritized
         learner's new masses and weighted residuals, the backward and its reduction."""
+        if self._returns:
+            return self._gradients_returns()
         P, E, L, cap, st = self.P, self.batch_size, self.L, self.capacity, self._stream()
         due, gam = self.due_dev.data_ptr(), self.gamma_dev.data_ptr()
         rows = (self.stash.data_ptr(), self.qa.data_ptr(), self.y.data_ptr(), self.d.data_ptr(),
@@ -563,6 +623,58 @@ class RecurrentDQNBase(EpisodicTrainer):
             self.src.data_ptr(), HIDDEN, P, E, L, T, K, cap, burn, due, self.mem.data_ptr(), *dirs,
             *back))
 
+    def _gradients_returns(self):
+        """_gradients when a learner is off the target's defaults (departures 13-14), for all due
+        learners: the target net's four Q' per row, the source net's forward with its argmax and
+        one step more, the returns launch that forms y, d and ep_loss (sel only when a learner is
+        double: without it N = 1 is the default chain's arithmetic), then the priority update and
+        the backward as they are."""
+        P, E, L, cap, st = self.P, self.batch_size, self.L, self.capacity, self._stream()
+        due = self.due_dev.data_ptr()
+        fwd = (self.q4.data_ptr(), self.stash.data_ptr(), self.qa.data_ptr(), self.sel.data_ptr(),
+               st)
+        ret = (self.qa.data_ptr(), self.q4.data_ptr(),
+               self.sel.data_ptr() if any(self._double_q) else None, self.y.data_ptr(),
+               self.d.data_ptr(), self.ep_loss.data_ptr(), st)
+        per = (self.n_step_dev.data_ptr(), max(self._n_step), self.double_dev.data_ptr(),
+               self.gamma_dev.data_ptr())
+        back = (self.stash.data_ptr(), self.d.data_ptr(), self.ep_loss.data_ptr(),
+                self.gpart.data_ptr(), self.grad.data_ptr(), self.loss.data_ptr(), st)
+        if self.window is None:
+            dirs = (self.d_slot.data_ptr(), self.d_len.data_ptr(), self.d_off.data_ptr(),
+                    self.d_tot.data_ptr())
+            for net, target in ((self.tgt, 1), (self.src, 0)):
+                N.check(self.lib.mz_drqn_pop_seq_forward_q(
+                    net.data_ptr(), HIDDEN, target, P, E, L, cap, due, self.mem.data_ptr(), *dirs,
+                    *fwd))
+            N.check(self.lib.mz_drqn_pop_seq_returns(
+                *per, due, P, E, L, cap, self.mem.data_ptr(), self.mem_term.data_ptr(), *dirs,
+                *ret))
+            N.check(self.lib.mz_drqn_pop_seq_backward(
+                self.src.data_ptr(), HIDDEN, P, E, L, cap, due, self.mem.data_ptr(), *dirs, *back))
+            return
+        T, K = self.window, max(self._burn_in)
+        state = self.mem_state.data_ptr() if self._state else None
+        burn, stored = self.burn_in_dev.data_ptr(), self.stored_dev.data_ptr()
+        dirs = (self.wdir.data_ptr(), self.d_off.data_ptr(), self.d_tot.data_ptr())
+        for net, target in ((self.tgt, 1), (self.src, 0)):
+            N.check(self.lib.mz_drqn_pop_window_forward_q(
+                net.data_ptr(), HIDDEN, target, P, E, L, T, K, cap, burn, stored, due,
+                self.mem.data_ptr(), state, *dirs, *fwd))
+        N.check(self.lib.mz_drqn_pop_window_returns(
+            *per, burn, due, P, E, L, T, K, cap, self.mem.data_ptr(), self.mem_term.data_ptr(),
+            *dirs, *ret))
+        if self._prio_due:  # on the new y: the new masses; d and ep_loss times the weights
+            N.check(self.lib.mz_drqn_pop_prio_update(
+                self.prio_alpha_dev.data_ptr(), self.prio_eta_dev.data_ptr(),
+                self.prio_eps_dev.data_ptr(), self.due_prio_dev.data_ptr(), HIDDEN, P, E, L, T,
+                cap, *dirs, self.qa.data_ptr(), self.y.data_ptr(), self.d.data_ptr(),
+                self.ep_loss.data_ptr(), self.isw.data_ptr(), self.mem_prio.data_ptr(),
+                self.mem_psum.data_ptr(), self.prio_max.data_ptr(), st))
+        N.check(self.lib.mz_drqn_pop_window_backward(
+            self.src.data_ptr(), HIDDEN, P, E, L, T, K, cap, burn, due, self.mem.data_ptr(), *dirs,
+            *back))
+
     # ---- the settings and the replay half of a checkpoint ---------------------------------------
     def _window_settings(self):
         """T with the burn-in and the initial state (a population's: the per-learner lists); None
@@ -580,9 +692,17 @@ class RecurrentDQNBase(EpisodicTrainer):
              "eta": list(self._priority_eta), "eps": list(self._priority_eps)}
         return {k: v[0] for k, v in s.items()} if self._ONE else s
 
+    def _returns_settings(self):
+        """double_q and n_step (a population's: the per-learner lists); None where every learner
+        has the defaults."""
+        if not any(self._double_q) and all(ns == 1 for ns in self._n_step):
+            return None
+        return {"double_q": copy.copy(self.double_q), "n_step": copy.copy(self.n_step)}
+
     def _check_settings(self, sd):
-        """ValueError unless the checkpoint's window and priority settings are this object's. (A
-        checkpoint from before either option has no such key: window=None, priority_alpha=None.)"""
+        """ValueError unless the checkpoint's window, priority and target settings are this
+        object's. (A checkpoint from before an option has no such key: window=None,
+        priority_alpha=None, double_q=False and n_step=1.)"""
         kind = "trainer" if self._ONE else "population"
         if sd.get("window") != self._window_settings():
             raise ValueError(f"the checkpoint's replay windows {sd.get('window')} differ from this "
@@ -590,6 +710,9 @@ class RecurrentDQNBase(EpisodicTrainer):
         if sd.get("priority") != self._priority_settings():
             raise ValueError(f"the checkpoint's prioritized replay {sd.get('priority')} differs "
                              f"from this {kind}'s {self._priority_settings()}")
+        if sd.get("returns") != self._returns_settings():
+            raise ValueError(f"the checkpoint's targets {sd.get('returns')} differ from this "
+                             f"{kind}'s {self._returns_settings()}")
 
     def _slots(self, k):
         """Buffer k as [P][capacity][...] (the single trainer's has no leading dimension)."""
@@ -614,9 +737,11 @@ class RecurrentDQNBase(EpisodicTrainer):
         self._save_slots(sd, ("mem", "mem_len", "mem_term"))
 
     def _save_options(self, sd):
-        """What the window and priority options add: the settings, the in-flight and the filled
-        slots' snapshots when a learner stores state, the filled slots' masses and sums and
-        prio_max when one is prioritized."""
+        """What the options add: double_q and n_step where a learner leaves their defaults; the
+        window and priority settings, the in-flight and the filled slots' snapshots when a learner
+        stores state, the filled slots' masses and sums and prio_max when one is prioritized."""
+        if self._returns_settings() is not None:
+            sd["returns"] = self._returns_settings()
         if self.window is not None:
             sd["window"] = self._window_settings()
         if self._state:
@@ -676,17 +801,19 @@ class VectorRecurrentDQNTrainer(RecurrentDQNBase):
                  target_update_frequency=10, explore_actions=4, train_every=1, seed=0, bank=True,
                  curriculum=False, growth=None, algorithm="r-prim", bank_candidates=1, window=None,
                  burn_in=0, initial_state="stored", archive=None, priority_alpha=None,
-                 priority_beta=0.6, priority_eta=0.9, priority_eps=1e-3):
+                 priority_beta=0.6, priority_eta=0.9, priority_eps=1e-3, double_q=False, n_step=1):
         """archive: EpisodicTrainer's explored-maze pool (None: off). priority_alpha: prioritized
         replay windows (departures 10-12; None: off, nothing of it is allocated or launched);
         priority_beta: a number, or (beta0, beta1, updates) for a linear schedule over the update
-        count."""
+        count. double_q, n_step: double-Q targets and n-step returns (departures 13-14; False and
+        1: off, the update's launches and bits are those without the arguments)."""
         one = lambda *vs: ([v] for v in vs)  # noqa: E731 (each value is the one learner's)
         self._configure(
             1, getattr(env, "num_envs", 1),
             *one(lr, starting_epsilon, final_epsilon, epsilon_decay, discount_factor), batch_size,
             memory_size, [target_update_frequency], explore_actions, train_every, [seed], window,
-            *one(burn_in, initial_state, priority_alpha, priority_beta, priority_eta, priority_eps))
+            *one(burn_in, initial_state, priority_alpha, priority_beta, priority_eta, priority_eps,
+                 double_q, n_step))
         super().__init__(env, device, bank=bank, curriculum=curriculum, growth=growth,
                          algorithm=algorithm, bank_candidates=bank_candidates, archive=archive)
         torch.manual_seed(seed)
